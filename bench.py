@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the GECCO denoiser forward on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (the forward: `denoised`; `--train`:
+`loss` and the updated `params`, flattened), at most 64 MB in all (a larger array as a fixed, seeded sample).  Inputs, weights and
+the training step's draws are seeded, so two builds run with the same arguments can be compared output for output.
 
 A "step" is one Diffusion.forward (EDMPrecond + LinearLift + 6-layer set transformer) over one batch
 of synthetic clouds resident in HBM: config C2 = B=64, N=2048, d=384, L=6, I=64, H=8.  With N > 1
@@ -276,6 +280,29 @@ def time_events(fn, iters, warmup=2):
     return s.elapsed_time(e) / iters  # ms
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all arrays together
+
+
+def host_copy(tensors):
+    """{name: tensor} -> {name: host copy}: what the timed path computed, taken before anything else reuses its buffers."""
+    return {k: v.detach().to("cpu", copy=True) for k, v in tensors.items()}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: each array as DIR/<name>.npy, float32 (float64 stays float64).  The arrays share DUMP_MAX_BYTES; one
+    larger than its share is written as a fixed, seeded sample of its flattened elements (the same indices on every run, in
+    increasing order), so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() > share:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:share // t.element_size()].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), t.contiguous().numpy())
+
+
 def time_graph_of(fns, reps=8, iters=4):
     """ms per replayed round of the launch sequence `fns` inside a hipGraph of `reps` rounds (HIP events around the
     replays, on the stream the graph is replayed on): no host launch gap inside the timed region — an event pair around
@@ -538,6 +565,7 @@ def train_bench(args, rank, world, dev):
         scaler.update()
         return loss
 
+    torch.manual_seed(200 + rank)   # the loss's sigma and noise draws: the same on every run
     for i in range(max(args.warmup, 1)):
         loss = step(i)
     torch.cuda.synchronize()
@@ -551,6 +579,8 @@ def train_bench(args, rank, world, dev):
     torch.cuda.synchronize()
     dt = gd.max_over_ranks(time.perf_counter() - t0, dev)
     assert torch.isfinite(loss.detach()).all()
+    if args.dump_outputs and rank == 0:   # now: the optimizer timing below steps the parameters again
+        dump_outputs(args.dump_outputs, host_copy({"loss": loss, "params": torch.cat([q.detach().reshape(-1) for q in params])}))
     ms = dt / args.steps * 1e3
     per_layer = 16 * Nt * Dt * Dt + 8 * Nt * I * Dt + 14 * I * Dt * Dt
     fwd_flops = Lt * per_layer + (2 * Nt * 672 * Dt + 12 * Nt * Dt if cond else 12 * Nt * Dt)   # per sample
@@ -867,6 +897,8 @@ def other_config_bench(args, rank, world, dev):
     torch.cuda.synchronize()
     dt = gd.max_over_ranks(time.perf_counter() - t0, dev)
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, host_copy({"denoised": out}))
     ms = dt / args.steps * 1e3
     tf = flops / (ms * 1e-3) / 1e12
     rec = {"metric": "denoiser_fwd_points_per_sec", "value": world * points * args.steps / dt, "unit": "points/s", "n_gpus": world,
@@ -920,7 +952,12 @@ def main():
     ap.add_argument("--force-collective", action="store_true",
                     help="--train: create the (RCCL) process group even for one rank and issue the per-bucket all-reduces in it")
     ap.add_argument("--selftest-launcher", action="store_true", help="N-rank plumbing on gloo with a stand-in step (no GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (rank 0; "
+                         "the inputs are seeded, so the same arguments give the same inputs on every run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become one.  Nothing above touched the GPU (importing torch does not), the ranks are
@@ -991,6 +1028,8 @@ def main():
     torch.cuda.synchronize()
     dt = gd.max_over_ranks(time.perf_counter() - t0, dev)
     assert torch.isfinite(out).all(), "non-finite denoiser output"
+    if args.dump_outputs and rank == 0:   # now: the roofline block below evaluates other modes into the same buffer
+        dump_outputs(args.dump_outputs, host_copy({"denoised": out}))
     dist_rep = distributed_report(dev, local_points_per_sec=B * N * args.steps / local_dt) if world > 1 else None
 
     ms = dt / args.steps * 1e3
