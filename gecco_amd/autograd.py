@@ -1486,7 +1486,7 @@ def _cnx_ln_bwd(z: Tensor, dy: Tensor, ln_w: Tensor, eps: float, patch2: bool):
     B, H, W, Cc = z.shape
     nb = lib.gecco_convnext_ln_bwd_blocks(B, H, W, Cc)
     if nb <= 0:
-        raise _lib.GeccoHipError("convnext LayerNorm backward: C must be 96, 192 or 384")
+        raise _lib.GeccoHipError("convnext LayerNorm backward: C must be 96, 192, 384 or 768")
     dz, parts = torch.empty_like(z), _new(nb, 3 * Cc, like=z)
     _lib.check(lib.gecco_convnext_ln_bwd_f32(_ptr(z), _ptr(dy), _ptr(ln_w), _ptr(dz), _ptr(parts), B, H, W, Cc, eps, int(patch2),
                                              _stream()), "gecco_convnext_ln_bwd_f32")

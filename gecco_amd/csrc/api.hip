@@ -2069,7 +2069,7 @@ int gecco_convnext_dwconv_ln_f32(const float* x, const float* w, const float* bi
                                  int B, int H, int W, int C, float eps, void* stream) {
     if (!x || !w || !bias || !ln_w || !ln_b || !out) return fail(-1, "convnext_dwconv_ln: null argument");
     int rc = cnx_dwconv_ln_launch(x, w, bias, ln_w, ln_b, out, nullptr, B, H, W, C, eps, (hipStream_t)stream);
-    if (rc == -9) return fail(-2, "convnext_dwconv_ln: C must be 96, 192 or 384");
+    if (rc == -9) return fail(-2, "convnext_dwconv_ln: C must be 96, 192, 384 or 768");
     TRY(rc, "convnext_dwconv_ln");
     return 0;
 }
@@ -2100,21 +2100,21 @@ int gecco_convnext_dwconv_ln_train_f32(const float* x, const float* w, const flo
                                        float* out, float* z, int B, int H, int W, int C, float eps, void* stream) {
     if (!x || !w || !bias || !ln_w || !ln_b || !out || !z) return fail(-1, "convnext_dwconv_ln_train: null argument");
     int rc = cnx_dwconv_ln_launch(x, w, bias, ln_w, ln_b, out, z, B, H, W, C, eps, (hipStream_t)stream);
-    if (rc == -9) return fail(-2, "convnext_dwconv_ln_train: C must be 96, 192 or 384");
+    if (rc == -9) return fail(-2, "convnext_dwconv_ln_train: C must be 96, 192, 384 or 768");
     TRY(rc, "convnext_dwconv_ln_train");
     return 0;
 }
 int gecco_convnext_dwconv_f32(const float* x, const float* w, const float* bias, float* out, int B, int H, int W, int C, void* stream) {
     if (!x || !w || !out) return fail(-1, "convnext_dwconv: null argument");
     int rc = cnx_dwconv_ln_launch(x, w, bias, nullptr, nullptr, out, nullptr, B, H, W, C, 0.f, (hipStream_t)stream);
-    if (rc == -9) return fail(-2, "convnext_dwconv: C must be 96, 192 or 384");
+    if (rc == -9) return fail(-2, "convnext_dwconv: C must be 96, 192, 384 or 768");
     TRY(rc, "convnext_dwconv");
     return 0;
 }
 int gecco_convnext_dwconv_bwd_f32(const float* dz, const float* w, const float* add, float* dx, int B, int H, int W, int C, void* stream) {
     if (!dz || !w || !dx) return fail(-1, "convnext_dwconv_bwd: null argument");
     int rc = cnx_dwconv_ln_launch(dz, w, nullptr, nullptr, nullptr, dx, nullptr, B, H, W, C, 0.f, (hipStream_t)stream, add, 1);
-    if (rc == -9) return fail(-2, "convnext_dwconv_bwd: C must be 96, 192 or 384");
+    if (rc == -9) return fail(-2, "convnext_dwconv_bwd: C must be 96, 192, 384 or 768");
     TRY(rc, "convnext_dwconv_bwd");
     return 0;
 }

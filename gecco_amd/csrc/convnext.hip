@@ -9,7 +9,7 @@
 // pyramid needs no NCHW -> NHWC transpose; the two pointwise linears of a block (96 % of its FLOPs) are the fused GEMM
 // of gemm_f32*.hip on rows = B H W (bias + GELU, or bias + residual with layer_scale folded into the weights), and
 // this file holds the HBM-bound rest: patchify stem, depthwise 7x7 + LayerNorm, LayerNorm + 2x2 patch gather, the
-// layer_scale fold.  LayerNorm statistics are per texel over its channels (fp32 sums over <= 384 values).
+// layer_scale fold.  LayerNorm statistics are per texel over its channels (fp32 sums over <= 768 values).
 #include "common.h"
 #include "kernels.h"
 
@@ -76,13 +76,15 @@ __global__ __launch_bounds__(256) void stem_conv_ln_kernel(const float* __restri
 }
 
 // ---- depthwise 7 x 7 (padding 3) + bias + LayerNorm over channels, channels-last.
-// A thread owns one 16-byte channel chunk of a GROUP of TX = 4 texels adjacent in W: a row of the window needs 10 texel
-// loads for the four outputs instead of 28, and one weight read per tap serves four texels.  The weights (C, 1, 7, 7) are
-// given TAP-MAJOR, (49, C) = weight.reshape(C, 49).T, and staged once per block in LDS (a tap's 4 channels are one 16-byte
-// read, the same address for every group of the block — a broadcast); a block walks `iters` batches of 256 / (C / 4) groups
-// to amortise that.  (The first form read w[c][tap] — four strided scalar loads per tap and texel — and ran 40x off the HBM
-// floor of the layer.)
-template <int C>
+// A thread owns NCH 16-byte channel chunks (c, c + C / NCH, ...) of a GROUP of TX = 4 texels adjacent in W: a row of the
+// window needs 10 texel loads for the four outputs instead of 28, and one weight read per tap serves four texels.  The weights
+// (C, 1, 7, 7) are given TAP-MAJOR, (49, C) = weight.reshape(C, 49).T, and staged once per block in LDS (a tap's 4 channels are
+// one 16-byte read, the same address for every group of the block — a broadcast); a block walks `iters` batches of
+// 256 / (C / 4 NCH) groups to amortise that.  (The first form read w[c][tap] — four strided scalar loads per tap and texel — and
+// ran 40x off the HBM floor of the layer.)  NCH = 1 for C <= 384; C = 768 (the fourth stage) takes NCH = 3: 64 lanes — one wave —
+// per group, four groups per block and no idle thread (at 4 channels per lane 192 lanes per group would leave 64 of 256 idle);
+// its 49 x 768 fp32 taps are 147 KiB of the 160 KiB of LDS, one block per CU.
+template <int C, int NCH = 1>
 __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ bias, const float* __restrict__ ln_w,
                                                          const float* __restrict__ ln_b, float* __restrict__ out,
@@ -92,20 +94,35 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
     // flipped copy of the weights); addp — a tensor added to the result (the skip connection's gradient of a CNBlock)
     // zout: also the convolution's own output (training: the LayerNorm's input).  ln_w == null: no LayerNorm — out is the
     // convolution (bias may be null too): with the taps reversed this is the convolution's input gradient.
-    constexpr int TPP = C / 4, PG = 256 / TPP, TX = 4, NPART = 4;
+    constexpr int TPP = C / (4 * NCH), PG = 256 / TPP, TX = 4, NPART = 4;
     static_assert(TPP % NPART == 0, "the LayerNorm partial sums split a group's threads in four");
     extern __shared__ __attribute__((aligned(16))) float cs[];
     float* wl = cs;                       // [49][C]
     float* red = wl + 49 * C;             // [TX][256] per-thread partials
     float* part = red + TX * 256;         // [PG][TX][NPART]
-    const int pg = threadIdx.x / TPP, t = threadIdx.x % TPP, c = 4 * t;
+    const int pg = threadIdx.x / TPP, t = threadIdx.x % TPP, c = 4 * t;   // chunk j: channels c + 4 TPP j
     for (int i = threadIdx.x; i < 49 * C / 4; i += 256) {   // w arrives tap-major (49, C): a coalesced copy
         const int tap = i / (C / 4), c4 = i % (C / 4);
         reinterpret_cast<f32x4*>(wl)[i] = reinterpret_cast<const f32x4*>(w)[flip ? (48 - tap) * (C / 4) + c4 : i];
     }
-    const f32x4 bias4 = pg < PG && bias ? *reinterpret_cast<const f32x4*>(bias + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    const f32x4 g4 = pg < PG && ln_w ? *reinterpret_cast<const f32x4*>(ln_w + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    const f32x4 b4 = pg < PG && ln_w ? *reinterpret_cast<const f32x4*>(ln_b + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    // NCH = 1: bias and LayerNorm affine held across the batches; NCH > 1 re-reads them where used (12 more registers each would spill)
+    f32x4 bias4[NCH], g4[NCH], b4[NCH];
+    auto load_bias = [&] {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j)
+            bias4[j] = pg < PG && bias ? *reinterpret_cast<const f32x4*>(bias + c + 4 * TPP * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+    auto load_affine = [&] {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            g4[j] = pg < PG && ln_w ? *reinterpret_cast<const f32x4*>(ln_w + c + 4 * TPP * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+            b4[j] = pg < PG && ln_w ? *reinterpret_cast<const f32x4*>(ln_b + c + 4 * TPP * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    if constexpr (NCH == 1) {
+        load_bias();
+        load_affine();
+    }
     const int GR = (W + TX - 1) / TX;     // groups per image row
     const size_t ngroups = (size_t)B * H * GR;
     // neighbouring strips share their halo rows (a window is 7 rows high): consecutive strips on one XCD, its L2 serves them
@@ -114,9 +131,12 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
     for (int it = 0; it < iters; ++it) {
         const size_t gid = ((size_t)vbx * iters + it) * PG + pg;
         const bool live = pg < PG && gid < ngroups;
-        f32x4 acc[TX];
+        if constexpr (NCH > 1) load_bias();
+        f32x4 acc[NCH][TX];
 #pragma unroll
-        for (int tx = 0; tx < TX; ++tx) acc[tx] = bias4;
+        for (int j = 0; j < NCH; ++j)
+#pragma unroll
+            for (int tx = 0; tx < TX; ++tx) acc[j][tx] = bias4[j];
         int wx0 = 0, hy = 0, b = 0;
         if (live) {
             wx0 = (int)(gid % GR) * TX;
@@ -127,19 +147,22 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
             for (int dy = -3; dy <= 3; ++dy) {
                 const int yy = hy + dy;
                 if (yy < 0 || yy >= H) continue;
-                const float* xr = xb + (size_t)yy * W * C;
-                f32x4 xv[TX + 6];
 #pragma unroll
-                for (int j = 0; j < TX + 6; ++j) {
-                    const int xx = wx0 - 3 + j;
-                    xv[j] = (xx >= 0 && xx < W) ? *reinterpret_cast<const f32x4*>(xr + (size_t)xx * C) : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-                const float* wr = wl + (dy + 3) * 7 * C + c;
+                for (int j = 0; j < NCH; ++j) {
+                    const float* xr = xb + (size_t)yy * W * C + 4 * TPP * j;
+                    f32x4 xv[TX + 6];
 #pragma unroll
-                for (int dx = 0; dx < 7; ++dx) {
-                    const f32x4 wv = *reinterpret_cast<const f32x4*>(wr + dx * C);
+                    for (int k = 0; k < TX + 6; ++k) {
+                        const int xx = wx0 - 3 + k;
+                        xv[k] = (xx >= 0 && xx < W) ? *reinterpret_cast<const f32x4*>(xr + (size_t)xx * C) : f32x4{0.f, 0.f, 0.f, 0.f};
+                    }
+                    const float* wr = wl + (dy + 3) * 7 * C + c + 4 * TPP * j;
 #pragma unroll
-                    for (int tx = 0; tx < TX; ++tx) acc[tx] += xv[tx + dx] * wv;
+                    for (int dx = 0; dx < 7; ++dx) {
+                        const f32x4 wv = *reinterpret_cast<const f32x4*>(wr + dx * C);
+#pragma unroll
+                        for (int tx = 0; tx < TX; ++tx) acc[j][tx] += xv[tx + dx] * wv;
+                    }
                 }
             }
         }
@@ -149,9 +172,13 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
 #pragma unroll
                 for (int tx = 0; tx < TX; ++tx)
                     if (wx0 + tx < W) {
-                        f32x4 r = acc[tx];
-                        if (addp) r += *reinterpret_cast<const f32x4*>(addp + (op - out) + (size_t)tx * C);
-                        *reinterpret_cast<f32x4*>(op + (size_t)tx * C) = r;
+#pragma unroll
+                        for (int j = 0; j < NCH; ++j) {
+                            const size_t off = (size_t)tx * C + 4 * TPP * j;
+                            f32x4 r = acc[j][tx];
+                            if (addp) r += *reinterpret_cast<const f32x4*>(addp + (op - out) + off);
+                            *reinterpret_cast<f32x4*>(op + off) = r;
+                        }
                     }
             }
             continue;
@@ -160,7 +187,10 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
             float* zp = zout + (((size_t)b * H + hy) * W + wx0) * C + c;
 #pragma unroll
             for (int tx = 0; tx < TX; ++tx)
-                if (wx0 + tx < W) *reinterpret_cast<f32x4*>(zp + (size_t)tx * C) = acc[tx];
+                if (wx0 + tx < W) {
+#pragma unroll
+                    for (int j = 0; j < NCH; ++j) *reinterpret_cast<f32x4*>(zp + (size_t)tx * C + 4 * TPP * j) = acc[j][tx];
+                }
         }
         // LayerNorm over each texel's C channels, two passes (mean, centred variance): per-thread partials in LDS, four
         // threads per (group, texel) add a quarter of them each, everyone combines the four quarters
@@ -169,9 +199,15 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
         for (int pass = 0; pass < 2; ++pass) {
 #pragma unroll
             for (int tx = 0; tx < TX; ++tx) {
-                f32x4 d = acc[tx];
-                if (pass == 1) { d = d - mean[tx]; d = d * d; }
-                red[tx * 256 + threadIdx.x] = d[0] + d[1] + d[2] + d[3];
+                float s = 0.f;
+#pragma unroll
+                for (int j = 0; j < NCH; ++j) {
+                    f32x4 d = acc[j][tx];
+                    if (pass == 1) { d = d - mean[tx]; d = d * d; }
+                    const float q = d[0] + d[1] + d[2] + d[3];
+                    s = j == 0 ? q : s + q;
+                }
+                red[tx * 256 + threadIdx.x] = s;
             }
             __syncthreads();
             if (pg < PG && t < TX * NPART) {
@@ -194,10 +230,15 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
             }
         }
         if (live) {
+            if constexpr (NCH > 1) load_affine();
             float* op = out + (((size_t)b * H + hy) * W + wx0) * C + c;
 #pragma unroll
             for (int tx = 0; tx < TX; ++tx)
-                if (wx0 + tx < W) *reinterpret_cast<f32x4*>(op + (size_t)tx * C) = (acc[tx] - mean[tx]) * rstd[tx] * g4 + b4;
+                if (wx0 + tx < W) {
+#pragma unroll
+                    for (int j = 0; j < NCH; ++j)
+                        *reinterpret_cast<f32x4*>(op + (size_t)tx * C + 4 * TPP * j) = (acc[j][tx] - mean[tx]) * rstd[tx] * g4[j] + b4[j];
+                }
         }
     }
 }
@@ -277,7 +318,6 @@ __global__ __launch_bounds__(256) void fold_scale_bwd_kernel(const float* __rest
         case 96: hipLaunchKernelGGL((KERNEL<96>), grid, dim3(256), 0, st, __VA_ARGS__); break;                  \
         case 192: hipLaunchKernelGGL((KERNEL<192>), grid, dim3(256), 0, st, __VA_ARGS__); break;                \
         case 384: hipLaunchKernelGGL((KERNEL<384>), grid, dim3(256), 0, st, __VA_ARGS__); break;                \
-        case 768: return -9; /* the fourth stage is not part of the pyramid (n_stages <= 3 in every config) */  \
         default: return -9;                                                                                     \
     }
 
@@ -289,31 +329,36 @@ int cnx_stem_launch(const float* x, const float* w, const float* bias, const flo
                        H, W, eps);
     return (int)hipGetLastError();
 }
+// channels per lane of dwconv7_ln_kernel: 4 (one chunk) up to C = 384, 12 at C = 768
+constexpr int dw_chunks(int C) { return C == 768 ? 3 : 1; }
+
 int cnx_dwconv_ln_launch(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out,
                          float* zout, int B, int H, int W, int C, float eps, hipStream_t st, const float* addp, int flip) {
-    if (C != 96 && C != 192 && C != 384) return -9;
-    const int pg = 256 / (C / 4);
+    if (C != 96 && C != 192 && C != 384 && C != 768) return -9;
+    const int pg = 256 / (C / (4 * dw_chunks(C)));
     const size_t ngroups = (size_t)B * H * ((W + 3) / 4), batches = (ngroups + pg - 1) / pg;
     // a block stages 49 C weights: enough batches per block to amortise that, enough blocks to fill the chip
     int iters = 1;
     while (iters < 16 && batches / (iters * 2) >= 512) iters *= 2;
     const unsigned grid = (unsigned)((batches + iters - 1) / iters);
-    const size_t lds = (size_t)(49 * C + 4 * 256 + pg * 4 * 4) * sizeof(float);
+    const size_t lds = (size_t)(49 * C + 4 * 256 + pg * 4 * 4) * sizeof(float);   // C = 768: 154880 bytes
 #define CNX_DW(CV)                                                                                                          \
     case CV: {                                                                                                              \
+        constexpr int NCH = dw_chunks(CV);                                                                                  \
         static bool attr = false;                                                                                           \
         if (!attr) {                                                                                                        \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv7_ln_kernel<CV>),                                 \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv7_ln_kernel<CV, NCH>),                            \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
             attr = true;                                                                                                    \
         }                                                                                                                   \
-        hipLaunchKernelGGL((dwconv7_ln_kernel<CV>), dim3(grid), dim3(256), lds, st, x, w, bias, ln_w, ln_b, out, zout, B, H, W, eps, iters, addp, flip); \
+        hipLaunchKernelGGL((dwconv7_ln_kernel<CV, NCH>), dim3(grid), dim3(256), lds, st, x, w, bias, ln_w, ln_b, out, zout, B, H, W, eps, iters, addp, flip); \
         break;                                                                                                              \
     }
     switch (C) {
         CNX_DW(96)
         CNX_DW(192)
         CNX_DW(384)
+        CNX_DW(768)
     }
 #undef CNX_DW
     return (int)hipGetLastError();

@@ -22,8 +22,8 @@ __device__ __forceinline__ float lanes_sum(float v, int width) {   // over `widt
 
 // ---- LayerNorm backward over the channels of a texel.  y = (z - mean) rstd g + b:
 //   xh = (z - mean) rstd,  gy = dy g,  dz = rstd (gy - mean_c(gy) - xh mean_c(gy xh)),  dg += dy xh,  db += dy,  dzsum += dz
-// (dzsum is the bias gradient of the convolution that produced z).  L = C / 12 lanes share a texel (8 / 16 / 32: a power of
-// two, sums by lane shuffles, no LDS in the loop); lane q owns the 16-byte chunks q, q + L, q + 2L.  patch2: dy is laid out
+// (dzsum is the bias gradient of the convolution that produced z).  L = C / 12 lanes share a texel (8 / 16 / 32 / 64: a power of
+// two, sums by lane shuffles, no LDS in the loop; at C = 768 a texel is a whole wave); lane q owns the 16-byte chunks q, q + L, q + 2L.  patch2: dy is laid out
 // as the 2 x 2 patch matrix of the downsampling convolution, (B, H/2, W/2, (dy, dx, c)) — the transpose of ln_patch2_kernel.
 template <int C>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ z, const float* __restrict__ dy,
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ z
                                                      float* __restrict__ parts, size_t npix, int H, int W, float eps, int patch2,
                                                      int iters) {
     constexpr int L = C / 12, PIX = 256 / L;
-    static_assert(L == 8 || L == 16 || L == 32, "C = 96, 192, 384");
+    static_assert(L == 8 || L == 16 || L == 32 || L == 64, "C = 96, 192, 384, 768");
     __shared__ float red[3 * PIX * C];   // 36 KiB for every C
     const int pl = threadIdx.x / L, q = threadIdx.x % L;
     f32x4 g4[3], ag[3], ab[3], az[3];
@@ -109,7 +109,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ z
 // ---- depthwise 7 x 7 weight gradient: dW[tap = (dy, dx)][c] = sum over texels dz[b, y, x, c] x[b, y + dy - 3, x + dx - 3, c].
 // Same thread layout as the forward kernel (a 16-byte channel chunk of four texels adjacent in W; a window row is ten texel
 // loads), one block per (strip, tap row dy): 7 four-channel accumulators per thread, carried over the block's `iters` batches of groups, then
-// summed over the block's groups through LDS.  parts: (gridDim.x, 49, C).
+// summed over the block's groups through LDS.  parts: (gridDim.x, 49, C).  At C = 768 a group takes 192 threads: one group per block,
+// the block's last 64 threads idle (21 KiB of LDS; the stage's maps are 7 x 7 or 8 x 8, the kernel is a small part of its backward).
 template <int C>
 __global__ __launch_bounds__(256) void dwconv7_dw_kernel(const float* __restrict__ x, const float* __restrict__ dz,
                                                          float* __restrict__ parts, int B, int H, int W, int iters) {
@@ -221,37 +222,39 @@ int dw_plan(int B, int H, int W, int C, int* iters) {
 }  // namespace
 
 int cnx_ln_bwd_blocks(int B, int H, int W, int C) {
-    if (C != 96 && C != 192 && C != 384) return -9;
+    if (C != 96 && C != 192 && C != 384 && C != 768) return -9;
     int it;
     return ln_bwd_plan((size_t)B * H * W, C, &it);
 }
 int cnx_ln_bwd_launch(const float* z, const float* dy, const float* ln_w, float* dz, float* parts, int B, int H, int W, int C,
                       float eps, int patch2, hipStream_t st) {
-    if ((C != 96 && C != 192 && C != 384) || (patch2 && ((H & 1) || (W & 1)))) return -9;
+    if ((C != 96 && C != 192 && C != 384 && C != 768) || (patch2 && ((H & 1) || (W & 1)))) return -9;
     const size_t npix = (size_t)B * H * W;
     int iters;
     const int grid = ln_bwd_plan(npix, C, &iters);
     switch (C) {
         case 96: hipLaunchKernelGGL((ln_bwd_kernel<96>), dim3(grid), dim3(256), 0, st, z, dy, ln_w, dz, parts, npix, H, W, eps, patch2, iters); break;
         case 192: hipLaunchKernelGGL((ln_bwd_kernel<192>), dim3(grid), dim3(256), 0, st, z, dy, ln_w, dz, parts, npix, H, W, eps, patch2, iters); break;
-        default: hipLaunchKernelGGL((ln_bwd_kernel<384>), dim3(grid), dim3(256), 0, st, z, dy, ln_w, dz, parts, npix, H, W, eps, patch2, iters); break;
+        case 384: hipLaunchKernelGGL((ln_bwd_kernel<384>), dim3(grid), dim3(256), 0, st, z, dy, ln_w, dz, parts, npix, H, W, eps, patch2, iters); break;
+        default: hipLaunchKernelGGL((ln_bwd_kernel<768>), dim3(grid), dim3(256), 0, st, z, dy, ln_w, dz, parts, npix, H, W, eps, patch2, iters); break;
     }
     return (int)hipGetLastError();
 }
 int cnx_dwconv_dw_blocks(int B, int H, int W, int C) {
-    if (C != 96 && C != 192 && C != 384) return -9;
+    if (C != 96 && C != 192 && C != 384 && C != 768) return -9;
     int it;
     return dw_plan(B, H, W, C, &it);
 }
 int cnx_dwconv_dw_launch(const float* x, const float* dz, float* parts, int B, int H, int W, int C, hipStream_t st) {
-    if (C != 96 && C != 192 && C != 384) return -9;
+    if (C != 96 && C != 192 && C != 384 && C != 768) return -9;
     int iters;
     const int gx = dw_plan(B, H, W, C, &iters);
     const dim3 grid(gx * 7);
     switch (C) {
         case 96: hipLaunchKernelGGL((dwconv7_dw_kernel<96>), grid, dim3(256), 0, st, x, dz, parts, B, H, W, iters); break;
         case 192: hipLaunchKernelGGL((dwconv7_dw_kernel<192>), grid, dim3(256), 0, st, x, dz, parts, B, H, W, iters); break;
-        default: hipLaunchKernelGGL((dwconv7_dw_kernel<384>), grid, dim3(256), 0, st, x, dz, parts, B, H, W, iters); break;
+        case 384: hipLaunchKernelGGL((dwconv7_dw_kernel<384>), grid, dim3(256), 0, st, x, dz, parts, B, H, W, iters); break;
+        default: hipLaunchKernelGGL((dwconv7_dw_kernel<768>), grid, dim3(256), 0, st, x, dz, parts, B, H, W, iters); break;
     }
     return (int)hipGetLastError();
 }

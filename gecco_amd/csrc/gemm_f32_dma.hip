@@ -406,9 +406,9 @@ bool gemm_f32_dma_supported(const GemmArgs& g, int precision) {
     if (precision < 0) precision = g.precision;
     if (g.C2 && ((g.n_split % DBN) || g.stats || g.residual || (g.ldc2 & 3) || g.n_split <= 0 || g.n_split >= g.Nout))
         return false;
-    // K <= 1024 with the AdaGN prologue (its coefficients are parked in LDS: 8 K bytes); without it up to 2048 (the ConvNeXt
-    // conditioner's 4 C -> C linears at C = 384: K = 1536)
-    return g.rows >= (precision == 1 ? 64 : 128) && g.K % DBK == 0 && g.K <= (g.pro_a ? 1024 : 2048) && !(g.Nout & 3) && !(g.ldc & 3) && !(g.ldr & 3) &&
+    // K <= 2048: the ConvNeXt conditioner's 4 C -> C linears at C = 384 (K = 1536); with the AdaGN prologue its coefficients are
+    // parked in LDS (8 K bytes: 16 KiB at K = 2048) — img_feature_proj behind GroupNorm(16) on the four-level pyramid, K = 1440
+    return g.rows >= (precision == 1 ? 64 : 128) && g.K % DBK == 0 && g.K <= 2048 && !(g.Nout & 3) && !(g.ldc & 3) && !(g.ldr & 3) &&
            !(g.lda & 3) && !(g.ldw & 7);
 }
 

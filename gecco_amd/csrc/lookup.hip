@@ -79,20 +79,28 @@ __device__ __forceinline__ f32x4 texel4(const float* fb, size_t off) {
     }
 }
 
-template <bool TEX16, bool OUT16 = false>
+// fp16 with saturation: |v| > 65504 (the largest half) stores +-65504 instead of inf; NaN passes through, every value the plain
+// conversion keeps finite converts to the same bits.  The pyramid's deepest level (768 channels after 12 - 30 more blocks) has
+// the largest magnitudes.
+__device__ __forceinline__ _Float16 sat_f16(float v) {
+    return (_Float16)(v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v));
+}
+
+// MAXCH: 16-byte chunks per lane, 64 x 4 x MAXCH channels: 4 (<= 1024 channels: three levels, 672 at ConvNeXt-T/S) or 6 (<= 1536:
+// the four-level pyramid's 1440).  The per-wave column partials of the GN statistics are MAXCH KiB x 8: 32 KiB or 48 KiB of LDS.
+template <int MAXCH, bool TEX16, bool OUT16 = false>
 __global__ __launch_bounds__(256) void ray_lookup_kernel(const float* __restrict__ geom,
                                                          const float* __restrict__ coef,
                                                          const float* __restrict__ K, LookupArgs a,
                                                          float* __restrict__ out, float* __restrict__ stats, int N,
                                                          int T) {
-    __shared__ float red[4][2][1024];  // per-wave column partials (sum C_l <= 1024)
+    __shared__ float red[4][2][256 * MAXCH];  // per-wave column partials (sum C_l <= 256 MAXCH)
     const int tile = blockIdx.x % T, b = blockIdx.x / T;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int Ct = a.c_total, C4 = Ct / 4;
     const float cin = coef ? coef[4 * b + 2] : 1.0f;
     const float* Kb = K + (size_t)b * 9;
 
-    constexpr int MAXCH = 4;  // float4 chunks per lane: 64 * 4 * 4 = 1024 channels max
     f32x4 s1[MAXCH], s2[MAXCH];
 #pragma unroll
     for (int c = 0; c < MAXCH; ++c) {
@@ -153,7 +161,7 @@ __global__ __launch_bounds__(256) void ray_lookup_kernel(const float* __restrict
             if constexpr (OUT16) {   // (B, N, Ct) halves for a matrix kernel that rounds its operand to fp16 anyway; the statistics are the fp32 values
                 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
                 reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(out) + ((size_t)b * N + m) * Ct)[c4] =
-                    f16x4{(_Float16)r[0], (_Float16)r[1], (_Float16)r[2], (_Float16)r[3]};
+                    f16x4{sat_f16(r[0]), sat_f16(r[1]), sat_f16(r[2]), sat_f16(r[3])};
             } else {
                 *reinterpret_cast<f32x4*>(orow + c4 * 4) = r;
             }
@@ -250,6 +258,7 @@ __device__ __forceinline__ void project_uv_jac(float g0, float g1, float g2, con
 // d out / d ix = wy0 (ne - nw) + wy1 (se - sw) and d out / d iy = wx0 (sw - nw) + wx1 (se - ne) over the in-range taps.  One wave per
 // point, lanes over 16-byte channel chunks as in the forward; a wave reduction, three floats out.
 // dKpart (optional): (B, T, 4) partials of the gradient with respect to (fx, cx, fy, cy) of the sample's camera matrix, one per block
+template <int MAXCH>
 __global__ __launch_bounds__(256) void ray_lookup_dgeom_kernel(const float* __restrict__ geom, const float* __restrict__ K, LookupArgs a,
                                                                const float* __restrict__ dout, float* __restrict__ dgeom,
                                                                float* __restrict__ dKpart, int N, int T) {
@@ -259,7 +268,6 @@ __global__ __launch_bounds__(256) void ray_lookup_dgeom_kernel(const float* __re
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int Ct = a.c_total, C4 = Ct / 4;
     const float* Kb = K + (size_t)b * 9;
-    constexpr int MAXCH = 4;
     int lvl[MAXCH], coff[MAXCH];
 #pragma unroll
     for (int c = 0; c < MAXCH; ++c) {
@@ -352,6 +360,7 @@ struct LookupGrads {
     float* d[4];   // channels-last (B, H, W, C) per level, zero-initialised by the caller
 };
 
+template <int MAXCH>
 __global__ __launch_bounds__(256) void ray_lookup_bwd_kernel(const float* __restrict__ geom,
                                                              const float* __restrict__ coef,
                                                              const float* __restrict__ K, LookupArgs a, LookupGrads gr,
@@ -361,7 +370,6 @@ __global__ __launch_bounds__(256) void ray_lookup_bwd_kernel(const float* __rest
     const int Ct = a.c_total, C4 = Ct / 4;
     const float cin = coef ? coef[4 * b + 2] : 1.0f;
     const float* Kb = K + (size_t)b * 9;
-    constexpr int MAXCH = 4;
     int lvl[MAXCH], coff[MAXCH];
 #pragma unroll
     for (int c = 0; c < MAXCH; ++c) {
@@ -598,9 +606,16 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ src, float* __rest
 
 int lookup_row_tile() { return LOOKUP_ROWS; }
 
+// channel capacity of the lookup kernels: MAXCH = 4 (<= 1024) or 6 (<= 1536); 0: c_total out of range
+static int lookup_chunks(const LookupArgs& a) {
+    if (a.n_levels < 1 || a.n_levels > 4 || a.c_total % 4) return 0;
+    return a.c_total <= 1024 ? 4 : a.c_total <= 1536 ? 6 : 0;
+}
+
 int ray_lookup_launch(const float* geom, const float* coef, const float* K, const LookupArgs& a, float* out,
                       float* stats, int B, int N, hipStream_t st) {
-    if (a.n_levels < 1 || a.n_levels > 4 || a.c_total > 1024 || a.c_total % 4) return -8;
+    const int mc = lookup_chunks(a);
+    if (!mc) return -8;
     int tot = 0;
     for (int l = 0; l < a.n_levels; ++l) {
         if (a.C[l] % 4) return -8;
@@ -608,13 +623,21 @@ int ray_lookup_launch(const float* geom, const float* coef, const float* K, cons
     }
     if (tot != a.c_total) return -8;
     const int T = (N + LOOKUP_ROWS - 1) / LOOKUP_ROWS;
-    if (a.out_f16) {
-        if (a.texel_f16) hipLaunchKernelGGL((ray_lookup_kernel<true, true>), dim3(B * T), dim3(256), 0, st, geom, coef, K, a, out, stats, N, T);
-        else hipLaunchKernelGGL((ray_lookup_kernel<false, true>), dim3(B * T), dim3(256), 0, st, geom, coef, K, a, out, stats, N, T);
-        return (int)hipGetLastError();
+#define LOOKUP_FWD(MC)                                                                                                                   \
+    if (a.out_f16) {                                                                                                                     \
+        if (a.texel_f16) hipLaunchKernelGGL((ray_lookup_kernel<MC, true, true>), dim3(B * T), dim3(256), 0, st, geom, coef, K, a, out, stats, N, T); \
+        else hipLaunchKernelGGL((ray_lookup_kernel<MC, false, true>), dim3(B * T), dim3(256), 0, st, geom, coef, K, a, out, stats, N, T); \
+    } else if (a.texel_f16) {                                                                                                            \
+        hipLaunchKernelGGL((ray_lookup_kernel<MC, true>), dim3(B * T), dim3(256), 0, st, geom, coef, K, a, out, stats, N, T);            \
+    } else {                                                                                                                             \
+        hipLaunchKernelGGL((ray_lookup_kernel<MC, false>), dim3(B * T), dim3(256), 0, st, geom, coef, K, a, out, stats, N, T);           \
     }
-    if (a.texel_f16) hipLaunchKernelGGL(ray_lookup_kernel<true>, dim3(B * T), dim3(256), 0, st, geom, coef, K, a, out, stats, N, T);
-    else hipLaunchKernelGGL(ray_lookup_kernel<false>, dim3(B * T), dim3(256), 0, st, geom, coef, K, a, out, stats, N, T);
+    if (mc == 4) {
+        LOOKUP_FWD(4)
+    } else {
+        LOOKUP_FWD(6)
+    }
+#undef LOOKUP_FWD
     return (int)hipGetLastError();
 }
 
@@ -623,9 +646,9 @@ __global__ void cast_f16_kernel(const float* __restrict__ src, _Float16* __restr
     typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const f32x4 v = reinterpret_cast<const f32x4*>(src)[i];
-        reinterpret_cast<f16x4*>(dst)[i] = f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+        reinterpret_cast<f16x4*>(dst)[i] = f16x4{sat_f16(v[0]), sat_f16(v[1]), sat_f16(v[2]), sat_f16(v[3])};
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) dst[(n & ~size_t(3)) + threadIdx.x] = (_Float16)src[(n & ~size_t(3)) + threadIdx.x];
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) dst[(n & ~size_t(3)) + threadIdx.x] = sat_f16(src[(n & ~size_t(3)) + threadIdx.x]);
 }
 }  // namespace
 
@@ -639,25 +662,31 @@ int cast_f16_launch(const float* src, void* dst, size_t n, hipStream_t st) {
 
 int ray_lookup_dgeom_launch(const float* geom, const float* K, const LookupArgs& a, const float* dout, float* dgeom, float* dKpart, int B,
                             int N, hipStream_t st) {
-    if (a.n_levels < 1 || a.n_levels > 4 || a.c_total > 1024 || a.c_total % 4) return -8;
+    const int mc = lookup_chunks(a);
+    if (!mc) return -8;
     for (int l = 0; l < a.n_levels; ++l)
         if (a.C[l] % 4) return -8;
     const int T = (N + LOOKUP_ROWS - 1) / LOOKUP_ROWS;
-    hipLaunchKernelGGL(ray_lookup_dgeom_kernel, dim3(B * T), dim3(256), 0, st, geom, K, a, dout, dgeom, dKpart, N, T);
+    if (mc == 4) hipLaunchKernelGGL(ray_lookup_dgeom_kernel<4>, dim3(B * T), dim3(256), 0, st, geom, K, a, dout, dgeom, dKpart, N, T);
+    else hipLaunchKernelGGL(ray_lookup_dgeom_kernel<6>, dim3(B * T), dim3(256), 0, st, geom, K, a, dout, dgeom, dKpart, N, T);
     return (int)hipGetLastError();
 }
 
 int ray_lookup_bwd_launch(const float* geom, const float* coef, const float* K, const LookupArgs& a,
                           float* const* dfeat, const float* dout, int B, int N, hipStream_t st) {
-    if (a.n_levels < 1 || a.n_levels > 4 || a.c_total > 1024 || a.c_total % 4) return -8;
+    const int mc = lookup_chunks(a);
+    if (!mc) return -8;
     LookupGrads gr;
     for (int l = 0; l < 4; ++l) gr.d[l] = l < a.n_levels ? dfeat[l] : nullptr;
     const int T = (N + LOOKUP_ROWS - 1) / LOOKUP_ROWS;
-    hipLaunchKernelGGL(ray_lookup_bwd_kernel, dim3(B * T), dim3(256), 0, st, geom, coef, K, a, gr, dout, N, T);
+    if (mc == 4) hipLaunchKernelGGL(ray_lookup_bwd_kernel<4>, dim3(B * T), dim3(256), 0, st, geom, coef, K, a, gr, dout, N, T);
+    else hipLaunchKernelGGL(ray_lookup_bwd_kernel<6>, dim3(B * T), dim3(256), 0, st, geom, coef, K, a, gr, dout, N, T);
     return (int)hipGetLastError();
 }
 
-// sorted form: N <= 4096 points, H W <= 2^17 texels per level, C_l % 4 == 0 and C_l <= 1024
+// sorted form: N <= 4096 points, H W <= 2^17 texels per level, C_l % 4 == 0 and C_l <= 1024 (c_total unbounded: the gather kernel
+// reads one level's C_l columns at a time).  The workspace is per (image, level): P entries (4 taps per point, padded to a power of
+// two) and max_l(H_l W_l) + 1 list starts — a 7 x 7 or 8 x 8 fourth level only uses the first 50 / 65 of the list-start row.
 static int sort_P(int N) {
     int P = 1024;
     while (P < 4 * N) P <<= 1;

@@ -49,6 +49,20 @@ __global__ __launch_bounds__(256) void col_stats_kernel(const float* __restrict_
         }
         return;
     }
+    if (C % 4 == 0) {   // wider rows (the four-level pyramid's 1440 lookup channels): a thread per 16-byte chunk walks the tile's rows
+        // in order — the summation order of the scalar loop below, four columns per load, the loads of a row coalesced over the block
+        for (int c4 = threadIdx.x; c4 < C / 4; c4 += blockDim.x) {
+            f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+            for (int m = m0; m < m1; ++m) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (size_t)m * C + c4 * 4);
+                s1 += v;
+                s2 += v * v;
+            }
+            *reinterpret_cast<f32x4*>(stats + (((size_t)b * T + tile) * 2 + 0) * C + c4 * 4) = s1;
+            *reinterpret_cast<f32x4*>(stats + (((size_t)b * T + tile) * 2 + 1) * C + c4 * 4) = s2;
+        }
+        return;
+    }
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         float s1 = 0.f, s2 = 0.f;
         for (int m = m0; m < m1; ++m) {

@@ -59,8 +59,8 @@ class ConvNeXtExtractor(FeaturePyramidExtractor):
         super().__init__()
         if model not in _SETTINGS:
             raise ValueError(f"Unknown model {model}")
-        if not 1 <= n_stages <= 3:
-            raise ValueError("the HIP conditioner implements the first three stages (every shipped config uses n_stages=3)")
+        if not 1 <= n_stages <= 4:
+            raise ValueError(f"n_stages must be 1..4 (ConvNeXt-T/S have four stages), got {n_stages}")
         self.stages = nn.ModuleList()
         prev = None
         for dim, depth in _SETTINGS[model][:n_stages]:
