@@ -141,7 +141,10 @@ class IdleConditioner(Conditioner):
 
 # ---------------------------------------------------------------------------------------------- sampler engine
 def karras_t_steps(num_steps: int, sigma_max: float, sigma_min: float, rho: float) -> Tensor:
-    """fp64 Karras schedule with t_N = 0 (reference diffusion.py:253-269), on the host."""
+    """fp64 Karras schedule with t_N = 0 (reference diffusion.py:253-269), on the host.  num_steps < 2 is refused: the grid divides by
+    num_steps - 1, so the reference's one-step schedule is 0 / 0 = nan and every sampler on it returns an all-nan cloud."""
+    if num_steps < 2:
+        raise ValueError(f"num_steps must be at least 2 (got {num_steps}): the Karras grid divides by num_steps - 1")
     i = torch.arange(num_steps, dtype=torch.float64)
     t = (sigma_max ** (1 / rho) + i / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
     return torch.cat([t, torch.zeros_like(t[:1])])

@@ -215,3 +215,48 @@ def setmetric_inputs(name):
     data = blobs(0.0)
     samples = blobs(spread)
     return torch.from_numpy(samples), torch.from_numpy(data)
+
+
+# sampler parity at production width (tests/test_hip_sampler_parity.py).  Each case injects every noise draw: entry 0 of
+# `sampler_noise` is the latent, entry i + 1 the churn draw of step i (Diffusion.sample_stochastic's `noise=`).
+SAMPLER_C2_CASE = dict(d=384, L=6, N=2048, B=1, seed=111, num_steps=64, long_steps=128, sigma_max=165.0)
+SAMPLER_TRAJ_CASE = dict(d=128, L=2, N=256, B=2, seed=112, num_steps=64, sigma_max=165.0)
+SAMPLER_C3_CASE = dict(d=384, L=6, N=2048, B=1, hw=224, context_dims=(96, 192, 384), seed=113, num_steps=32, sigma_max=165.0)
+UPSAMPLE_C5_CASE = dict(d=384, L=6, N=2048, B=1, n_new=512, seed=114, num_steps=3, num_substeps=2, sigma_max=165.0)
+TRAIN_CASE = dict(B=8, seed=115, steps=300, lr=1e-3, n_blobs=4)
+
+
+def sampler_noise(seed, num_steps, B, N):
+    """(num_steps + 1, B, N, 3): the latent draw, then one churn draw per step."""
+    rs = np.random.RandomState(seed)
+    return torch.from_numpy(rs.randn(num_steps + 1, B, N, 3).astype(np.float32))
+
+
+def sphere_clouds(seed, B, N, n_blobs=TRAIN_CASE["n_blobs"]):
+    """Structured data-space clouds (B, N, 3): the points of each cloud lie on the surfaces of `n_blobs` seeded spheres (random
+    centres and radii per cloud), at the scale of the unconditional reparam (GAUSS_MEAN / GAUSS_SIGMA): unit scale in diffusion space."""
+    rs = np.random.RandomState(seed)
+    out = np.empty((B, N, 3))
+    for b in range(B):
+        centres = rs.randn(n_blobs, 3) * 1.2
+        radii = 0.3 + 0.5 * rs.rand(n_blobs)
+        which = rs.randint(0, n_blobs, size=N)
+        u = rs.randn(N, 3)
+        u /= np.linalg.norm(u, axis=1, keepdims=True)
+        out[b] = centres[which] + radii[which, None] * u
+    data = torch.from_numpy(out.astype(np.float32))
+    return data * torch.tensor(GAUSS_SIGMA) + torch.tensor(GAUSS_MEAN)
+
+
+def upsample_draws(seed, B, N, n_new, num_steps, num_substeps):
+    """All randn draws of one upsample call in the reference's call order (as upsample_draw_list, for any shape)."""
+    rs = np.random.RandomState(seed)
+    f = lambda *s: torch.from_numpy(rs.randn(*s).astype(np.float32))
+    out = [f(B, n_new, 3)]
+    for i in range(num_steps):
+        out.append(f(B, N, 3))
+        for u in range(num_substeps):
+            out.append(f(B, n_new, 3))
+            if u < num_substeps - 1 and i < num_steps - 1:
+                out.append(f(B, n_new, 3))
+    return out

@@ -92,6 +92,63 @@ def test_schedule_table_matches_oracle():
     assert tab2[0, 3] == 0 and tab2[127, 3] == 0 and (tab2[:, 3] > 0).any()
 
 
+def _reference_schedule_rows(num_steps, sigma_max, sigma_min, rho, S_churn, S_min, S_max, S_noise):
+    """The reference sampler's per-step scalars, restated from its loop (diffusion.py:253-269, 318-325, 465): fp64 Karras times with
+    t_N = 0, gamma = min(S_churn / num_steps, sqrt 2 - 1) inside [S_min, S_max], t_hat = t_cur + gamma t_cur, the churn coefficient
+    sqrt(t_hat^2 - t_cur^2) S_noise and the upsampler's redo coefficient sqrt(t_cur^2 - t_next^2)."""
+    idx = torch.arange(num_steps, dtype=torch.float64)
+    t = (sigma_max ** (1 / rho) + idx / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
+    t = torch.cat([t, torch.zeros_like(t[:1])])
+    rows = []
+    for i in range(num_steps):
+        t_cur, t_next = t[i], t[i + 1]
+        gamma = min(S_churn / num_steps, math.sqrt(2) - 1) if S_min <= t_cur <= S_max else 0
+        t_hat = t_cur + gamma * t_cur
+        rows.append([t_cur, t_hat, t_next, (t_hat ** 2 - t_cur ** 2).sqrt() * S_noise, (t_cur ** 2 - t_next ** 2).sqrt(), 0, 0, 0])
+    return t, torch.tensor([[float(v) for v in r] for r in rows], dtype=torch.float64)
+
+
+@pytest.mark.parametrize("num_steps,S_churn,S_min,S_max,S_noise", [
+    (1, 0.5, 0.0, float("inf"), 1.0),       # one step: the reference's (num_steps - 1) = 0 divides 0 by 0, t_0 = nan; refused
+    (2, 0.5, 0.0, float("inf"), 1.0),       # eager branch, one full step + the last step
+    (3, 0.5, 0.0, float("inf"), 1.0),       # the smallest graph-captured trajectory
+    (128, 0.5, 0.0, float("inf"), 1.0),     # the papers' length
+    (16, 40.0, 0.0, float("inf"), 1.0),     # S_churn / num_steps = 2.5: gamma clamps at sqrt 2 - 1
+    (64, 10.0, 0.0, float("inf"), 1.007),   # S_noise != 1 (EDM's tuned value)
+    (64, 30.0, 0.05, 20.0, 1.003),          # a churn window that contains neither end of the schedule
+    (64, 0.0, 0.0, float("inf"), 1.0),      # sample_ode: no churn anywhere
+])
+def test_schedule_table_matches_the_reference_loop(num_steps, S_churn, S_min, S_max, S_noise):
+    from gecco_amd.diffusion import build_schedule_table, karras_t_steps
+    ts_ref, tab_ref = _reference_schedule_rows(num_steps, 165.0, 0.002, 7, S_churn, S_min, S_max, S_noise)
+    if num_steps == 1:   # the reference's grid is 0 / 0 there; the samplers refuse it instead of returning nan
+        with pytest.raises(ValueError, match="num_steps"):
+            karras_t_steps(num_steps, 165.0, 0.002, 7)
+        ts = ts_ref
+    else:
+        ts = karras_t_steps(num_steps, 165.0, 0.002, 7)
+    torch.testing.assert_close(ts, ts_ref, rtol=0, atol=0, equal_nan=True)
+    tab = build_schedule_table(ts, num_steps, S_churn, S_min, S_max, S_noise)
+    assert tab.shape == (num_steps, 8) and tab.dtype == torch.float64
+    torch.testing.assert_close(tab, tab_ref, rtol=0, atol=0, equal_nan=True)   # bit-exact, column by column
+    if num_steps == 1:
+        assert torch.isnan(tab[0, :2]).all() and tab[0, 2] == 0   # as the reference: a one-step schedule has no finite t_0
+        return
+    assert abs(float(tab[0, 0]) - 165.0) < 1e-12 and tab[-1, 2] == 0 and abs(float(tab[-1, 0]) - 0.002) < 1e-15
+    gamma = tab[:, 1] / tab[:, 0] - 1
+    inside = (tab[:, 0] >= S_min) & (tab[:, 0] <= S_max)
+    assert torch.all(gamma[~inside] == 0)
+    if S_churn > 0:
+        expect = min(S_churn / num_steps, math.sqrt(2) - 1)
+        torch.testing.assert_close(gamma[inside], torch.full_like(gamma[inside], expect), rtol=1e-12, atol=0)
+        if S_churn / num_steps > math.sqrt(2) - 1:
+            assert torch.all(tab[:, 1] <= tab[:, 0] * math.sqrt(2) * (1 + 1e-15))   # the clamp: t_hat <= sqrt 2 t_cur
+    if S_min > 0:
+        assert not inside[0] and not inside[-1] and inside.any()   # the window excludes both ends
+    else:
+        assert torch.all(tab[:, 3][inside] > 0) == (S_churn > 0)
+
+
 def test_modules_refuse_cpu_and_autograd():
     from gecco_amd import _lib
     m = build_uncond(64, 1)
