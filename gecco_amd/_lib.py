@@ -41,6 +41,10 @@ class GeccoLinearLift(C.Structure):
                 ("lower_b", c_f), ("sigma_data", C.c_float)]
 
 
+class GeccoLinearLiftG(C.Structure):
+    _fields_ = [("base", GeccoLinearLift), ("geometry_dim", C.c_int), ("do_norm", C.c_int)]
+
+
 class GeccoPyramid(C.Structure):
     _fields_ = [("n_levels", C.c_int), ("C", C.c_int * 4), ("H", C.c_int * 4), ("W", C.c_int * 4), ("feat", c_f * 4),
                 ("texel_f16", C.c_int)]
@@ -164,6 +168,10 @@ SIGNATURES = {
     "gecco_set_transformer_workspace_bytes": (sz, [C.POINTER(GeccoSetTransformer), i, i]),
     "gecco_linear_lift_fwd_f32": (i, [C.POINTER(GeccoLinearLift), vp, vp, vp, vp, PP, PP, i, i, vp, sz, vp]),
     "gecco_linear_lift_workspace_bytes": (sz, [C.POINTER(GeccoLinearLift), i, i]),
+    "gecco_lift_g_f32": (i, [vp, vp, vp, vp, vp, vp, i, i, i, i, vp]),
+    "gecco_lower_edm_g_f32": (i, [vp] * 7 + [i, i, i, i, i, fl, vp]),
+    "gecco_linear_lift_g_fwd_f32": (i, [C.POINTER(GeccoLinearLiftG), vp, vp, vp, vp, PP, PP, i, i, vp, sz, vp]),
+    "gecco_linear_lift_g_workspace_bytes": (sz, [C.POINTER(GeccoLinearLiftG), i, i]),
     "gecco_nchw_to_nhwc_f32": (i, [vp, vp, i, i, i, i, vp]),
     "gecco_bilinear_taps_f32": (i, [vp, i, i, vp, vp, vp, vp, sz, vp]),
     "gecco_ray_lookup_taps_f32": (i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, vp]),
@@ -202,6 +210,10 @@ SIGNATURES = {
     "gecco_lift_bwd_f32": (i, [vp, vp, vp, i, i, i, vp]),
     "gecco_lower_bwd_f32": (i, [vp, vp, vp, vp, vp, sz, i, fl, vp]),
     "gecco_lower_bwd_blocks": (i, [sz]),
+    "gecco_lift_g_bwd_f32": (i, [vp, vp, vp, i, i, i, i, vp]),
+    "gecco_lower_g_bwd_f32": (i, [vp, vp, vp, vp, vp, sz, i, i, i, fl, vp]),
+    "gecco_lower_g_bwd_blocks": (i, [sz]),
+    "gecco_sampler_refresh_known_g_f64": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
     "gecco_sampler_refresh_known_f64": (i, [vp, vp, vp, vp, vp, i, i, i, i, vp]),
     "gecco_distance_matrix_f32": (i, [vp, vp, vp, i, i, i, i, vp]),
     "gecco_chamfer_f32": (i, [vp, vp, vp, vp, i, i, i, i, vp]),

@@ -1321,9 +1321,9 @@ class UnpoolAttnFn(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------------------- lift / lower
 class LiftFn(torch.autograd.Function):
-    """Linear(3 -> C) on (B, N, 3) (linear_lift.py:44-46 `lift`, models/ray.py `xyz_embed`).  The gradient with respect to the geometry
-    (dx = dy W: a Linear(C -> 3) with weight W^T, the lowering kernel) is formed only when a caller asks for it — guidance, score
-    Jacobians; the training step never does."""
+    """Linear(G -> C) on (B, N, G) (linear_lift.py:44-46 `lift`, models/ray.py `xyz_embed`).  The gradient with respect to the geometry
+    (dx = dy W: a Linear(C -> G) with weight W^T, the lowering kernel) is formed only when a caller asks for it — guidance, score
+    Jacobians; the training step never does.  G = 3 keeps its original kernels; other widths use the G-generic ones."""
 
     @staticmethod
     def forward(ctx, x, W, b):
@@ -1337,8 +1337,10 @@ class LiftFn(torch.autograd.Function):
         x, W = ctx.saved_tensors
         dy = _f(dy)
         lib = _lib.load()
-        B, N, _ = x.shape
+        B, N, G = x.shape
         Cc = ctx.C
+        if G != 3:
+            return _lift_g_backward(ctx, x, W, dy)
         dx = None
         if ctx.needs_input_grad[0]:
             one, zero = torch.ones(B, Cc, device=dy.device), torch.zeros(B, Cc, device=dy.device)
@@ -1352,8 +1354,61 @@ class LiftFn(torch.autograd.Function):
         return dx, red[:3].t().contiguous(), red[3].contiguous()
 
 
+def _lift_g_backward(ctx, x, W, dy):
+    lib = _lib.load()
+    B, N, G = x.shape
+    Cc = ctx.C
+    dx = None
+    if ctx.needs_input_grad[0]:   # a Linear(C -> G) with weight W^T: the plain lowering kernel, no GroupNorm vectors
+        dx = hip_ops.lower_edm(dy, None, None, W.t().contiguous(), None, do_norm=False)
+    if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+        return dx, None, None
+    T = lib.gecco_stats_row_tiles(N)
+    part = _new(B, T, G + 1, Cc, like=x)
+    _lib.check(lib.gecco_lift_g_bwd_f32(_ptr(dy), _ptr(x), _ptr(part), B, N, Cc, G, _stream()), "lift_g_bwd")
+    red = _reduce(part, (G + 1) * Cc, B * T, (G + 1) * Cc).reshape(G + 1, Cc)
+    return dx, red[:G].t().contiguous(), red[G].contiguous()
+
+
+def _lower_g_backward(feat, W, dF, do_norm: bool, eps: float):
+    """dfeat, dW (G, C), db (G) of F = Linear(C -> G)([LayerNorm](feat)) (lower_g_bwd_kernel)."""
+    lib = _lib.load()
+    B, N, Cc = feat.shape
+    G = W.shape[0]
+    rows = B * N
+    nb = lib.gecco_lower_g_bwd_blocks(rows)
+    stride = G * Cc + 16
+    dfeat, part = torch.empty_like(feat), _new(nb, stride, like=feat)
+    _lib.check(lib.gecco_lower_g_bwd_f32(_ptr(feat), _ptr(dF), _ptr(W), _ptr(dfeat), _ptr(part), rows, Cc, G, int(do_norm), eps,
+                                         _stream()), "lower_g_bwd")
+    red = _reduce(part, stride, nb, stride)
+    return dfeat, red[: G * Cc].reshape(G, Cc), red[G * Cc: G * Cc + G].contiguous()
+
+
+class LowerPlainFn(torch.autograd.Function):
+    """F = Linear(C -> G)(feat) on (B, N, C): LinearLift(do_norm=False)'s `lower` (reference linear_lift.py:28-29)."""
+
+    @staticmethod
+    def forward(ctx, feat, W, b):
+        feat = _f(feat)
+        ctx.save_for_backward(feat, W)
+        return hip_ops.lower_edm(feat, None, None, W, b, do_norm=False)
+
+    @staticmethod
+    def backward(ctx, dF):
+        feat, W = ctx.saved_tensors
+        return _lower_g_backward(feat, W, _f(dF), False, 0.0)
+
+
+def lower(net, feats):
+    """LinearLift's `lower` with autograd: LayerNorm + Linear(C -> G) (do_norm) or Linear(C -> G)."""
+    if net._do_norm:
+        return LowerFn.apply(feats, net.lower[1].weight, net.lower[1].bias, net.lower[0].eps)
+    return LowerPlainFn.apply(feats, net.lower.weight, net.lower.bias)
+
+
 class LowerFn(torch.autograd.Function):
-    """F = Linear(C -> 3)(LayerNorm_C(feat)) on (B, N, C)."""
+    """F = Linear(C -> G)(LayerNorm_C(feat)) on (B, N, C); G = 3 on its original kernels."""
 
     @staticmethod
     def forward(ctx, feat, W, b, eps):
@@ -1366,6 +1421,8 @@ class LowerFn(torch.autograd.Function):
     def backward(ctx, dF):
         feat, W = ctx.saved_tensors
         dF = _f(dF)
+        if W.shape[0] != 3:
+            return (*_lower_g_backward(feat, W, dF, True, ctx.eps), None)
         lib = _lib.load()
         B, N, Cc = feat.shape
         rows = B * N
@@ -1887,6 +1944,6 @@ def linear_lift_edm(net, x, sigma, sigma_data, do_cache=False, cache=None):
     c_noise = sigma.log() / 4
     feats = LiftFn.apply(c_in * x, net.lift.weight, net.lift.bias)
     feats, out_cache = set_transformer(net.inner, feats, c_noise, do_cache, cache)
-    F_x = LowerFn.apply(feats, net.lower[1].weight, net.lower[1].bias, net.lower[0].eps)
+    F_x = lower(net, feats)
     den = c_skip * x + c_out * F_x
     return (den, out_cache) if do_cache else den

@@ -1640,6 +1640,48 @@ int gecco_linear_lift_fwd_f32(const GeccoLinearLift* m, const float* x, const fl
     return 0;
 }
 
+int gecco_lift_g_f32(const float* x, const float* coef, const float* W, const float* bias, float* out, float* stats,
+                     int B, int N, int C, int G, void* stream) {
+    if (G < 1 || G > GECCO_MAX_GEOMETRY_DIM) return fail(-2, "lift_g: geometry_dim %d outside 1 .. %d", G, GECCO_MAX_GEOMETRY_DIM);
+    TRY(lift_g_launch(x, coef, W, bias, out, stats, B, N, C, G, (hipStream_t)stream), "lift_g");
+    return 0;
+}
+
+int gecco_lower_edm_g_f32(const float* feat, const float* x, const float* coef, const float* W, const float* bias, float* out,
+                          float* raw, int B, int N, int C, int G, int do_norm, float eps, void* stream) {
+    if (coef && !x) return fail(-1, "lower_edm_g: x required with coef");
+    if (G < 1 || G > GECCO_MAX_GEOMETRY_DIM) return fail(-2, "lower_edm_g: geometry_dim %d outside 1 .. %d", G, GECCO_MAX_GEOMETRY_DIM);
+    if (C <= 0 || C % 4 || C > 512) return fail(-2, "lower_edm_g: feature_dim %d (needs C %% 4 == 0, C <= 512)", C);
+    TRY(lower_g_launch(feat, x, coef, W, bias, out, raw, B, N, C, G, do_norm, eps, (hipStream_t)stream), "lower_edm_g");
+    return 0;
+}
+
+size_t gecco_linear_lift_g_workspace_bytes(const GeccoLinearLiftG* m, int B, int N) {
+    return carve_ll(&m->base, B, N, nullptr).bytes;
+}
+
+int gecco_linear_lift_g_fwd_f32(const GeccoLinearLiftG* m, const float* x, const float* sigma, float* denoised,
+                                float* raw, const float* const* h_in, float* const* h_out, int B, int N, void* ws,
+                                size_t ws_bytes, void* stream) {
+    if (!m || !x || !sigma || !(denoised || raw)) return fail(-1, "linear_lift_g: null argument");
+    const int G = m->geometry_dim, C = m->base.inner.C;
+    if (G < 1 || G > GECCO_MAX_GEOMETRY_DIM)
+        return fail(-2, "linear_lift_g: geometry_dim %d outside 1 .. %d", G, GECCO_MAX_GEOMETRY_DIM);
+    if (C % 4 || C > 512) return fail(-2, "linear_lift_g: feature_dim %d (needs C %% 4 == 0, C <= 512)", C);
+    LLWorkspace w = carve_ll(&m->base, B, N, ws);
+    if (ws_bytes < w.bytes) return fail(-7, "linear_lift_g: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    if (m->base.inner.ctx_dim != 1) return fail(-3, "linear_lift_g: t_embed_dim must be 1 under EDMPrecond");
+    TRY(edm_coeffs_launch(sigma, m->base.sigma_data, w.coef, B, s), "edm_coeffs");
+    TRY(lift_g_launch(x, w.coef, m->base.lift_w, m->base.lift_b, w.feat, w.stats, B, N, C, G, s), "lift_g");
+    int rc = st_forward(&m->base.inner, w.feat, w.coef + 4 * (size_t)B, w.stats, row_tiles_stats(N), h_in, h_out, nullptr, B,
+                        N, w.st_ws, w.st_bytes, s);
+    if (rc) return rc;
+    TRY(lower_g_launch(w.feat, x, w.coef, m->base.lower_w, m->base.lower_b, denoised, raw, B, N, C, G, m->do_norm, 1e-5f, s),
+        "lower_edm_g");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- conditional path
 int gecco_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int H, int W, void* stream) {
     TRY(nchw_to_nhwc_launch(src, dst, B, C, H, W, (hipStream_t)stream), "nchw_to_nhwc");
@@ -1971,6 +2013,20 @@ int gecco_lower_bwd_f32(const float* feat, const float* dF, const float* W, floa
     return 0;
 }
 
+int gecco_lift_g_bwd_f32(const float* dY, const float* xin, float* partial, int B, int N, int C, int G, void* stream) {
+    if (G < 1 || G > GECCO_MAX_GEOMETRY_DIM) return fail(-2, "lift_g_bwd: geometry_dim %d outside 1 .. %d", G, GECCO_MAX_GEOMETRY_DIM);
+    TRY(lift_g_bwd_launch(dY, xin, partial, B, N, C, G, (hipStream_t)stream), "lift_g_bwd");
+    return 0;
+}
+int gecco_lower_g_bwd_blocks(size_t rows) { return lower_g_bwd_blocks(rows); }
+int gecco_lower_g_bwd_f32(const float* feat, const float* dF, const float* W, float* dfeat, float* partial, size_t rows,
+                          int C, int G, int do_norm, float eps, void* stream) {
+    if (G < 1 || G > GECCO_MAX_GEOMETRY_DIM) return fail(-2, "lower_g_bwd: geometry_dim %d outside 1 .. %d", G, GECCO_MAX_GEOMETRY_DIM);
+    if (C <= 0 || C % 4 || C > 512) return fail(-2, "lower_g_bwd: feature_dim %d (needs C %% 4 == 0, C <= 512)", C);
+    TRY(lower_g_bwd_launch(feat, dF, W, dfeat, partial, rows, C, G, do_norm, eps, (hipStream_t)stream), "lower_g_bwd");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- optimizer
 int gecco_adam_ema_step_f32(const GeccoAdamEma* a, void* stream) {
     return gecco_adam_ema_step_amp_f32(a, nullptr, nullptr, nullptr, stream);
@@ -2011,6 +2067,14 @@ int gecco_sampler_refresh_known_f64(double* x, const float* known, const float* 
                                     int col, int m, int n_known, int B, void* stream) {
     if (!x || !known || !noise || !sched || !step) return fail(-1, "sampler_refresh_known: null argument");
     TRY(sampler_refresh_known_launch(x, known, noise, sched, step, col, m, n_known, B, (hipStream_t)stream), "sampler_refresh_known");
+    return 0;
+}
+int gecco_sampler_refresh_known_g_f64(double* x, const float* known, const float* noise, const double* sched, const int* step,
+                                      int col, int m, int n_known, int width, int B, void* stream) {
+    if (!x || !known || !noise || !sched || !step) return fail(-1, "sampler_refresh_known_g: null argument");
+    if (width < 1) return fail(-2, "sampler_refresh_known_g: width %d", width);
+    TRY(sampler_refresh_known_w_launch(x, known, noise, sched, step, col, m, n_known, width, B, (hipStream_t)stream),
+        "sampler_refresh_known_g");
     return 0;
 }
 int gecco_distance_matrix_f32(const float* a, const float* b, float* D, int B, int N, int M, int squared, void* stream) {

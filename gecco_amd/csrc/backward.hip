@@ -413,6 +413,153 @@ __global__ __launch_bounds__(256) void lower_bwd_v4_kernel(const float* __restri
     }
 }
 
+// ---- geometry width G (LinearLift(geometry_dim = G, do_norm), 1 <= G <= 16): the lift and lower backward of pointwise.hip's
+// lift_g / lower_g.  G = 3 with the LayerNorm keeps lift_bwd_kernel / lower_bwd_v4_kernel above.
+
+// lift backward: partial[b, tile] = {dW^T (G, C), db (C)}, (G + 1, C), from dY (B, N, C) and xin (B, N, G)
+template <int G>
+__global__ __launch_bounds__(256) void lift_g_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ xin,
+                                                         float* __restrict__ partial, int N, int C, int T, int tile_rows) {
+    extern __shared__ float xs[];   // [tile_rows][G]
+    const int tile = blockIdx.x % T, b = blockIdx.x / T;
+    const int m0 = tile * tile_rows, m1 = min(N, m0 + tile_rows);
+    for (int i = threadIdx.x; i < (m1 - m0) * G; i += blockDim.x) xs[i] = xin[((size_t)b * N + m0) * G + i];
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        float a[G + 1];
+#pragma unroll
+        for (int g = 0; g <= G; ++g) a[g] = 0.f;
+        for (int m = 0; m < m1 - m0; ++m) {
+            const float gy = dY[((size_t)b * N + m0 + m) * C + c];
+#pragma unroll
+            for (int g = 0; g < G; ++g) a[g] += gy * xs[m * G + g];
+            a[G] += gy;
+        }
+        float* p = partial + ((size_t)b * T + tile) * (G + 1) * C;
+#pragma unroll
+        for (int g = 0; g <= G; ++g) p[(size_t)g * C + c] = a[g];
+    }
+}
+
+// lower backward for G outputs, F = Linear(C -> G)([LayerNorm](feat)): dfeat, and per-block partials {dW (G, C), db (G)}.
+// lower_bwd_v4 keeps w[3][C / 32] and acc[3][C / 32] per lane and an [8][3C + 4] LDS reduction; at G = 16, C = 512 that is
+// 512 VGPRs and ~262 KB, so the work is split differently.  A tile is 16 rows, one per 16-lane group: the group holds its row in
+// registers (CPL 16-byte chunks per lane: feat read once), forms the LayerNorm statistics and dyhat = dF W by shuffles and W
+// from LDS, writes dfeat once, and parks yhat (16 x C) and dF (16 x 16) in LDS.  After a barrier the whole block accumulates
+// dW[g][c] += dF[r][g] * yhat[r][c] over the tile's rows: thread t owns the (g, 16-byte chunk) items t, t + 256, .. of the
+// G x C / 4 grid — at most P * CPL / 16 f32x4 accumulators, 32 VGPRs at G = 16, C = 512.  LDS: (G + 16) C + 256 floats.
+template <int CPL, int P, bool NORM>
+__global__ __launch_bounds__(256) void lower_g_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ dF,
+                                                          const float* __restrict__ W, float* __restrict__ dfeat,
+                                                          float* __restrict__ partial, size_t rows, int C, int G, float eps,
+                                                          int rows_per_block) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];   // W [G][C] | yhat [16][C] | dF [16][16]
+    constexpr int KMAX = (P * CPL + 15) / 16;
+    const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    const int nch = C >> 2;
+    f32x4* lw = reinterpret_cast<f32x4*>(sm);
+    f32x4* ys = lw + (size_t)G * nch;
+    float* gs = sm + (size_t)(G + 16) * C;
+    for (int i = threadIdx.x; i < G * nch; i += 256) lw[i] = reinterpret_cast<const f32x4*>(W)[i];
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    int ko[KMAX], kc[KMAX];
+    f32x4 acc[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+        const int item = threadIdx.x + 256 * k;
+        ko[k] = item < G * nch ? item / nch : -1;
+        kc[k] = item < G * nch ? item % nch : 0;
+        acc[k] = z;
+    }
+    float bacc = 0.f;
+    auto gsum = [](float v) {
+        v += __shfl_xor(v, 8, 64);
+        v += __shfl_xor(v, 4, 64);
+        v += __shfl_xor(v, 2, 64);
+        v += __shfl_xor(v, 1, 64);
+        return v;
+    };
+    __syncthreads();
+    const size_t r0 = (size_t)blockIdx.x * rows_per_block;
+    for (int t0 = 0; t0 < rows_per_block; t0 += 16) {
+        const size_t row = r0 + t0 + grp;
+        const bool live = row < rows;
+        f32x4 f[CPL];
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int ch = sub + 16 * i;
+            f[i] = live && ch < nch ? *(reinterpret_cast<const f32x4*>(feat + row * C) + ch) : z;
+        }
+        float g[P];
+#pragma unroll
+        for (int o = 0; o < P; ++o) g[o] = live && o < G ? dF[row * G + o] : 0.f;
+        float rstd = 1.f;
+        if (NORM) {
+            float s1 = 0.f;
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) s1 += (f[i][0] + f[i][1]) + (f[i][2] + f[i][3]);
+            const float mean = gsum(s1) / C;
+            float s2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) {
+                const int ch = sub + 16 * i;
+                f[i] = ch < nch ? f[i] - mean : z;
+                const f32x4 d = f[i] * f[i];
+                s2 += (d[0] + d[1]) + (d[2] + d[3]);
+            }
+            rstd = rsqrtf(gsum(s2) / C + eps);
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) f[i] = f[i] * rstd;   // yhat
+        }
+        f32x4 dyh[CPL];
+        float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int ch = sub + 16 * i;
+            dyh[i] = z;
+            if (ch < nch) {
+#pragma unroll
+                for (int o = 0; o < P; ++o)
+                    if (o < G) dyh[i] += lw[o * nch + ch] * g[o];
+                ys[grp * nch + ch] = f[i];
+            }
+            if (NORM) {
+                const f32x4 e = dyh[i] * f[i];
+                m1 += (dyh[i][0] + dyh[i][1]) + (dyh[i][2] + dyh[i][3]);
+                m2 += (e[0] + e[1]) + (e[2] + e[3]);
+            }
+        }
+        if (NORM) {
+            m1 = gsum(m1) / C;
+            m2 = gsum(m2) / C;
+        }
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) {
+                const int ch = sub + 16 * i;
+                if (ch < nch)
+                    *(reinterpret_cast<f32x4*>(dfeat + row * C) + ch) = NORM ? (dyh[i] - m1 - f[i] * m2) * rstd : dyh[i];
+            }
+        }
+        gs[grp * 16 + sub] = sub < P ? g[sub < P ? sub : 0] : 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (ko[k] >= 0) {
+#pragma unroll 4
+                for (int r = 0; r < 16; ++r) acc[k] += ys[r * nch + kc[k]] * gs[r * 16 + ko[k]];
+            }
+        if (threadIdx.x < G)
+            for (int r = 0; r < 16; ++r) bacc += gs[r * 16 + threadIdx.x];
+        __syncthreads();
+    }
+    float* p = partial + (size_t)blockIdx.x * ((size_t)G * C + 16);
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+        if (ko[k] >= 0) *reinterpret_cast<f32x4*>(p + (size_t)ko[k] * C + 4 * kc[k]) = acc[k];
+    if (threadIdx.x < 16) p[(size_t)G * C + threadIdx.x] = threadIdx.x < G ? bacc : 0.f;
+}
+
 unsigned grid_for(size_t n) {
     size_t g = (n + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
@@ -489,5 +636,69 @@ int lower_bwd_launch(const float* feat, const float* dF, const float* W, float* 
     }
     hipLaunchKernelGGL(lower_bwd_kernel, dim3((unsigned)lower_bwd_blocks(rows)), dim3(256), lds, st, feat, dF, W, dfeat,
                        partial, rows, C, eps, 128);
+    return (int)hipGetLastError();
+}
+
+int lift_g_bwd_launch(const float* dY, const float* xin, float* partial, int B, int N, int C, int G, hipStream_t st) {
+    if (G < 1 || G > GECCO_MAX_GEOMETRY) return -2;
+    if (B <= 0 || N <= 0) return 0;
+    const int tr = stats_row_tile(N), T = (N + tr - 1) / tr;
+    const size_t lds = (size_t)tr * G * sizeof(float);
+    switch (G) {
+#define LIFT_G_BWD(GG) case GG: hipLaunchKernelGGL((lift_g_bwd_kernel<GG>), dim3(B * T), dim3(256), lds, st, dY, xin, partial, N, C, T, tr); break;
+        LIFT_G_BWD(1) LIFT_G_BWD(2) LIFT_G_BWD(3) LIFT_G_BWD(4) LIFT_G_BWD(5) LIFT_G_BWD(6) LIFT_G_BWD(7) LIFT_G_BWD(8)
+        LIFT_G_BWD(9) LIFT_G_BWD(10) LIFT_G_BWD(11) LIFT_G_BWD(12) LIFT_G_BWD(13) LIFT_G_BWD(14) LIFT_G_BWD(15) LIFT_G_BWD(16)
+#undef LIFT_G_BWD
+    }
+    return (int)hipGetLastError();
+}
+
+namespace {
+constexpr int LOWER_G_BWD_ROWS = 128;   // rows per block: 8 tiles of 16
+
+template <int CPL, int P, bool NORM>
+void lower_g_bwd_go(unsigned nblk, size_t lds, hipStream_t st, const float* feat, const float* dF, const float* W, float* dfeat,
+                    float* partial, size_t rows, int C, int G, float eps) {
+    static size_t attr = 0;   // (G + 16) C + 256 floats: 66.5 KB at G = 16, C = 512, above the 64 KB default
+    if (lds > 64 * 1024 && lds > attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lower_g_bwd_kernel<CPL, P, NORM>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr = lds;
+    }
+    hipLaunchKernelGGL((lower_g_bwd_kernel<CPL, P, NORM>), dim3(nblk), dim3(256), lds, st, feat, dF, W, dfeat, partial, rows, C, G,
+                       eps, LOWER_G_BWD_ROWS);
+}
+template <int CPL, int P>
+void lower_g_bwd_norm(bool norm, unsigned nblk, size_t lds, hipStream_t st, const float* feat, const float* dF, const float* W,
+                      float* dfeat, float* partial, size_t rows, int C, int G, float eps) {
+    if (norm) lower_g_bwd_go<CPL, P, true>(nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
+    else lower_g_bwd_go<CPL, P, false>(nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
+}
+template <int CPL>
+void lower_g_bwd_p(int P, bool norm, unsigned nblk, size_t lds, hipStream_t st, const float* feat, const float* dF, const float* W,
+                   float* dfeat, float* partial, size_t rows, int C, int G, float eps) {
+    switch (P) {
+        case 1: lower_g_bwd_norm<CPL, 1>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
+        case 2: lower_g_bwd_norm<CPL, 2>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
+        case 4: lower_g_bwd_norm<CPL, 4>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
+        case 8: lower_g_bwd_norm<CPL, 8>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
+        default: lower_g_bwd_norm<CPL, 16>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
+    }
+}
+}  // namespace
+
+int lower_g_bwd_blocks(size_t rows) { return (int)((rows + LOWER_G_BWD_ROWS - 1) / LOWER_G_BWD_ROWS); }
+int lower_g_bwd_launch(const float* feat, const float* dF, const float* W, float* dfeat, float* partial, size_t rows, int C,
+                       int G, int do_norm, float eps, hipStream_t st) {
+    if (G < 1 || G > GECCO_MAX_GEOMETRY || C <= 0 || C % 4 || C > 512) return -2;
+    if (rows == 0) return 0;
+    const unsigned nblk = (unsigned)lower_g_bwd_blocks(rows);
+    const size_t lds = ((size_t)(G + 16) * C + 256) * sizeof(float);
+    const int cpl = (C / 4 + 15) / 16, P = geometry_pow2(G);
+    switch (cpl) {
+#define LOWER_G_BWD(CPL) case CPL: lower_g_bwd_p<CPL>(P, do_norm != 0, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
+        LOWER_G_BWD(1) LOWER_G_BWD(2) LOWER_G_BWD(3) LOWER_G_BWD(4) LOWER_G_BWD(5) LOWER_G_BWD(6) LOWER_G_BWD(7) LOWER_G_BWD(8)
+#undef LOWER_G_BWD
+    }
     return (int)hipGetLastError();
 }

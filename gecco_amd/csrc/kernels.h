@@ -302,6 +302,11 @@ int lift_bwd_launch(const float* dY, const float* xin, float* partial, int B, in
 int lower_bwd_blocks(size_t rows);
 int lower_bwd_launch(const float* feat, const float* dF, const float* W, float* dfeat, float* partial, size_t rows,
                      int C, float eps, hipStream_t st);
+// partial (B, stats row tiles, G + 1, C) = {dW^T rows, db}; lower: partial (lower_g_bwd_blocks, G * C + 16) = {dW (G, C), db (G)}
+int lift_g_bwd_launch(const float* dY, const float* xin, float* partial, int B, int N, int C, int G, hipStream_t st);
+int lower_g_bwd_blocks(size_t rows);
+int lower_g_bwd_launch(const float* feat, const float* dF, const float* W, float* dfeat, float* partial, size_t rows, int C,
+                       int G, int do_norm, float eps, hipStream_t st);
 
 // attention_f32.hip
 // precision 1 = split-bf16, 2 = fp16 arithmetic (attention_x3.hip) when the head dim allows, else the exact fp32 kernels
@@ -400,6 +405,14 @@ int lift_launch(const float* x, const float* coef, const float* W, const float* 
 int lower_edm_launch(const float* feat, const float* x, const float* coef, const float* W, const float* bias,
                      const float* gn_a, const float* gn_o, float* out, float* raw, int B, int N, int C, float eps,
                      hipStream_t st);
+// geometry width G (1 .. GECCO_MAX_GEOMETRY) and LinearLift(do_norm=False): out = (c_in x) W^T + b with W (C, G);
+// F = Linear(C -> G)([LayerNorm](feat)), D = c_skip x + c_out F with W (G, C), C % 4 == 0, C <= 512
+#define GECCO_MAX_GEOMETRY 16
+int geometry_pow2(int G);
+int lift_g_launch(const float* x, const float* coef, const float* W, const float* bias, float* out, float* stats, int B,
+                  int N, int C, int G, hipStream_t st);
+int lower_g_launch(const float* feat, const float* x, const float* coef, const float* W, const float* bias, float* out,
+                   float* raw, int B, int N, int C, int G, int do_norm, float eps, hipStream_t st);
 
 // optim.hip — Adam + EMA shadow weights in one pass over flat fp32 buffers (n % 4 == 0, 16-byte aligned)
 struct AdamEmaArgs {
@@ -439,6 +452,8 @@ int sinkhorn_cost_launch(const float* C, const float* f, const float* g, float* 
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);
+int sampler_refresh_known_w_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
+                                   int m, int n_known, int width, int B, hipStream_t st);
 
 // convnext.hip — channels-last ConvNeXt conditioner pieces (the pointwise linears run on the fused GEMM)
 // zout (optional): the LayerNorm's input as well (training).  dwconv: ln_w == null -> out is the plain convolution (bias optional)

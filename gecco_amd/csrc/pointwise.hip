@@ -501,6 +501,160 @@ __global__ __launch_bounds__(256) void lower_edm_v5_kernel(const float* __restri
     }
 }
 
+// ---- geometry width G != 3 or LinearLift(do_norm=False) (reference linear_lift.py:14-31): the lift and the lower of a
+// G-component geometry, 1 <= G <= 16.  G = 3 with the LayerNorm keeps lift_kernel / lower_edm_v4 / v5 above.
+
+// lift_kernel for G components: same tile, same statistics, the same left-to-right dot-product association
+template <int G>
+__global__ __launch_bounds__(256) void lift_g_kernel(const float* __restrict__ x, const float* __restrict__ coef,
+                                                     const float* __restrict__ W, const float* __restrict__ bias,
+                                                     float* __restrict__ out, float* __restrict__ stats, int N, int C,
+                                                     int T) {
+    __shared__ float xs[STATS_ROWS * G];
+    const int tile = blockIdx.x % T, b = blockIdx.x / T;
+    const int m0 = tile * STATS_ROWS, m1 = min(N, m0 + STATS_ROWS);
+    const float cin = coef ? coef[4 * b + 2] : 1.0f;
+    for (int i = threadIdx.x; i < (m1 - m0) * G; i += blockDim.x) xs[i] = cin * x[((size_t)b * N + m0) * G + i];
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        float w[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) w[g] = W[c * G + g];
+        const float bb = bias ? bias[c] : 0.f;
+        float s1 = 0.f, s2 = 0.f;
+        for (int m = 0; m < m1 - m0; ++m) {
+            float v = xs[m * G] * w[0];
+#pragma unroll
+            for (int g = 1; g < G; ++g) v += xs[m * G + g] * w[g];
+            v += bb;
+            out[((size_t)b * N + m0 + m) * C + c] = v;
+            s1 += v;
+            s2 += v * v;
+        }
+        if (stats) {
+            stats[(((size_t)b * T + tile) * 2 + 0) * C + c] = s1;
+            stats[(((size_t)b * T + tile) * 2 + 1) * C + c] = s2;
+        }
+    }
+}
+
+// Reduce-scatter of P per-lane partial sums (P = G rounded up to a power of two) over a 16-lane group.  Recursive halving over
+// the lane offsets 8, 4, .. 16 / P: at each step a lane keeps the half of its outputs that its offset bit selects and adds the
+// partner's copy of that half; plain sums over the remaining offsets then finish it.  Lane sub ends with the full sum of output
+// sub >> (4 - log2 P).  Cost: P - 1 + 4 - log2 P shuffles (15 at P = 16, against 64 for sixteen independent 4-shuffle sums).
+template <int P>
+__device__ __forceinline__ float group_reduce_scatter(float (&a)[P], int sub) {
+#pragma unroll
+    for (int o = 8, h = P / 2; h >= 1; o >>= 1, h >>= 1) {
+        const bool hi = (sub & o) != 0;
+#pragma unroll
+        for (int j = 0; j < h; ++j) {
+            const float send = hi ? a[j] : a[j + h];
+            const float keep = hi ? a[j + h] : a[j];
+            a[j] = keep + __shfl_xor(send, o, 64);
+        }
+    }
+    float r = a[0];
+#pragma unroll
+    for (int o = 8 / P; o >= 1; o >>= 1) r += __shfl_xor(r, o, 64);
+    return r;
+}
+
+template <int P>
+__device__ __forceinline__ constexpr int log2_pow2() { return P >= 16 ? 4 : P >= 8 ? 3 : P >= 4 ? 2 : P >= 2 ? 1 : 0; }
+
+// lower_edm_v5's layout for G outputs: a 16-lane group per row, rpg rows per group (the next row's chunks load while this one
+// reduces), W [G][C] staged in LDS once per block.  NORM: per-point LayerNorm (linear_lift.py:25-27); else the plain
+// Linear(C -> G) of do_norm=False — no statistics passes and no GroupNorm vectors.  D = c_skip * x + c_out * F.
+template <int CPL, int P, bool NORM>
+__global__ __launch_bounds__(256) void lower_g_kernel(const float* __restrict__ feat, const float* __restrict__ x,
+                                                      const float* __restrict__ coef, const float* __restrict__ W,
+                                                      const float* __restrict__ bias, float* __restrict__ out,
+                                                      float* __restrict__ raw, int B, int N, int C, int G, float eps,
+                                                      int rpg) {
+    extern __shared__ __attribute__((aligned(16))) float lw[];   // W [G][C]
+    const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    const size_t rows = (size_t)B * N;
+    const size_t row0 = (size_t)blockIdx.x * 16 * rpg;
+    const int nch = C >> 2;
+    for (int i = threadIdx.x; i < G * nch; i += 256) reinterpret_cast<f32x4*>(lw)[i] = reinterpret_cast<const f32x4*>(W)[i];
+    __syncthreads();
+    auto gsum = [](float v) {
+        v += __shfl_xor(v, 8, 64);
+        v += __shfl_xor(v, 4, 64);
+        v += __shfl_xor(v, 2, 64);
+        v += __shfl_xor(v, 1, 64);
+        return v;
+    };
+    constexpr int SH = 4 - log2_pow2<P>();
+    const int oi = sub >> SH;                                   // the output this lane holds after the reduce-scatter
+    const bool writer = (sub & ((1 << SH) - 1)) == 0 && oi < G;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    auto row_of = [&](int rr) { return row0 + (size_t)rr * 16 + grp; };
+    auto load = [&](f32x4 (&v)[CPL], int rr) {
+        const size_t rraw = row_of(rr);
+        const size_t row = rraw < rows ? rraw : rows - 1;   // idle groups shadow the last row: the shuffles stay full-width
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int ch = sub + 16 * i;
+            v[i] = ch < nch ? *(reinterpret_cast<const f32x4*>(feat + row * C) + ch) : z;
+        }
+    };
+    f32x4 v[CPL], vn[CPL];
+    load(v, 0);
+#pragma unroll 1
+    for (int rr = 0; rr < rpg; ++rr) {
+        if (rr + 1 < rpg) load(vn, rr + 1);
+        const size_t row_raw = row_of(rr);
+        const bool live = row_raw < rows;
+        const size_t row = live ? row_raw : rows - 1;
+        if (NORM) {
+            float s1 = 0.f;
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) s1 += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+            const float mean = gsum(s1) / C;
+            float s2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) {
+                const int ch = sub + 16 * i;
+                const f32x4 d = ch < nch ? v[i] - mean : z;
+                v[i] = d;
+                s2 += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+            }
+            const float rstd = rsqrtf(gsum(s2) / C + eps);
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) v[i] = v[i] * rstd;
+        }
+        float a[P];
+#pragma unroll
+        for (int o = 0; o < P; ++o) a[o] = 0.f;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int ch = sub + 16 * i;
+            if (ch < nch) {
+#pragma unroll
+                for (int o = 0; o < P; ++o)
+                    if (o < G) {
+                        const f32x4 w = reinterpret_cast<const f32x4*>(lw)[o * nch + ch];
+                        a[o] += (v[i][0] * w[0] + v[i][1] * w[1]) + (v[i][2] * w[2] + v[i][3] * w[3]);
+                    }
+            }
+        }
+        const float r = group_reduce_scatter<P>(a, sub);
+        if (live && writer) {
+            const int b = (int)(row / N);
+            const float Fv = r + (bias ? bias[oi] : 0.f);
+            if (raw) raw[row * G + oi] = Fv;
+            if (out) {
+                const float cs = coef ? coef[4 * b + 0] : 0.f, co = coef ? coef[4 * b + 1] : 1.f;
+                out[row * G + oi] = coef ? cs * x[row * G + oi] + co * Fv : Fv;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) v[i] = vn[i];
+    }
+}
+
 }  // namespace
 
 int stats_row_tile(int rows) { (void)rows; return STATS_ROWS; }
@@ -616,5 +770,61 @@ int lower_edm_launch(const float* feat, const float* x, const float* coef, const
                            gn_a, gn_o, out, raw, B, N, C, eps);
     }
 #undef LOWER_V4
+    return (int)hipGetLastError();
+}
+
+int geometry_pow2(int G) { return G <= 1 ? 1 : G <= 2 ? 2 : G <= 4 ? 4 : G <= 8 ? 8 : 16; }
+
+int lift_g_launch(const float* x, const float* coef, const float* W, const float* bias, float* out, float* stats, int B,
+                  int N, int C, int G, hipStream_t st) {
+    if (G < 1 || G > GECCO_MAX_GEOMETRY) return -2;
+    const int T = (N + STATS_ROWS - 1) / STATS_ROWS;
+    if (B <= 0 || N <= 0) return 0;
+    switch (G) {
+#define LIFT_G(GG) case GG: hipLaunchKernelGGL((lift_g_kernel<GG>), dim3(B * T), dim3(256), 0, st, x, coef, W, bias, out, stats, N, C, T); break;
+        LIFT_G(1) LIFT_G(2) LIFT_G(3) LIFT_G(4) LIFT_G(5) LIFT_G(6) LIFT_G(7) LIFT_G(8)
+        LIFT_G(9) LIFT_G(10) LIFT_G(11) LIFT_G(12) LIFT_G(13) LIFT_G(14) LIFT_G(15) LIFT_G(16)
+#undef LIFT_G
+    }
+    return (int)hipGetLastError();
+}
+
+namespace {
+template <int CPL, int P>
+void lower_g_dispatch(bool norm, dim3 grid, size_t lds, hipStream_t st, const float* feat, const float* x, const float* coef,
+                      const float* W, const float* bias, float* out, float* raw, int B, int N, int C, int G, float eps, int rpg) {
+    if (norm)
+        hipLaunchKernelGGL((lower_g_kernel<CPL, P, true>), grid, dim3(256), lds, st, feat, x, coef, W, bias, out, raw, B, N, C, G, eps, rpg);
+    else
+        hipLaunchKernelGGL((lower_g_kernel<CPL, P, false>), grid, dim3(256), lds, st, feat, x, coef, W, bias, out, raw, B, N, C, G, eps, rpg);
+}
+template <int CPL>
+void lower_g_dispatch_p(int P, bool norm, dim3 grid, size_t lds, hipStream_t st, const float* feat, const float* x,
+                        const float* coef, const float* W, const float* bias, float* out, float* raw, int B, int N, int C,
+                        int G, float eps, int rpg) {
+    switch (P) {
+        case 1: lower_g_dispatch<CPL, 1>(norm, grid, lds, st, feat, x, coef, W, bias, out, raw, B, N, C, G, eps, rpg); break;
+        case 2: lower_g_dispatch<CPL, 2>(norm, grid, lds, st, feat, x, coef, W, bias, out, raw, B, N, C, G, eps, rpg); break;
+        case 4: lower_g_dispatch<CPL, 4>(norm, grid, lds, st, feat, x, coef, W, bias, out, raw, B, N, C, G, eps, rpg); break;
+        case 8: lower_g_dispatch<CPL, 8>(norm, grid, lds, st, feat, x, coef, W, bias, out, raw, B, N, C, G, eps, rpg); break;
+        default: lower_g_dispatch<CPL, 16>(norm, grid, lds, st, feat, x, coef, W, bias, out, raw, B, N, C, G, eps, rpg); break;
+    }
+}
+}  // namespace
+
+int lower_g_launch(const float* feat, const float* x, const float* coef, const float* W, const float* bias, float* out,
+                   float* raw, int B, int N, int C, int G, int do_norm, float eps, hipStream_t st) {
+    if (G < 1 || G > GECCO_MAX_GEOMETRY || C <= 0 || C % 4 || C > 512) return -2;
+    const size_t rows = (size_t)B * N;
+    if (rows == 0) return 0;
+    const int cpl = (C / 4 + 15) / 16, P = geometry_pow2(G);
+    const int rpg = rows >= (size_t)16 * 8 * 512 ? 8 : 1;   // lower_edm_launch's threshold for its v5 form
+    const dim3 grid((unsigned)((rows + 16 * rpg - 1) / (16 * rpg)));
+    const size_t lds = (size_t)G * C * sizeof(float);
+    switch (cpl) {
+#define LOWER_G(CPL) case CPL: lower_g_dispatch_p<CPL>(P, do_norm != 0, grid, lds, st, feat, x, coef, W, bias, out, raw, B, N, C, G, eps, rpg); break;
+        LOWER_G(1) LOWER_G(2) LOWER_G(3) LOWER_G(4) LOWER_G(5) LOWER_G(6) LOWER_G(7) LOWER_G(8)
+#undef LOWER_G
+    }
     return (int)hipGetLastError();
 }

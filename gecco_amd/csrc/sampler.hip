@@ -45,6 +45,18 @@ __global__ void refresh_known_f64_kernel(double* __restrict__ x, const float* __
     }
 }
 
+// The same for rows of `width` components (a LinearLift of geometry_dim = width); x is (B, m + n_known, width) fp64.
+__global__ void refresh_known_w_f64_kernel(double* __restrict__ x, const float* __restrict__ known, const float* __restrict__ noise,
+                                           const double* __restrict__ sched, const int* __restrict__ step, int col, int m,
+                                           int n_known, int width, int B) {
+    const float c = (float)sched[(size_t)(*step) * SCHED_COLS + col];
+    const size_t per = (size_t)n_known * width, total = (size_t)B * per;
+    for (size_t i = gid(); i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / per, r = i % per;
+        x[(b * (size_t)(m + n_known) + m) * width + r] = (double)known[i] + (double)(c * noise[i]);
+    }
+}
+
 // data_ctx = data + noise * (float)t_cur, all fp32 (diffusion.py:430)
 __global__ void add_noise_f32_kernel(const float* __restrict__ x, const float* __restrict__ noise,
                                      size_t noise_step_stride, const double* __restrict__ sched,
@@ -252,5 +264,12 @@ int relu_bwd_launch(const float* y, const float* dy, float* du, size_t n, hipStr
 }
 int gaussian_act_launch(const float* x, const float* alpha, float* y, size_t n, int normalized, hipStream_t st) {
     hipLaunchKernelGGL(gaussian_act_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, alpha, y, n, normalized);
+    return (int)hipGetLastError();
+}
+int sampler_refresh_known_w_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
+                                   int m, int n_known, int width, int B, hipStream_t st) {
+    if (width < 1) return -2;
+    hipLaunchKernelGGL(refresh_known_w_f64_kernel, dim3(grid_for((size_t)B * n_known * width)), dim3(256), 0, st, x, known, noise,
+                       sched, step, col, m, n_known, width, B);
     return (int)hipGetLastError();
 }

@@ -168,7 +168,7 @@ def _vp(t: Tensor | None):
 
 
 class _SamplerState:
-    """Device buffers + kernel launches of one trajectory over `shape` = (B, n, 3)."""
+    """Device buffers + kernel launches of one trajectory over `shape` = (B, n, G)."""
 
     def __init__(self, shape, device, sched_host: Tensor):
         self.lib = _lib.load()
@@ -409,7 +409,7 @@ class Diffusion(_Base):
         `Diffusion.solve_sample_ode` integrates with diffrax's Heun solver on the schedule's time grid
         (gecco-jax models/diffusion.py:333-374); the torch package does not ship it (gecco-torch/README.md:49-52).  Same
         device loop as `sample_stochastic` with S_churn = 0: num_steps steps = 2 num_steps - 1 evaluations, fp64 state,
-        one captured hipGraph per step.  `latents` (optional, (B, N, 3)): the starting noise instead of a generator draw.
+        one captured hipGraph per step.  `latents` (optional, (B, N, G)): the starting noise instead of a generator draw.
 
         Where the two differ (parity unpinned: jax / diffrax are absent from the image).  diffrax's Heun applies the second-order
         correction on EVERY step of `StepTo(ts)`, and the JAX schedule's last time is its sigma_min > 0, where the trajectory ends
@@ -433,13 +433,14 @@ class Diffusion(_Base):
     @_frozen_weights
     def sample_inpaint(self, known: Tensor, m_to_inpaint: int, context: Context3d | None = None, num_substeps: int = 1,
                        seed: int | None = 42, noise: Sequence[Tensor] | None = None, **kwargs) -> Tensor:
-        """Completion of partial clouds (gecco-jax models/stochastic.py:101-231, `sample_inpaint`): `known` (B, n, 3) data-space
+        """Completion of partial clouds (gecco-jax models/stochastic.py:101-231, `sample_inpaint`): `known` (B, n, G) data-space
         points are kept — re-noised to the current level at every sub-step — while `m_to_inpaint` new points are sampled
-        jointly with them; returns the (B, m, 3) new points in data space (fp64).  Per step i, sub-step j: refresh the
+        jointly with them; returns the (B, m, G) new points in data space (fp64).  Per step i, sub-step j: refresh the
         known part at sigma_i, churn, Euler step to sigma_{i+1}, 2nd-order correction when i < steps - 1, and between
         sub-steps noise back up from sigma_{i+1} to sigma_i.  The JAX package draws per-step keys; here a generator
-        (`seed`) or the injected `noise` list supplies the draws in call order: [initial (B, m + n, 3)], then per
-        (i, j): known-part noise (B, n, 3), churn noise (B, m + n, 3) [, redo noise (B, m + n, 3) when j < num_substeps - 1]."""
+        (`seed`) or the injected `noise` list supplies the draws in call order: [initial (B, m + n, G)], then per
+        (i, j): known-part noise (B, n, G), churn noise (B, m + n, G) [, redo noise (B, m + n, G) when j < num_substeps - 1].
+        G = known.shape[-1], the model's geometry_dim."""
         kw = {**self.sampler_kwargs, **kwargs}
         num_steps = kw["num_steps"]
         device, dtype = self.example_param.device, self.example_param.dtype
@@ -458,29 +459,33 @@ class Diffusion(_Base):
             return torch.randn(tuple(shape), device=device, dtype=dtype, generator=rng)
 
         known = known.to(device=device, dtype=dtype).contiguous()
-        B, n, _ = known.shape
+        B, n, G = known.shape
         m = int(m_to_inpaint)
         known_diff = self.reparam.data_to_diffusion(known, context).contiguous()
         post_context = self.conditioner(context)
         ts = karras_t_steps(num_steps, kw["sigma_max"], kw["sigma_min"], kw["rho"])
         sched = build_schedule_table(ts, num_steps, kw["S_churn"], kw["S_min"], kw["S_max"], kw["S_noise"])
-        st = _SamplerState((B, m + n, 3), device, sched)
+        st = _SamplerState((B, m + n, G), device, sched)
         lib = st.lib
 
         def refresh():   # x_cur[:, m:] = known_diff + randn * sigma_cur
             nz = randn(known.shape)
-            _lib.check(lib.gecco_sampler_refresh_known_f64(_vp(st.x_cur), _vp(known_diff), _vp(nz), _vp(st.sched), _vp(st.step),
-                                                           0, m, n, B, st._s()), "sampler_refresh_known")
+            if G == 3:
+                _lib.check(lib.gecco_sampler_refresh_known_f64(_vp(st.x_cur), _vp(known_diff), _vp(nz), _vp(st.sched), _vp(st.step),
+                                                               0, m, n, B, st._s()), "sampler_refresh_known")
+            else:
+                _lib.check(lib.gecco_sampler_refresh_known_g_f64(_vp(st.x_cur), _vp(known_diff), _vp(nz), _vp(st.sched),
+                                                                 _vp(st.step), 0, m, n, G, B, st._s()), "sampler_refresh_known_g")
 
         # x_init = [0 | known_diff] + randn * sigma_0  (stochastic.py:189-197)
-        init = randn((B, m + n, 3))
-        base = torch.zeros(B, m + n, 3, device=device, dtype=dtype)
+        init = randn((B, m + n, G))
+        base = torch.zeros(B, m + n, G, device=device, dtype=dtype)
         base[:, m:] = known_diff
         st.x_cur.copy_(base.double() + (init * float(ts[0])).double())
         for i in range(num_steps):
             for j in range(num_substeps):
                 refresh()
-                st.churn(randn((B, m + n, 3)), 0)
+                st.churn(randn((B, m + n, G)), 0)
                 self(st.x_in, st.sigma, context, post_context, out=st.den)
                 st.euler()
                 if i < num_steps - 1:
@@ -489,7 +494,7 @@ class Diffusion(_Base):
                 else:
                     st.x_cur.copy_(st.x_next)
                 if j < num_substeps - 1:
-                    st.redo(randn((B, m + n, 3)))
+                    st.redo(randn((B, m + n, G)))
             st.advance()
         return self.reparam.diffusion_to_data(st.x_cur, context)[:, :m]
 
@@ -502,10 +507,10 @@ class Diffusion(_Base):
         eps^T J eps for Rademacher probes eps, the SAME probes at every evaluation, as the JAX code's constant `noise_key` makes them);
         logp = log N(latent; 0, sigma_max^2) + the integrated divergence + the reparametrisation's log |det|.
 
-        With the EDM schedule (sigma(t) = t, scale 1) dx/dt = (x - D(x; t)) / t, so eps^T J eps = (n - eps^T J_D eps) / t with n = 3 N:
+        With the EDM schedule (sigma(t) = t, scale 1) dx/dt = (x - D(x; t)) / t, so eps^T J eps = (n - eps^T J_D eps) / t with n = G N:
         one evaluation of the denoiser and one vector-Jacobian product through it (the HIP autograd Functions' input gradients,
-        `test_gradient_with_respect_to_the_noisy_cloud`) per probe and ODE stage.  data (B, N, 3) in data space -> (B,) fp64.
-        `probes` (optional, (n_trace_samples, B, N, 3) of +-1) replaces the generator draw (parity tests).  The state is fp64, the
+        `test_gradient_with_respect_to_the_noisy_cloud`) per probe and ODE stage.  data (B, N, G) in data space -> (B,) fp64.
+        `probes` (optional, (n_trace_samples, B, N, G) of +-1) replaces the generator draw (parity tests).  The state is fp64, the
         network input fp32, as in the samplers.  Parity unpinned (jax / diffrax absent): the test compares with `oracle/cpu_ref.py`'s
         restatement on torch autograd.  The reparametrisation's log |det| comes from `Reparam.ladj_data_to_diffusion` (closed forms:
         NoReparam 0, GaussianReparam -N sum_d log sigma_d, UVLReparam per point from the pinhole projection, atanh and log-range —
@@ -537,7 +542,7 @@ class Diffusion(_Base):
             q.requires_grad_(False)       # only the input carries a gradient: the weight-gradient kernels are skipped
 
         def field(t: float, xs: Tensor):
-            """(dx/dt, d logp/dt) at (t, xs): fp64 tensors (B, N, 3), (B,)."""
+            """(dx/dt, d logp/dt) at (t, xs): fp64 tensors (B, N, G), (B,)."""
             with torch.enable_grad():
                 xg = xs.float().requires_grad_(True)
                 D = self(xg, torch.full((B,), t, device=device, dtype=torch.float32), context, post_context)

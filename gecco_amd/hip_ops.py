@@ -536,27 +536,50 @@ def edm_coeffs(sigma: Tensor, sigma_data: float = 1.0) -> Tensor:
     return coef
 
 
-def lift(x: Tensor, coef: Tensor | None, W: Tensor, bias: Tensor, want_stats: bool = False):
+MAX_GEOMETRY_DIM = 16   # GECCO_MAX_GEOMETRY_DIM: the 16-lane row group of the lowering kernels, one lane per output
+
+
+def check_geometry_dim(G: int) -> None:
+    if not 1 <= G <= MAX_GEOMETRY_DIM:
+        raise ValueError(f"the HIP LinearLift supports geometry_dim 1 .. {MAX_GEOMETRY_DIM}, got {G}")
+
+
+def lift(x: Tensor, coef: Tensor | None, W: Tensor, bias: Tensor | None, want_stats: bool = False):
+    """(c_in x) W^T + b on (B, N, G), G from the shapes: G = 3 on the original kernel, other widths on the G-generic one."""
     lib = _lib.load()
-    B, N, three = x.shape
-    assert three == 3 and W.shape[1] == 3
+    B, N, G = x.shape
+    assert W.shape[1] == G, (W.shape, x.shape)
     Cc = W.shape[0]
     out = torch.empty(B, N, Cc, device=x.device, dtype=torch.float32)
     stats = torch.empty(B, lib.gecco_stats_row_tiles(N), 2, Cc, device=x.device, dtype=torch.float32) if want_stats else None
-    check(lib.gecco_lift_f32(_ptr(x), _ptr(coef), _ptr(W), _ptr(bias), _ptr(out), _ptr(stats), B, N, Cc, _stream()),
-          "gecco_lift_f32")
+    if G == 3:
+        check(lib.gecco_lift_f32(_ptr(x), _ptr(coef), _ptr(W), _ptr(bias), _ptr(out), _ptr(stats), B, N, Cc, _stream()),
+              "gecco_lift_f32")
+    else:
+        check_geometry_dim(G)
+        check(lib.gecco_lift_g_f32(_ptr(x), _ptr(coef), _ptr(W), _ptr(bias), _ptr(out), _ptr(stats), B, N, Cc, G, _stream()),
+              "gecco_lift_g_f32")
     return (out, stats) if want_stats else out
 
 
-def lower_edm(feat: Tensor, x: Tensor | None, coef: Tensor | None, W: Tensor, bias: Tensor,
-              gn: tuple[Tensor, Tensor] | None = None, want_raw: bool = False, eps: float = GN_EPS):
+def lower_edm(feat: Tensor, x: Tensor | None, coef: Tensor | None, W: Tensor, bias: Tensor | None,
+              gn: tuple[Tensor, Tensor] | None = None, want_raw: bool = False, eps: float = GN_EPS, do_norm: bool = True):
+    """F = Linear(C -> G)(LayerNorm(feat)) (do_norm) or Linear(C -> G)(feat) (do_norm=False), or the GroupNorm form `gn`
+    (G = 3 only); D = c_skip x + c_out F.  G = W.shape[0]: G = 3 with a norm keeps the original kernels."""
     lib = _lib.load()
     B, N, Cc = feat.shape
-    out = torch.empty(B, N, 3, device=feat.device, dtype=torch.float32)
+    G = W.shape[0]
+    out = torch.empty(B, N, G, device=feat.device, dtype=torch.float32)
     raw = torch.empty_like(out) if want_raw else None
-    check(lib.gecco_lower_edm_f32(_ptr(feat), _ptr(x), _ptr(coef), _ptr(W), _ptr(bias), _ptr(gn[0]) if gn else None,
-                                  _ptr(gn[1]) if gn else None, _ptr(out), _ptr(raw), B, N, Cc, eps, _stream()),
-          "gecco_lower_edm_f32")
+    if G == 3 and (do_norm or gn is not None):
+        check(lib.gecco_lower_edm_f32(_ptr(feat), _ptr(x), _ptr(coef), _ptr(W), _ptr(bias), _ptr(gn[0]) if gn else None,
+                                      _ptr(gn[1]) if gn else None, _ptr(out), _ptr(raw), B, N, Cc, eps, _stream()),
+              "gecco_lower_edm_f32")
+    else:
+        assert gn is None, "the GroupNorm lower form is 3-wide (RayNetwork)"
+        check_geometry_dim(G)
+        check(lib.gecco_lower_edm_g_f32(_ptr(feat), _ptr(x), _ptr(coef), _ptr(W), _ptr(bias), _ptr(out), _ptr(raw), B, N, Cc, G,
+                                        int(do_norm), eps, _stream()), "gecco_lower_edm_g_f32")
     return (out, raw) if want_raw else out
 
 
@@ -804,24 +827,37 @@ class LinearLiftPlan:
     """EDMPrecond(LinearLift(SetTransformer)) = the unconditional Diffusion.forward, one C call."""
 
     def __init__(self, p: Mapping[str, Tensor], H: int, I: int = 64, pre: str = "", sigma_data: float = 1.0,
-                 precision: str | None = None, act: int | None = None, options: Mapping[str, int] | None = None):
+                 precision: str | None = None, act: int | None = None, options: Mapping[str, int] | None = None,
+                 geometry_dim: int = 3, do_norm: bool = True):
+        check_geometry_dim(geometry_dim)
         self.st = SetTransformerPlan(p, pre + "inner.", H, I, precision=precision, act=act, options=options)
         self.p = p
         self.lib = self.st.lib
-        self.table = GeccoLinearLift(self.st.table, _ptr(p[pre + "lift.weight"]), _ptr(p[pre + "lift.bias"]),
-                                     _ptr(p[pre + "lower.1.weight"]), _ptr(p[pre + "lower.1.bias"]), sigma_data)
+        low = pre + ("lower.1." if do_norm else "lower.")
+        base = GeccoLinearLift(self.st.table, _ptr(p[pre + "lift.weight"]), _ptr(p[pre + "lift.bias"]),
+                               _ptr(p[low + "weight"]), _ptr(p[low + "bias"]), sigma_data)
+        # G = 3 with the LayerNorm: the original table and entry point (the same kernels); any other form: GeccoLinearLiftG
+        self.generic = not (geometry_dim == 3 and do_norm)
+        self.table = _lib.GeccoLinearLiftG(base, geometry_dim, int(do_norm)) if self.generic else base
+        self._tbl_type = type(self.table)
+        self._fwd = self.lib.gecco_linear_lift_g_fwd_f32 if self.generic else self.lib.gecco_linear_lift_fwd_f32
+        self._ws_bytes = self.lib.gecco_linear_lift_g_workspace_bytes if self.generic else self.lib.gecco_linear_lift_workspace_bytes
         self._ws: dict[tuple[int, int], Tensor] = {}
         self.images = self.st.images   # workspace key -> the token its weight images were built under (frozen_weights)
 
+    @staticmethod
+    def _inner(tbl):
+        return tbl.base.inner if isinstance(tbl, _lib.GeccoLinearLiftG) else tbl.inner
+
     def set_option(self, name: str, value: int) -> None:
         """Pin a path switch for THIS plan (0 / 1; negative: follow the process-wide default again)."""
-        _pin_option(self.table.inner, name, value)
+        _pin_option(self._inner(self.table), name, value)
         self.st.set_option(name, value)
 
     def workspace(self, B: int, N: int, idx: int = 0) -> Tensor:
         key = (B, N, idx)
         if key not in self._ws:
-            self._ws[key] = _ws(self.lib.gecco_linear_lift_workspace_bytes(C.byref(self.table), B, N), self.st.device)
+            self._ws[key] = _ws(self._ws_bytes(C.byref(self.table), B, N), self.st.device)
         return self._ws[key]
 
     def forward(self, x: Tensor, sigma: Tensor, return_raw: bool = False, cache: Sequence[Tensor] | None = None,
@@ -835,16 +871,17 @@ class LinearLiftPlan:
         def call(lo, hi, idx):
             ws = self.workspace(hi - lo, N, idx)
             key, tok = (hi - lo, N, idx), self.images.token(cache is not None)
-            tbl = GeccoLinearLift.from_buffer_copy(self.table)    # this call's own copy: nothing another call / thread can alias
-            ready = tbl.inner.images_ready = self.images.ready(key, tok)
+            tbl = self._tbl_type.from_buffer_copy(self.table)    # this call's own copy: nothing another call / thread can alias
+            inner = self._inner(tbl)
+            ready = inner.images_ready = self.images.ready(key, tok)
             if parts > 1:
-                _pin_option(tbl.inner, "mlpwshare", 1)
+                _pin_option(inner, "mlpwshare", 1)
             cut = (lambda ts: None if ts is None else [None if t is None else t[lo:hi] for t in ts])
             try:
-                check(self.lib.gecco_linear_lift_fwd_f32(
+                check(self._fwd(
                     C.byref(tbl), _ptr(x[lo:hi]), _ptr(sigma[lo:hi]), _ptr(den[lo:hi]), _ptr(None if raw is None else raw[lo:hi]),
                     self.st._ptr_array(cut(cache), L), self.st._ptr_array(cut(h_out), L), hi - lo, N, C.c_void_p(ws.data_ptr()),
-                    ws.numel(), _stream()), "gecco_linear_lift_fwd_f32")
+                    ws.numel(), _stream()), "gecco_linear_lift_g_fwd_f32" if self.generic else "gecco_linear_lift_fwd_f32")
             except BaseException:
                 self.images.failed(key)
                 raise

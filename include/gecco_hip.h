@@ -487,6 +487,29 @@ int gecco_linear_lift_fwd_f32(const GeccoLinearLift* m, const float* x, const fl
                               size_t ws_bytes, void* stream);
 size_t gecco_linear_lift_workspace_bytes(const GeccoLinearLift* m, int B, int N);
 
+/* ---- geometry width G and LinearLift(do_norm=False) (linear_lift.py:14-31), 1 <= G <= GECCO_MAX_GEOMETRY_DIM ---------------
+ * G = 3 with the LayerNorm stays on gecco_lift_f32 / gecco_lower_edm_f32 / GeccoLinearLift above. */
+#define GECCO_MAX_GEOMETRY_DIM 16
+/* out = (c_in * x) @ W^T + b: x (B, N, G), W (C, G); coef / bias / stats as gecco_lift_f32. */
+int gecco_lift_g_f32(const float* x, const float* coef, const float* W, const float* bias, float* out, float* stats,
+                     int B, int N, int C, int G, void* stream);
+/* F = Linear(C->G)(LayerNorm(feat)) (do_norm != 0) or Linear(C->G)(feat); D = c_skip*x + c_out*F.  W (G, C), bias (G) or NULL;
+ * x / out / raw (B, N, G).  C % 4 == 0, C <= 512. */
+int gecco_lower_edm_g_f32(const float* feat, const float* x, const float* coef, const float* W, const float* bias, float* out,
+                          float* raw, int B, int N, int C, int G, int do_norm, float eps, void* stream);
+
+typedef struct GeccoLinearLiftG {   /* LinearLift(geometry_dim = G, do_norm) under EDMPrecond */
+    GeccoLinearLift base;           /* lower_w (G, C): lower.1.weight (do_norm) or lower.weight; lift_w (C, G) */
+    int geometry_dim;
+    int do_norm;
+} GeccoLinearLiftG;
+
+/* gecco_linear_lift_fwd_f32 for a GeccoLinearLiftG: x / denoised / raw (B, N, G). */
+int gecco_linear_lift_g_fwd_f32(const GeccoLinearLiftG* m, const float* x, const float* sigma, float* denoised,
+                                float* raw, const float* const* h_in, float* const* h_out, int B, int N, void* ws,
+                                size_t ws_bytes, void* stream);
+size_t gecco_linear_lift_g_workspace_bytes(const GeccoLinearLiftG* m, int B, int N);
+
 /* ---- image-conditional path ------------------------------------------------------------------- */
 
 /* dst[i] = fp16(src[i]) (round to nearest even), n elements: the fp16 texel image of a channels-last pyramid level. */
@@ -686,6 +709,12 @@ int gecco_lift_bwd_f32(const float* dY, const float* xin, float* partial, int B,
 int gecco_lower_bwd_f32(const float* feat, const float* dF, const float* W, float* dfeat, float* partial, size_t rows,
                         int C, float eps, void* stream);
 int gecco_lower_bwd_blocks(size_t rows);
+/* the same for G components (1 .. 16) and either do_norm: lift partial (B, gecco_stats_row_tiles(N), G + 1, C) = {dW^T, db};
+ * lower dfeat (rows, C), partial (gecco_lower_g_bwd_blocks(rows), G*C + 16) = {dW (G, C), db (G), 16 - G zeros}. */
+int gecco_lift_g_bwd_f32(const float* dY, const float* xin, float* partial, int B, int N, int C, int G, void* stream);
+int gecco_lower_g_bwd_f32(const float* feat, const float* dF, const float* W, float* dfeat, float* partial, size_t rows,
+                          int C, int G, int do_norm, float eps, void* stream);
+int gecco_lower_g_bwd_blocks(size_t rows);
 
 /* ---- optimizer step -------------------------------------------------------------------
  * torch.optim.Adam(lr=1e-4) of Diffusion.configure_optimizers (diffusion.py:210-211) fused with the EMA shadow-weight
@@ -724,6 +753,9 @@ int gecco_ema_update_f32(const float* p, float* ema, size_t n, double decay, voi
  * fp64, known / noise (B, n_known, 3) fp32 (diffusion space). */
 int gecco_sampler_refresh_known_f64(double* x, const float* known, const float* noise, const double* sched, const int* step,
                                     int col, int m, int n_known, int B, void* stream);
+/* the same for rows of `width` components: x (B, m + n_known, width), known / noise (B, n_known, width). */
+int gecco_sampler_refresh_known_g_f64(double* x, const float* known, const float* noise, const double* sched, const int* step,
+                                      int col, int m, int n_known, int width, int B, void* stream);
 /* D[b, i, j] = |a[b, i] - b[b, j]| formed as sqrt(max(|a|^2 + |b|^2 - 2 a.b, 0)) (gecco-jax geometry.py:8-24); squared != 0:
  * no square root.  a (B, N, 3), b (B, M, 3), D (B, N, M). */
 int gecco_distance_matrix_f32(const float* a, const float* b, float* D, int B, int N, int M, int squared, void* stream);
