@@ -294,9 +294,16 @@ def _linear_dx(dy: Tensor, W: Tensor, residual: Tensor | None = None, prec: str 
 # dX chain running ahead on the main one.  Ordering: the side stream waits for the main stream's work issued so far (dy and x
 # exist), the caching allocator is told about the cross-stream uses (record_stream), and ONE engine callback per backward pass
 # makes the main stream wait for the side stream when the pass ends — after loss.backward() returns, every gradient is
-# ordered on the main stream as before.  Mid-pass consumers on the main stream (a gradient that is ACCUMULATED into an
-# existing .grad, the data-parallel reducer's bucket launch) synchronise explicitly.
-_SIDE = {"stream": None, "pending": False}
+# ordered on the main stream as before.
+# The rule: a gradient goes to the side stream only when nothing on the main stream reads it before the pass ends — autograd must
+# HAND OVER the tensor to the parameter, not add it to anything.  So every parameter the call forms a gradient for (the bias with the
+# weight) is decided at BACKWARD time: a plain leaf (not a view), no .grad yet, and no gradient formed for it on the side stream
+# earlier in this pass (`_SIDE["leaves"]`).  A second contribution in one pass — the same parameter used twice, as in a backward of
+# l(b1) + l(b2) — is summed by the engine on the main stream: the later call is formed on the main stream after it has waited for
+# the side stream (one wait, only in that case; a forward-time count of pending uses would need per-parameter bookkeeping in every
+# forward to buy the same thing).  Other mid-pass consumers on the main stream (the data-parallel reducer's bucket launch)
+# synchronise explicitly.
+_SIDE = {"stream": None, "pending": False, "leaves": {}}   # leaves: id -> parameter given a side-stream gradient in this pass
 
 
 def _side_enabled() -> bool:
@@ -313,14 +320,45 @@ def sync_side_stream() -> None:
         _SIDE["pending"] = False
 
 
+def _side_pass_end() -> None:
+    sync_side_stream()
+    _SIDE["leaves"].clear()
+
+
+def _side_free(t: Tensor) -> bool:
+    """t may receive a gradient formed on the side stream (the rule above)."""
+    return t.is_leaf and t._base is None and t.grad is None and id(t) not in _SIDE["leaves"]
+
+
+def _side_seen(leaves) -> bool:
+    """One of `leaves` already has a side-stream gradient from this pass: the engine will add the next one to it on the main stream."""
+    return any(id(t) in _SIDE["leaves"] for t in leaves)
+
+
+def _side_issued(leaves) -> None:
+    """Side-stream work was issued: the pass-end callback orders it (right away outside a backward pass); `leaves` got their gradients
+    there."""
+    _SIDE["pending"] = True
+    try:   # one callback per call (the first to run does the wait, the rest find nothing pending)
+        torch.autograd.Variable._execution_engine.queue_callback(_side_pass_end)
+    except RuntimeError:   # not inside a backward pass: order it right away
+        sync_side_stream()
+        return
+    for t in leaves:
+        if t.is_leaf:
+            _SIDE["leaves"][id(t)] = t
+
+
 def _linear_dw(dy: Tensor, x: Tensor, want_db: bool = False, pro=None, leaf: Tensor | None = None, prec: str | None = None,
-               side_ok: bool = False):
-    """leaf: the parameter this gradient is FOR, when the caller knows that nothing will read the result before the pass ends —
-    a leaf that is not a view (a view's gradient is scattered into its base by autograd, on the main stream, right away) and
-    has no .grad yet (autograd then keeps the tensor instead of adding it into an existing one).  Only then the side stream.
-    side_ok (round 6): the weight is a third of nn.MultiheadAttention's packed in_proj handed out by `InProjSplitFn`, whose backward joins
-    the thirds' gradients ON the side stream (`_inproj_side_ok` checked the packed parameter at forward time)."""
-    if not _side_enabled() or not (side_ok or (leaf is not None and leaf.is_leaf and leaf._base is None and leaf.grad is None)):
+               side_ok: bool = False, bias: Tensor | None = None):
+    """leaf: the parameter this gradient is FOR (bias: the one db is for, with want_db) — the side stream when both pass
+    `_side_free` now.  side_ok: the weight is a third of nn.MultiheadAttention's packed in_proj handed out by `InProjSplitFn`, whose
+    backward joins the thirds' gradients on the side stream (`_inproj_side_ok`, checked by the caller at backward time)."""
+    assert leaf is None or not want_db or bias is not None, "the side-stream decision needs the bias db is for"
+    leaves = () if leaf is None else (leaf, bias) if want_db else (leaf,)
+    if not _side_enabled() or not (side_ok or (leaves and all(_side_free(t) for t in leaves))):
+        if _side_seen(leaves):
+            sync_side_stream()
         return _linear_dw_main(dy, x, want_db, pro, prec)
     if _SIDE["stream"] is None:
         _SIDE["stream"] = torch.cuda.Stream()
@@ -332,12 +370,7 @@ def _linear_dw(dy: Tensor, x: Tensor, want_db: bool = False, pro=None, leaf: Ten
         t.record_stream(side)
     for t in (res if isinstance(res, tuple) else (res,)):
         t.record_stream(main)
-    _SIDE["pending"] = True
-    try:   # one callback per call (the first to run does the wait, the rest find nothing pending): no state to go stale if a
-        # backward pass is abandoned half way
-        torch.autograd.Variable._execution_engine.queue_callback(sync_side_stream)
-    except RuntimeError:   # not inside a backward pass: order it right away
-        sync_side_stream()
+    _side_issued(leaves)
     return res
 
 
@@ -483,7 +516,8 @@ class LinearFn(torch.autograd.Function):
         x = _f(x)
         ctx.save_for_backward(x, W)
         ctx.has_bias = b is not None
-        ctx.side_ok = bool(getattr(W, "_gecco_side_ok", False))
+        ctx.b = b
+        ctx.inproj = getattr(W, "_gecco_inproj", None)   # a third of a packed in_proj: (W, b) packed (`InProjSplitFn`)
         prec = ctx.prec = _lin_precision()
         res = None if residual is None else _f(residual)
         if x.dtype == torch.float16:   # an fp16 tensor of an `_io16_ok` layer (the unpool attention's output): fp16 A tiles, fp32 result
@@ -513,10 +547,11 @@ class LinearFn(torch.autograd.Function):
         # (an fp16 input's gradient leaves as an fp16 tensor: its consumer — the attention backward — reads it as an fp16 operand)
         dx = _linear_dx(dy, W, prec=prec, out_f16=x.dtype == torch.float16) if ctx.needs_input_grad[0] else None
         dW = db = None
+        side_ok = ctx.inproj is not None and _inproj_side_ok(*ctx.inproj)
         if ctx.has_bias and ctx.needs_input_grad[2] and ctx.needs_input_grad[1]:
-            dW, db = _linear_dw(dy, x, want_db=True, leaf=W, prec=prec, side_ok=ctx.side_ok)
+            dW, db = _linear_dw(dy, x, want_db=True, leaf=W, prec=prec, side_ok=side_ok, bias=ctx.b)
         elif ctx.needs_input_grad[1]:
-            dW = _linear_dw(dy, x, leaf=W, prec=prec, side_ok=ctx.side_ok)
+            dW = _linear_dw(dy, x, leaf=W, prec=prec, side_ok=side_ok)
         elif ctx.has_bias and ctx.needs_input_grad[2]:
             db = _linear_db(dy)
         n = len(ctx.needs_input_grad)        # 3 .. 5: called without / with a residual (and the statistics flag)
@@ -534,6 +569,7 @@ class LinearPairFn(torch.autograd.Function):
         x = _f(x)
         ctx.save_for_backward(x, W1, W2)
         ctx.bias = (b1 is not None, b2 is not None)
+        ctx.b = (b1, b2)
         prec = ctx.prec = _lin_precision()
         img = None
         if W1.shape[0] % 128 == 0 and W2.shape[0] % 128 == 0 and _image_ok(x.shape[1], W1.shape[1], W1.shape[0] + W2.shape[0], prec):
@@ -550,9 +586,9 @@ class LinearPairFn(torch.autograd.Function):
         prec = ctx.prec
         dx = _linear_dx(d2, W2, residual=_linear_dx(d1, W1, prec=prec), prec=prec) if need[0] else None
         out = [dx]
-        for d, has_b, iw, Wl in ((d1, ctx.bias[0], 1, W1), (d2, ctx.bias[1], 3, W2)):
+        for d, has_b, iw, Wl, bl in ((d1, ctx.bias[0], 1, W1, ctx.b[0]), (d2, ctx.bias[1], 3, W2, ctx.b[1])):
             if need[iw] and has_b and need[iw + 1]:
-                out += list(_linear_dw(d, x, want_db=True, leaf=Wl, prec=prec))
+                out += list(_linear_dw(d, x, want_db=True, leaf=Wl, prec=prec, bias=bl))
             else:
                 out += [_linear_dw(d, x, leaf=Wl, prec=prec) if need[iw] else None, _linear_db(d) if has_b and need[iw + 1] else None]
         return tuple(out)
@@ -671,7 +707,7 @@ class AdaGNPairFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         a, o, stats, t2 = _adagn_coeffs(x, t, sw, sb, bw, bb, G, eps, stats)
         prec = ctx.prec = _lin_precision()   # "bf16x3" or "fp16" (_pro_ok)
-        ctx.side2 = bool(getattr(W2, "_gecco_side_ok", False))
+        ctx.inproj2, ctx.b2 = getattr(W2, "_gecco_inproj", None), b2
         B, R, K = x.shape
         N1, N2 = W1.shape[0], W2.shape[0]
         if io16:   # (`_io16_ok`) K | V and q as fp16 tensors: the same A-stationary kernel, its fp16 row-major epilogue
@@ -728,10 +764,11 @@ class AdaGNPairFn(torch.autograd.Function):
         xw, prow = (y16, None) if (y16.numel() and dKV.dtype == torch.float16 and dq.dtype == torch.float16) else (x, (a, o))
         dW1 = _linear_dw(dKV, xw, pro=prow, leaf=W1, prec=prec) if need[9] else None
         dW2 = db2 = None
+        side2 = ctx.inproj2 is not None and _inproj_side_ok(*ctx.inproj2)
         if need[10] and ctx.has_b2 and need[11]:
-            dW2, db2 = _linear_dw(dq, xw, want_db=True, pro=prow, leaf=W2, prec=prec, side_ok=ctx.side2)
+            dW2, db2 = _linear_dw(dq, xw, want_db=True, pro=prow, leaf=W2, prec=prec, side_ok=side2, bias=ctx.b2)
         elif need[10]:
-            dW2 = _linear_dw(dq, xw, pro=prow, leaf=W2, prec=prec, side_ok=ctx.side2)
+            dW2 = _linear_dw(dq, xw, pro=prow, leaf=W2, prec=prec, side_ok=side2)
         elif ctx.has_b2 and need[11]:
             db2 = _linear_db(dq.float() if dq.dtype != torch.float32 else dq)
         dx, dsw, dsb, dbw, dbb, dt = _adagn_backward(x, stats, t2, sw, sb, dY, dskip, ctx.G, ctx.eps, True, gst=gst, bw=bw if need[1] else None)
@@ -776,6 +813,7 @@ class AdaGNMlpFn(torch.autograd.Function):
         ctx.save_for_backward(x, stats, t2, sw, sb, a, o, u, h, alpha if alpha is not None else x.new_empty(0), W0, W2, bw,
                               y16 if y16 is not None else x.new_empty(0))
         ctx.G, ctx.eps, ctx.kind, ctx.bias, ctx.t_shape = G, eps, kind, (b0 is not None, b2 is not None), tuple(t.shape)
+        ctx.b = (b0, b2)
         out = _linear_fwd_h16(h, W2, b2, x, want_stats) if h16 else _linear_fwd(h, W2, b2, x, want_stats, prec)
         if want_stats:
             ctx.mark_non_differentiable(out[1])
@@ -795,15 +833,15 @@ class AdaGNMlpFn(torch.autograd.Function):
                 and _du16_ok(prec, x.shape[1], W2.shape[0], W2.shape[1], x.shape[2]))
         du, dalpha = _act_linear_dx(dout, u, h, alpha, W2, ctx.kind, need[11], prec, du16=du16)
 
-        def wgrads(g, act_in, has_b, iw, ib, Wl, pro=None):
+        def wgrads(g, act_in, has_b, iw, ib, Wl, bl, pro=None):
             if has_b and need[ib] and need[iw]:
-                return _linear_dw(g, act_in, want_db=True, pro=pro, leaf=Wl, prec=prec)
+                return _linear_dw(g, act_in, want_db=True, pro=pro, leaf=Wl, prec=prec, bias=bl)
             return (_linear_dw(g, act_in, pro=pro, leaf=Wl, prec=prec) if need[iw] else None), (_linear_db(g) if has_b and need[ib] else None)
-        dW2, db2 = wgrads(dout, h, ctx.bias[1], 12, 13, W2)
+        dW2, db2 = wgrads(dout, h, ctx.bias[1], 12, 13, W2, ctx.b[1])
         if du.dtype == torch.float16 and y16.numel():   # both operands as fp16 images: the DMA form of the weight-gradient kernel
-            dW0, db0 = wgrads(du, y16, ctx.bias[0], 9, 10, W0)
+            dW0, db0 = wgrads(du, y16, ctx.bias[0], 9, 10, W0, ctx.b[0])
         else:
-            dW0, db0 = wgrads(du, x, ctx.bias[0], 9, 10, W0, pro=(a, o))
+            dW0, db0 = wgrads(du, x, ctx.bias[0], 9, 10, W0, ctx.b[0], pro=(a, o))
         dY, gst = _linear_dx_dot(du, W0, x, prec=prec)
         dx, dsw, dsb, dbw, dbb, dt = _adagn_backward(x, stats, t2, sw, sb, dY, dout, ctx.G, ctx.eps, True, gst=gst, bw=bw if need[1] else None)
         return dx, (dt.reshape(ctx.t_shape) if dt is not None else None), dsw, dsb, dbw, dbb, None, None, None, dW0, db0, dalpha, dW2, db2, None, None
@@ -1049,7 +1087,7 @@ class LinearActLinearFn(torch.autograd.Function):
             u = _linear_fwd(x, W0, b0, None, False, prec)
             h = _act_forward(u, alpha, kind)
         ctx.save_for_backward(x, u, h, alpha if alpha is not None else x.new_empty(0), W0, W2)
-        ctx.kind, ctx.bias = kind, (b0 is not None, b2 is not None)
+        ctx.kind, ctx.bias, ctx.b = kind, (b0 is not None, b2 is not None), (b0, b2)
         res = None if residual is None else _f(residual)
         out = _linear_fwd_h16(h, W2, b2, res, want_stats) if h16 else _linear_fwd(h, W2, b2, res, want_stats, prec)
         if want_stats:
@@ -1067,12 +1105,12 @@ class LinearActLinearFn(torch.autograd.Function):
         prec = ctx.prec
         du, dalpha = _act_linear_dx(dy, u, h, alpha, W2, ctx.kind, need[3], prec)
 
-        def wgrads(g, a, has_b, iw, ib, Wl):
+        def wgrads(g, a, has_b, iw, ib, Wl, bl):
             if has_b and need[ib] and need[iw]:
-                return _linear_dw(g, a, want_db=True, leaf=Wl, prec=prec)
+                return _linear_dw(g, a, want_db=True, leaf=Wl, prec=prec, bias=bl)
             return (_linear_dw(g, a, leaf=Wl, prec=prec) if need[iw] else None), (_linear_db(g) if has_b and need[ib] else None)
-        dW2, db2 = wgrads(dy, h, ctx.bias[1], 4, 5, W2)
-        dW0, db0 = wgrads(du, x, ctx.bias[0], 1, 2, W0)
+        dW2, db2 = wgrads(dy, h, ctx.bias[1], 4, 5, W2, ctx.b[1])
+        dW0, db0 = wgrads(du, x, ctx.bias[0], 1, 2, W0, ctx.b[0])
         dx = _linear_dx(du, W0, prec=prec) if need[0] else None
         return dx, dW0, db0, dalpha, dW2, db2, (dy if need[6] else None), None, None
 
@@ -1089,7 +1127,7 @@ class ActLinearFn(torch.autograd.Function):
         u = _f(u)
         h = _act_forward(u, alpha, kind)
         ctx.save_for_backward(u, h, alpha if alpha is not None else u.new_empty(0), W)
-        ctx.kind, ctx.has_bias = kind, b is not None
+        ctx.kind, ctx.has_bias, ctx.b = kind, b is not None, b
         prec = ctx.prec = _lin_precision()
         res = None if residual is None else _f(residual)
         out = _linear_fwd(h, W, b, res, want_stats, prec)
@@ -1108,7 +1146,7 @@ class ActLinearFn(torch.autograd.Function):
         du, dalpha = _act_linear_dx(dy, u, h, alpha, W, ctx.kind, ctx.needs_input_grad[1], prec)
         dW = db = None
         if ctx.has_bias and ctx.needs_input_grad[3] and ctx.needs_input_grad[2]:
-            dW, db = _linear_dw(dy, h, want_db=True, leaf=W, prec=prec)
+            dW, db = _linear_dw(dy, h, want_db=True, leaf=W, prec=prec, bias=ctx.b)
         elif ctx.needs_input_grad[2]:
             dW = _linear_dw(dy, h, leaf=W, prec=prec)
         elif ctx.has_bias and ctx.needs_input_grad[3]:
@@ -1658,7 +1696,7 @@ class CnxBlockFn(torch.autograd.Function):
             h = _act_forward(u, None, 4)
         out = _linear_fwd(h, w2f, b2f, x.view(1, rows, Cc), False, ctx.prec)
         ctx.save_for_backward(x, z, w_tap, ln_w, y, u, h, W1, W2, b2, lsv, w2f)
-        ctx.eps, ctx.ls_shape = eps, ls.shape
+        ctx.eps, ctx.ls_shape, ctx.b1 = eps, ls.shape, b1
         return out.view(B, H, W, Cc)
 
     @staticmethod
@@ -1675,7 +1713,7 @@ class CnxBlockFn(torch.autograd.Function):
         dW2, db2, dls = torch.empty_like(W2), torch.empty_like(b2), torch.empty_like(lsv)
         _lib.check(lib.gecco_convnext_fold_scale_bwd_f32(_ptr(dWp), _ptr(dbp), _ptr(W2), _ptr(b2), _ptr(lsv), _ptr(dW2), _ptr(db2),
                                                          _ptr(dls), Cc, W2.shape[1], _stream()), "gecco_convnext_fold_scale_bwd_f32")
-        dW1, db1 = _linear_dw(du, y.view(1, rows, Cc), want_db=True, leaf=W1, prec=prec)
+        dW1, db1 = _linear_dw(du, y.view(1, rows, Cc), want_db=True, leaf=W1, prec=prec, bias=ctx.b1)
         dy = _linear_dx(du, W1, prec=prec).view(B, H, W, Cc)
         dz, dg, dbl, dbias = _cnx_ln_bwd(z, dy, ln_w, ctx.eps, False)
         dx = None
@@ -1749,10 +1787,20 @@ def convnext_pyramid(ext, image: Tensor) -> list[Tensor]:
 
 
 def _inproj_side_ok(W: Tensor, b: Tensor) -> bool:
-    """The packed in_proj parameters are plain leaves without a gradient yet (`zero_grad(set_to_none=True)`): autograd will KEEP the joined
-    gradient instead of adding it into an existing one, so the thirds' weight gradients and their join may live on the side stream."""
+    """The packed in_proj parameters may receive their joined gradient on the side stream (`_side_free`, checked at BACKWARD time by
+    the thirds' weight gradients and by the join alike): autograd will KEEP the joined gradient instead of adding it to anything."""
     return (os.environ.get("GECCO_TRAIN_INPROJ_SIDE", "1") != "0" and _side_enabled()
-            and all(t.is_leaf and t._base is None and t.grad is None and t.requires_grad for t in (W, b)))
+            and all(_side_free(t) and t.requires_grad for t in (W, b)))
+
+
+def _join_thirds(a, b_, rows_a, rows_b):
+    """The packed gradient from its two thirds' (a missing one as zeros)."""
+    if a is None and b_ is None:
+        return None
+    ref = a if a is not None else b_
+    a = ref.new_zeros(rows_a, *ref.shape[1:]) if a is None else a
+    b_ = ref.new_zeros(rows_b, *ref.shape[1:]) if b_ is None else b_
+    return torch.cat([a, b_], 0)
 
 
 class InProjSplitFn(torch.autograd.Function):
@@ -1765,41 +1813,32 @@ class InProjSplitFn(torch.autograd.Function):
     def forward(ctx, W, b, Cc):
         ctx.Cc = Cc
         ctx.set_materialize_grads(False)
-        ctx.side_join = _inproj_side_ok(W, b)
+        ctx.packed = (W, b)
         return W[:Cc], b[:Cc], W[Cc:], b[Cc:]
 
     @staticmethod
     def backward(ctx, gWq, gbq, gWkv, gbkv):
         Cc = ctx.Cc
-
-        def join(a, b_, rows_a, rows_b):
-            if a is None and b_ is None:
-                return None
-            ref = a if a is not None else b_
-            a = ref.new_zeros(rows_a, *ref.shape[1:]) if a is None else a
-            b_ = ref.new_zeros(rows_b, *ref.shape[1:]) if b_ is None else b_
-            return torch.cat([a, b_], 0)
-        if ctx.side_join and _SIDE["stream"] is not None and _side_enabled():
-            # the thirds' gradients were formed on the weight-gradient side stream (`_linear_dw(side_ok=True)`): join them there, in its
-            # order; the packed parameter has no .grad yet, so autograd only keeps the result — nothing on the main stream reads it before
-            # the pass-end callback (or the data-parallel reducer's explicit sync) has ordered the side stream in front
-            side, main = _SIDE["stream"], torch.cuda.current_stream()
-            side.wait_stream(main)       # (a third that was formed on the main stream after all)
-            with torch.cuda.stream(side):
-                gW, gb = join(gWq, gWkv, Cc, 2 * Cc), join(gbq, gbkv, Cc, 2 * Cc)
-            for t in (gWq, gbq, gWkv, gbkv):
-                if t is not None:
-                    t.record_stream(side)
-            for t in (gW, gb):
-                if t is not None:
-                    t.record_stream(main)
-            _SIDE["pending"] = True
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(sync_side_stream)
-            except RuntimeError:
+        W, b = ctx.packed
+        if not (_inproj_side_ok(W, b) and _SIDE["stream"] is not None):
+            if _side_seen((W, b)):   # (a third formed on the side stream; the engine adds the result to the side-stream one of this pass)
                 sync_side_stream()
-            return gW, gb, None
-        return join(gWq, gWkv, Cc, 2 * Cc), join(gbq, gbkv, Cc, 2 * Cc), None
+            return _join_thirds(gWq, gWkv, Cc, 2 * Cc), _join_thirds(gbq, gbkv, Cc, 2 * Cc), None
+        # the thirds' gradients were formed on the weight-gradient side stream (`_linear_dw(side_ok=True)`): join them there, in its
+        # order; nothing on the main stream reads the result before the pass-end callback (or the data-parallel reducer's explicit
+        # sync) has ordered the side stream in front
+        side, main = _SIDE["stream"], torch.cuda.current_stream()
+        side.wait_stream(main)       # (a third that was formed on the main stream after all)
+        with torch.cuda.stream(side):
+            gW, gb = _join_thirds(gWq, gWkv, Cc, 2 * Cc), _join_thirds(gbq, gbkv, Cc, 2 * Cc)
+        for t in (gWq, gbq, gWkv, gbkv):
+            if t is not None:
+                t.record_stream(side)
+        for t in (gW, gb):
+            if t is not None:
+                t.record_stream(main)
+        _side_issued((W, b))
+        return gW, gb, None
 
 
 # ------------------------------------------------------------------------------------------- network composition
@@ -1854,8 +1893,8 @@ def broadcasting_layer(layer, x, t, h=None, stats=None, want_stats=False):
     R = x.shape[1]
     if os.environ.get("GECCO_TRAIN_INPROJ_SPLIT", "1") != "0":
         Wq, bq, Wkv, bkv = InProjSplitFn.apply(bc.unpool.in_proj_weight, bc.unpool.in_proj_bias, Cc)
-        if _inproj_side_ok(bc.unpool.in_proj_weight, bc.unpool.in_proj_bias):
-            Wq._gecco_side_ok = Wkv._gecco_side_ok = True    # (read by the Functions that differentiate with respect to them)
+        # (read by the Functions that differentiate with respect to the thirds: `_inproj_side_ok` at backward time)
+        Wq._gecco_inproj = Wkv._gecco_inproj = (bc.unpool.in_proj_weight, bc.unpool.in_proj_bias)
     else:   # plain slices: autograd's slice backward (A/B runs)
         W_, b_ = bc.unpool.in_proj_weight, bc.unpool.in_proj_bias
         Wq, bq, Wkv, bkv = W_[:Cc], b_[:Cc], W_[Cc:], b_[Cc:]
