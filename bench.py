@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the GECCO denoiser forward on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what its headline figure needs: it sets up, warms up, times the K steps, writes its outputs if
+`--dump-outputs` is given, and prints the result line.  `--full` adds everything else the benchmark measures (the extra objects
+listed below); the headline figure and the dumped outputs are the same either way, since both are taken before any of it runs.
 
 `--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (the forward: `denoised`; `--train`:
 `loss` and the updated `params`, flattened), at most 64 MB in all (a larger array as a fixed, seeded sample).  Inputs, weights and
@@ -33,7 +37,7 @@ C3 | C4` is the image-conditional step (frozen channels-last ConvNeXt conditione
 RayNetwork; C4 = BASELINE's data-parallel configuration: N = 4096, d = 512).  `--config C3 | C4 | C5` without `--train`
 times one evaluation of the other BASELINE shapes (C5: the cached upsampling evaluation of 16 384 new points).
 
-Extra objects on that line:
+Extra objects on that line with `--full` (`--no-roofline`, `--no-sampler`, `--no-cpu-baseline`, `--no-extras` leave one out):
   roofline     — the dominant kernel of the measured mode.  mixed (default): mlp.0 on the A-stationary h8 kernel
                  (gemm_h8_astat_kernel: AdaGN apply + fp16 main product + two fp8 cross terms + GaussianActivation, 20 % of device
                  time), bound "mfma" against 2500 / 1.5 TFLOP/s of 2MNK (1.5 matrix-pipe units per product with the fp6 cross terms; 2 with GECCO_H6=0), its HBM side beside it
@@ -44,10 +48,12 @@ Extra objects on that line:
                  executed matrix-pipe work / time / 2500 TFLOP/s and counter bytes / time / 8 TB/s.  fp16 (opt-in): the fused
                  point MLP (mlp_fused_f16_kernel), same method.  bf16x3 / fp32: the LDS-DMA GEMM at its four call-site shapes.
                  The rocprofv3 --kernel-trace --stats summary of the same model lives in profiles/.
-  train, configs, upsample — what else the tree does, measured by child processes of the default run (`--no-extras` skips
+  train, configs, upsample — what else the tree does, measured by child processes of the `--full` run (`--no-extras` skips
                  them): the C2 training step with its dominant kernel's own roofline fraction, the C3 / C4 / C5 forward shapes,
                  Diffusion.upsample per outer step (eager and captured).
   cpu_baseline — the oracle (plain PyTorch CPU restatement of the reference) on a bounded sample.
+  also         — the other arithmetic modes and the headline mode's eager loop (with the roofline), frozen_weights_*,
+                 sample_128_steps, set_metrics (with the extras), and with N > 1 the all-reduce sweep in `distributed`.
 """
 from __future__ import annotations
 
@@ -924,11 +930,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-sampler", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: roofline, the other arithmetic modes, frozen weights, the "
+                         "128-step sample, the CPU baseline, the all-reduce sweep of N > 1, and the extras (without it a run sets up, "
+                         "warms up, times the steps, dumps and prints the headline line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline block and the other arithmetic modes")
+    ap.add_argument("--no-sampler", action="store_true", help="--full without the 128-step sample (--config C5: without Diffusion.upsample)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra blocks of the default run (train / configs / upsample: child processes, ~6 s of timed work each)")
+                    help="--full without its extra blocks (train / configs / upsample: child processes, ~6 s of timed work each)")
     ap.add_argument("--eager", action="store_true", help="time eager Diffusion.forward calls instead of the hipGraph replay")
     ap.add_argument("--precision", default=os.environ.get("GECCO_PRECISION", "w2"), choices=["fp32", "bf16x3", "mixed", "w2", "fp16"],
                     help="arithmetic of the linears and attention products: w2 (default: the mixed mode with the point MLP of each layer as "
@@ -1030,7 +1040,9 @@ def main():
     assert torch.isfinite(out).all(), "non-finite denoiser output"
     if args.dump_outputs and rank == 0:   # now: the roofline block below evaluates other modes into the same buffer
         dump_outputs(args.dump_outputs, host_copy({"denoised": out}))
-    dist_rep = distributed_report(dev, local_points_per_sec=B * N * args.steps / local_dt) if world > 1 else None
+    # every rank's own rate always; the all-reduce bandwidth sweep (timed runs of its own) with --full
+    dist_rep = distributed_report(dev, local_points_per_sec=B * N * args.steps / local_dt,
+                                  **({} if args.full else {"sizes": ()})) if world > 1 else None
 
     ms = dt / args.steps * 1e3
     value = world * B * N * args.steps / dt
@@ -1062,7 +1074,7 @@ def main():
     rec["config"]["workload"] = rec["config"]["workload"].replace(
         "fp32 MFMA", {"fp16": "fp16 MFMA", "bf16x3": "split-bf16 MFMA", "fp32": "fp32 MFMA", "mixed": "mixed fp16 / fp8-cross-term / split-bf16 MFMA",
                      "w2": "mixed fp16 / fp6- and fp8-cross-term MFMA, one-launch point MLP"}[mode])
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         site_mode = "bf16x3" if mode in ("mixed", "w2") else mode
         sites = gemm_call_sites(ops, dev, site_mode) if mode not in ("mixed", "w2") else []   # mixed / w2: their own rounds (h8_round, w2_round)
         tot_f, tot_b, tot_ms, per = 0.0, 0.0, 0.0, {}
@@ -1232,7 +1244,7 @@ def main():
                 eager_step()
             torch.cuda.synchronize()
             rec["eager_ms_per_step"] = (time.perf_counter() - t0) / 10 * 1e3
-    if rank == 0 and world == 1 and not args.eager:
+    if rank == 0 and world == 1 and args.full and not args.eager:
         # beside the headline (whose every replay rebuilds the weight images, as a forward between two weight updates must): the same
         # graph captured inside hip_ops.frozen_weights() — images built once by the warm-up call, as every sampler call does
         try:   # (an extra: whatever happens here must not cost the headline line)
@@ -1246,7 +1258,7 @@ def main():
         except Exception as e:
             rec["frozen_weights_ms_per_step"] = None
             rec["frozen_weights_error"] = repr(e)[:300]
-    if rank == 0 and world == 1 and not args.no_sampler:
+    if rank == 0 and world == 1 and args.full and not args.no_sampler:
         # Metric 2 (BASELINE.json): 128-step sample_stochastic wall-clock = 255 evaluations + fp64 sampler kernels,
         # one hipGraph per step replayed 127 times
         model.sample_stochastic((B, N, 3), None, num_steps=4)  # warm-up (graph capture path)
@@ -1258,7 +1270,7 @@ def main():
         assert torch.isfinite(smp).all()
         rec["sample_128_steps"] = {"seconds": ts, "evaluations": 255, "points_per_sec": B * N / ts,
                                    "ms_per_evaluation": ts / 255 * 1e3, "hipgraph": True}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline(p_cpu, x_cpu, sigma_cpu)
     if rank == 0 and "roofline" in rec:
         # whole evaluation against both roofs: executed matrix-pipe work / time / 2500 TFLOP/s, and HBM bytes from the counters
@@ -1273,7 +1285,7 @@ def main():
             "counter_bytes_per_evaluation": cb, "counter_source": tjw.get("source"),
             "hbm_gbs": cb / (ms * 1e-3) / 1e9 if cb else None, "hbm_frac": cb / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS if cb else None,
             "algorithmic_bytes_fp32_stream": 6.04e9}
-    if rank == 0 and world == 1 and not args.no_extras and not args.eager:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.eager:
         # what else the tree does, in front of the driver (compact; each a child process with ~10 timed steps).  The headline is
         # complete at this point: it goes to stderr now (a harness that loses patience with the extras still has it), this
         # process gives its device memory back before the children start, and the extras share ONE time budget (a slow or
