@@ -1590,7 +1590,8 @@ def _cnx_ln_bwd(z: Tensor, dy: Tensor, ln_w: Tensor, eps: float, patch2: bool):
 
 
 class CnxStemFn(torch.autograd.Function):
-    """LayerNorm2d(Conv2d(3, C, k4, s4)(image)) -> (B, H/4, W/4, C)   (torchvision ConvNeXt features[0])."""
+    """LayerNorm2d(Conv2d(3, C, k4, s4)(image)) -> (B, H/4, W/4, C)   (torchvision ConvNeXt features[0]; H/4, W/4 floor, the
+    pixels beyond the 4 (H/4) x 4 (W/4) corner are in no patch and get a zero gradient)."""
 
     @staticmethod
     def forward(ctx, img, w, b, ln_w, ln_b, eps):
@@ -1615,6 +1616,11 @@ class CnxStemFn(torch.autograd.Function):
             # the 4 x 4 patches do not overlap: d patch = dz W (a linear's dX product), then every value back to its pixel
             dp = _linear_dx(dz.view(1, B * h * w_, Cc), _f(w.reshape(Cc, 48)))
             dimg = dp.view(B, h, w_, 3, 4, 4).permute(0, 3, 1, 4, 2, 5).reshape(B, 3, 4 * h, 4 * w_)
+            H, W = img.shape[2], img.shape[3]
+            if (H, W) != (4 * h, 4 * w_):
+                full = img.new_zeros(B, 3, H, W)
+                full[:, :, :4 * h, :4 * w_] = dimg
+                dimg = full
         patches = _new(B, h * w_, 48, like=z)
         _lib.check(_lib.load().gecco_convnext_im2col4_f32(_ptr(img), _ptr(patches), B, img.shape[2], img.shape[3], _stream()),
                    "gecco_convnext_im2col4_f32")

@@ -2125,7 +2125,7 @@ int gecco_convnext_stem_f32(const float* x, const float* w, const float* bias, c
                             int B, int H, int W, int C, float eps, void* stream) {
     if (!x || !w || !bias || !ln_w || !ln_b || !out) return fail(-1, "convnext_stem: null argument");
     int rc = cnx_stem_launch(x, w, bias, ln_w, ln_b, out, nullptr, B, H, W, C, eps, (hipStream_t)stream);
-    if (rc == -9) return fail(-2, "convnext_stem: needs C == 96 and H, W multiples of 4");
+    if (rc == -9) return fail(-2, "convnext_stem: needs C == 96 and H, W >= 4");
     TRY(rc, "convnext_stem");
     return 0;
 }
@@ -2141,7 +2141,7 @@ int gecco_convnext_ln_patch2_f32(const float* x, const float* ln_w, const float*
                                  float eps, void* stream) {
     if (!x || !ln_w || !ln_b || !out) return fail(-1, "convnext_ln_patch2: null argument");
     int rc = cnx_ln_patch2_launch(x, ln_w, ln_b, out, B, H, W, C, eps, (hipStream_t)stream);
-    if (rc == -9) return fail(-2, "convnext_ln_patch2: C must be 96, 192 or 384 and H, W even");
+    if (rc == -9) return fail(-2, "convnext_ln_patch2: C must be 96, 192 or 384 and H, W >= 2");
     TRY(rc, "convnext_ln_patch2");
     return 0;
 }
@@ -2156,7 +2156,7 @@ int gecco_convnext_stem_train_f32(const float* x, const float* w, const float* b
                                   float* z, int B, int H, int W, int C, float eps, void* stream) {
     if (!x || !w || !bias || !ln_w || !ln_b || !out || !z) return fail(-1, "convnext_stem_train: null argument");
     int rc = cnx_stem_launch(x, w, bias, ln_w, ln_b, out, z, B, H, W, C, eps, (hipStream_t)stream);
-    if (rc == -9) return fail(-2, "convnext_stem_train: needs C == 96 and H, W multiples of 4");
+    if (rc == -9) return fail(-2, "convnext_stem_train: needs C == 96 and H, W >= 4");
     TRY(rc, "convnext_stem_train");
     return 0;
 }
@@ -2193,7 +2193,7 @@ int gecco_convnext_ln_bwd_f32(const float* z, const float* dy, const float* ln_w
                               float eps, int patch2, void* stream) {
     if (!z || !dy || !ln_w || !dz || !parts) return fail(-1, "convnext_ln_bwd: null argument");
     int rc = cnx_ln_bwd_launch(z, dy, ln_w, dz, parts, B, H, W, C, eps, patch2, (hipStream_t)stream);
-    if (rc == -9) return fail(-2, "convnext_ln_bwd: C must be 96, 192 or 384 (and H, W even for the patch layout)");
+    if (rc == -9) return fail(-2, "convnext_ln_bwd: C must be 96, 192, 384 or 768 (and H, W >= 2 for the patch layout)");
     TRY(rc, "convnext_ln_bwd");
     return 0;
 }
@@ -2201,7 +2201,7 @@ int gecco_convnext_dwconv_dw_blocks(int B, int H, int W, int C) { return cnx_dwc
 int gecco_convnext_dwconv_dw_f32(const float* x, const float* dz, float* parts, int B, int H, int W, int C, void* stream) {
     if (!x || !dz || !parts) return fail(-1, "convnext_dwconv_dw: null argument");
     int rc = cnx_dwconv_dw_launch(x, dz, parts, B, H, W, C, (hipStream_t)stream);
-    if (rc == -9) return fail(-2, "convnext_dwconv_dw: C must be 96, 192 or 384");
+    if (rc == -9) return fail(-2, "convnext_dwconv_dw: C must be 96, 192, 384 or 768");
     TRY(rc, "convnext_dwconv_dw");
     return 0;
 }
@@ -2222,7 +2222,7 @@ int gecco_gelu_bwd_f32(const float* u, const float* dy, float* du, size_t n, voi
 int gecco_convnext_im2col4_f32(const float* x, float* out, int B, int H, int W, void* stream) {
     if (!x || !out) return fail(-1, "convnext_im2col4: null argument");
     int rc = cnx_im2col4_launch(x, out, B, H, W, (hipStream_t)stream);
-    if (rc == -9) return fail(-2, "convnext_im2col4: H, W must be multiples of 4");
+    if (rc == -9) return fail(-2, "convnext_im2col4: H, W must be >= 4");
     TRY(rc, "convnext_im2col4");
     return 0;
 }

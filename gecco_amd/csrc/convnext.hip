@@ -21,6 +21,7 @@ __device__ __forceinline__ float group_sum(float v, int width) {   // sum over `
 }
 
 // ---- stem: out[b, h, w, :] = LN(W x_patch + bias), x NCHW (B, 3, H, W), patch 4 x 4 stride 4, weight (C, 3, 4, 4).
+// Ho = H / 4, Wo = W / 4 floor like Conv2d: the last H % 4 rows and W % 4 columns of the image are never read.
 // 8 lanes per output texel, lane q computes channels q, q + 8, ...; the 48 patch values sit in LDS.
 template <int C>
 __global__ __launch_bounds__(256) void stem_conv_ln_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -244,7 +245,8 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
 }
 
 // ---- downsample front half: LayerNorm over channels of every input texel, written where the 2 x 2 stride-2 conv's
-// GEMM reads it: out[b, h/2, w/2, (dy, dx, c)] (K = 4 C contiguous per output texel).
+// GEMM reads it: out[b, h/2, w/2, (dy, dx, c)] (K = 4 C contiguous per output texel).  An odd H or W floors like the
+// strided Conv2d: the slots walk the cropped (2 (H/2), 2 (W/2)) map, the input's last row / column is never read.
 template <int C>
 __global__ __launch_bounds__(256) void ln_patch2_kernel(const float* __restrict__ x, const float* __restrict__ ln_w,
                                                         const float* __restrict__ ln_b, float* __restrict__ out, int B, int H,
@@ -252,12 +254,14 @@ __global__ __launch_bounds__(256) void ln_patch2_kernel(const float* __restrict_
     constexpr int TPP = C / 4, PIX = 256 / TPP;
     __shared__ float red[2][256];
     const int pl = threadIdx.x / TPP, t = threadIdx.x % TPP;
-    const size_t npix = (size_t)B * H * W;
+    const int He = H & ~1, We = W & ~1;
+    const size_t npix = (size_t)B * He * We;
     const size_t p = (size_t)blockIdx.x * PIX + pl;
     const bool live = pl < PIX && p < npix;
     const int c = 4 * t;
+    const int wx = (int)(p % We), hy = (int)((p / We) % He), b = (int)(p / ((size_t)We * He));
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (live) v = *reinterpret_cast<const f32x4*>(x + p * C + c);
+    if (live) v = *reinterpret_cast<const f32x4*>(x + (((size_t)b * H + hy) * W + wx) * C + c);
     red[0][threadIdx.x] = v[0] + v[1] + v[2] + v[3];
     __syncthreads();
     float s1 = 0.f;
@@ -272,7 +276,6 @@ __global__ __launch_bounds__(256) void ln_patch2_kernel(const float* __restrict_
         for (int i = 0; i < TPP; ++i) s2 += red[1][pl * TPP + i];
     const float rstd = rsqrtf(s2 / C + eps);
     if (live) {
-        const int wx = (int)(p % W), hy = (int)((p / W) % H), b = (int)(p / ((size_t)W * H));
         const f32x4 g4 = *reinterpret_cast<const f32x4*>(ln_w + c), b4 = *reinterpret_cast<const f32x4*>(ln_b + c);
         const size_t op = ((size_t)b * (H / 2) + hy / 2) * (W / 2) + wx / 2;
         *reinterpret_cast<f32x4*>(out + op * 4 * C + ((hy & 1) * 2 + (wx & 1)) * C + c) = d * rstd * g4 + b4;
@@ -323,7 +326,7 @@ __global__ __launch_bounds__(256) void fold_scale_bwd_kernel(const float* __rest
 
 int cnx_stem_launch(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out, float* zout,
                     int B, int H, int W, int C, float eps, hipStream_t st) {
-    if (C != 96 || (H & 3) || (W & 3)) return -9;
+    if (C != 96 || H < 4 || W < 4) return -9;   // any H, W >= 4: the last H % 4 rows, W % 4 columns are dropped
     const size_t npix = (size_t)B * (H / 4) * (W / 4);
     hipLaunchKernelGGL((stem_conv_ln_kernel<96>), dim3((unsigned)((npix + 31) / 32)), dim3(256), 0, st, x, w, bias, ln_w, ln_b, out, zout, B,
                        H, W, eps);
@@ -365,9 +368,9 @@ int cnx_dwconv_ln_launch(const float* x, const float* w, const float* bias, cons
 }
 int cnx_ln_patch2_launch(const float* x, const float* ln_w, const float* ln_b, float* out, int B, int H, int W, int C, float eps,
                          hipStream_t st) {
-    if ((H & 1) || (W & 1)) return -9;
+    if (H < 2 || W < 2) return -9;   // an odd H or W drops the last row or column
     const int pix = 256 / (C / 4);
-    const dim3 grid((unsigned)(((size_t)B * H * W + pix - 1) / pix));
+    const dim3 grid((unsigned)(((size_t)B * (H & ~1) * (W & ~1) + pix - 1) / pix));
     CNX_DISPATCH(ln_patch2_kernel, C, grid, x, ln_w, ln_b, out, B, H, W, eps);
     return (int)hipGetLastError();
 }

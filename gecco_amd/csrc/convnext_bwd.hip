@@ -24,7 +24,8 @@ __device__ __forceinline__ float lanes_sum(float v, int width) {   // over `widt
 //   xh = (z - mean) rstd,  gy = dy g,  dz = rstd (gy - mean_c(gy) - xh mean_c(gy xh)),  dg += dy xh,  db += dy,  dzsum += dz
 // (dzsum is the bias gradient of the convolution that produced z).  L = C / 12 lanes share a texel (8 / 16 / 32 / 64: a power of
 // two, sums by lane shuffles, no LDS in the loop; at C = 768 a texel is a whole wave); lane q owns the 16-byte chunks q, q + L, q + 2L.  patch2: dy is laid out
-// as the 2 x 2 patch matrix of the downsampling convolution, (B, H/2, W/2, (dy, dx, c)) — the transpose of ln_patch2_kernel.
+// as the 2 x 2 patch matrix of the downsampling convolution, (B, H/2, W/2, (dy, dx, c)) — the transpose of ln_patch2_kernel; the
+// last row / column of an odd map is in no patch (the strided convolution floors): its dy is 0, never read, and its dz exactly 0.
 template <int C>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ z, const float* __restrict__ dy,
                                                      const float* __restrict__ ln_w, float* __restrict__ dz,
@@ -43,18 +44,20 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ z
     for (int it = 0; it < iters; ++it) {
         const size_t p = ((size_t)blockIdx.x * iters + it) * PIX + pl;
         const bool live = p < npix;
+        bool has_dy = live;
         f32x4 zv[3], dv[3];
         size_t dyo = p * C;
         if (patch2 && live) {
             const int wx = (int)(p % W), hy = (int)((p / W) % H);
             const size_t b = p / ((size_t)W * H);
+            has_dy = hy < (H & ~1) && wx < (W & ~1);
             dyo = (((b * (H / 2) + hy / 2) * (W / 2) + wx / 2) * 4 + ((hy & 1) * 2 + (wx & 1))) * C;
         }
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int c = 4 * (q + L * j);
             zv[j] = live ? *reinterpret_cast<const f32x4*>(z + p * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-            dv[j] = live ? *reinterpret_cast<const f32x4*>(dy + dyo + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+            dv[j] = has_dy ? *reinterpret_cast<const f32x4*>(dy + dyo + c) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
         float s1 = 0.f;
 #pragma unroll
@@ -189,16 +192,19 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* __restrict__
 }
 
 // ---- the stem's patch matrix: out[(b, ho, wo), (ci, dy, dx)] = x[b, ci, 4 ho + dy, 4 wo + dx] — the k order of
-// conv.weight.reshape(C, 48), so the stem's weight gradient is dz^T @ out.
+// conv.weight.reshape(C, 48), so the stem's weight gradient is dz^T @ out.  Ho = H / 4, Wo = W / 4 floor like the stem; a row of a
+// patch is one 16-byte load when W % 4 == 0, four scalar loads otherwise (its address is then not 16-byte aligned).
 __global__ __launch_bounds__(256) void im2col4_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int H, int W) {
     const int Ho = H / 4, Wo = W / 4;
+    const bool vec = (W & 3) == 0;
     const size_t total = (size_t)B * Ho * Wo * 12;   // one 16-byte piece (ci, dy, dx = 0..3) per index
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int piece = (int)(i % 12), ci = piece >> 2, dy = piece & 3;
         const size_t p = i / 12;
         const int wo = (int)(p % Wo), ho = (int)((p / Wo) % Ho);
         const size_t b = p / ((size_t)Wo * Ho);
-        reinterpret_cast<f32x4*>(out)[i] = *reinterpret_cast<const f32x4*>(x + ((b * 3 + ci) * H + 4 * ho + dy) * W + 4 * wo);
+        const float* src = x + ((b * 3 + ci) * H + 4 * ho + dy) * W + 4 * wo;
+        reinterpret_cast<f32x4*>(out)[i] = vec ? *reinterpret_cast<const f32x4*>(src) : f32x4{src[0], src[1], src[2], src[3]};
     }
 }
 
@@ -228,7 +234,7 @@ int cnx_ln_bwd_blocks(int B, int H, int W, int C) {
 }
 int cnx_ln_bwd_launch(const float* z, const float* dy, const float* ln_w, float* dz, float* parts, int B, int H, int W, int C,
                       float eps, int patch2, hipStream_t st) {
-    if ((C != 96 && C != 192 && C != 384 && C != 768) || (patch2 && ((H & 1) || (W & 1)))) return -9;
+    if ((C != 96 && C != 192 && C != 384 && C != 768) || (patch2 && (H < 2 || W < 2))) return -9;
     const size_t npix = (size_t)B * H * W;
     int iters;
     const int grid = ln_bwd_plan(npix, C, &iters);
@@ -273,7 +279,7 @@ int gelu_bwd_launch(const float* u, const float* dy, float* du, size_t n, hipStr
     return (int)hipGetLastError();
 }
 int cnx_im2col4_launch(const float* x, float* out, int B, int H, int W, hipStream_t st) {
-    if ((H & 3) || (W & 3)) return -9;
+    if (H < 4 || W < 4) return -9;
     const size_t total = (size_t)B * (H / 4) * (W / 4) * 12;
     const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 8192);
     hipLaunchKernelGGL(im2col4_kernel, dim3(grid ? grid : 1), dim3(256), 0, st, x, out, B, H, W);

@@ -93,11 +93,26 @@ class ConvNeXtExtractor(FeaturePyramidExtractor):
         """Channels-last forward on the HIP path.  With gradients enabled and trainable parameters it runs as autograd
         Functions (autograd.convnext_pyramid: the reference trains the conditioner with the denoiser); otherwise the fused
         inference sequence below."""
+        self.check_image_size(raw_ctx.image.shape[-2], raw_ctx.image.shape[-1])
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             from ..autograd import convnext_pyramid
             return FeaturePyramidContext(features=convnext_pyramid(self, raw_ctx.image), K=raw_ctx.K)
         with torch.no_grad():
             return self._forward_inference(raw_ctx)
+
+    def map_sizes(self, H: int, W: int) -> list[tuple[int, int]]:
+        """(h, w) of every level for an H x W image: the stem and each downsample floor like torchvision's strided Conv2d."""
+        sizes = [(H // 4, W // 4)]
+        for _ in range(len(self.stages) - 1):
+            sizes.append((sizes[-1][0] // 2, sizes[-1][1] // 2))
+        return sizes
+
+    def check_image_size(self, H: int, W: int) -> None:
+        """Any image size whose maps are all non-empty; a smaller one is refused before anything is launched."""
+        sizes = self.map_sizes(H, W)
+        if min(min(s) for s in sizes) < 1:
+            raise ValueError(f"ConvNeXtExtractor({len(self.stages)} stages): a {H} x {W} image gives maps {sizes}, one of them empty "
+                             f"(needs H, W >= {4 * 2 ** (len(self.stages) - 1)})")
 
     def _forward_inference(self, raw_ctx: Context3d) -> FeaturePyramidContext:
         lib = _lib.load()

@@ -782,15 +782,17 @@ int gecco_sinkhorn_f32(const float* C, float* f, float* g, float* rowcost, float
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
  * gecco_linear_ex_f32 on rows = B H W (act = 4: exact-erf GELU; the second one with the block input as residual and
  * layer_scale folded into its weights by gecco_convnext_fold_scale_f32); these are the rest of a block. */
-/* stem: out = LayerNorm_C(Conv2d(3 -> C, k4, s4)(x) + bias); x NCHW (B, 3, H, W), w (C, 3, 4, 4), out (B, H/4, W/4, C); C == 96 */
+/* stem: out = LayerNorm_C(Conv2d(3 -> C, k4, s4)(x) + bias); x NCHW (B, 3, H, W), w (C, 3, 4, 4), out (B, H/4, W/4, C); C == 96.
+ * H, W >= 4, any residue mod 4: H/4, W/4 floor like Conv2d (the last H % 4 rows and W % 4 columns are not read). */
 int gecco_convnext_stem_f32(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out,
                             int B, int H, int W, int C, float eps, void* stream);
 /* CNBlock front half: out = LayerNorm_C(dwconv7x7(x, padding 3) + bias); w TAP-MAJOR (49, C) = the module's weight
  * (C, 1, 7, 7) reshaped to (C, 49) and transposed (a re-layout of 19 .. 75 KB of parameters, like the 2 x 2 downsample
- * weight's); C in {96, 192, 384} */
+ * weight's); C in {96, 192, 384, 768}; any H, W */
 int gecco_convnext_dwconv_ln_f32(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out,
                                  int B, int H, int W, int C, float eps, void* stream);
-/* downsample front half: LayerNorm_C per texel, written as the 2 x 2 stride-2 conv's GEMM operand (B, H/2, W/2, (dy, dx, c)) */
+/* downsample front half: LayerNorm_C per texel, written as the 2 x 2 stride-2 conv's GEMM operand (B, H/2, W/2, (dy, dx, c)).
+ * H, W >= 2; an odd H or W floors like the strided Conv2d: the last row / column of the map is neither read nor written. */
 int gecco_convnext_ln_patch2_f32(const float* x, const float* ln_w, const float* ln_b, float* out, int B, int H, int W, int C,
                                  float eps, void* stream);
 /* Wo[n, k] = s[n] W[n, k], bo[n] = s[n] b[n] (CNBlock.layer_scale folded into its second linear) */
@@ -817,7 +819,8 @@ int gecco_convnext_fold_scale_bwd_f32(const float* dWp, const float* dbp, const 
 /* LayerNorm_C backward per texel from its input z (B, H, W, C) (statistics recomputed): dz, and per-block column partials
  * parts (gecco_convnext_ln_bwd_blocks(B, H, W, C), 3, C) = [d ln_w | d ln_b | column sums of dz] (the last is the bias
  * gradient of the convolution that produced z); reduce with gecco_reduce_batch_f32.  patch2 != 0: dy is laid out as the
- * downsample GEMM's operand (B, H/2, W/2, (dy, dx, c)) — the backward of gecco_convnext_ln_patch2_f32. */
+ * downsample GEMM's operand (B, H/2, W/2, (dy, dx, c)) — the backward of gecco_convnext_ln_patch2_f32; the last row / column
+ * of an odd map is in no patch: its dz is 0 and dy is not read there.  C in {96, 192, 384, 768}. */
 int gecco_convnext_ln_bwd_blocks(int B, int H, int W, int C);
 int gecco_convnext_ln_bwd_f32(const float* z, const float* dy, const float* ln_w, float* dz, float* parts, int B, int H, int W, int C,
                               float eps, int patch2, void* stream);
@@ -828,7 +831,8 @@ int gecco_convnext_dwconv_dw_f32(const float* x, const float* dz, float* parts, 
 /* y = GELU(u) (exact erf form, nn.GELU()) and du = dy GELU'(u) on n values (n % 4 == 0) */
 int gecco_gelu_f32(const float* u, float* y, size_t n, void* stream);
 int gecco_gelu_bwd_f32(const float* u, const float* dy, float* du, size_t n, void* stream);
-/* the stem's patch matrix (B H/4 W/4, 48), k = (ci, dy, dx) as in conv.weight.reshape(C, 48): its weight gradient is dz^T @ patches */
+/* the stem's patch matrix (B H/4 W/4, 48), k = (ci, dy, dx) as in conv.weight.reshape(C, 48): its weight gradient is dz^T @ patches.
+ * H, W >= 4, floored like the stem */
 int gecco_convnext_im2col4_f32(const float* x, float* out, int B, int H, int W, void* stream);
 
 #ifdef __cplusplus

@@ -41,3 +41,37 @@ def test_four_level_conditional_model_state_dict():
     assert net.img_feature_proj[0].num_channels == 1440 and net.img_feature_proj[0].num_groups == 16
     assert m.state_dict()["backbone.model.img_feature_proj.1.weight"].shape == (128, 1440)
     assert any(k.startswith("conditioner.stages.3.") for k in m.state_dict())
+
+
+@pytest.mark.parametrize("n,hw,maps", [(4, (137, 137), [(34, 34), (17, 17), (8, 8), (4, 4)]),
+                                       (4, (201, 143), [(50, 35), (25, 17), (12, 8), (6, 4)]),
+                                       (4, (33, 33), [(8, 8), (4, 4), (2, 2), (1, 1)]), (3, (130, 150), [(32, 37), (16, 18), (8, 9)])])
+def test_map_sizes_floor_like_torchvision(n, hw, maps):
+    """Any image size: the stem and every downsample floor like torchvision's strided Conv2d (the reference's ShapeNet images are
+    137 x 137, data/shapenet_cond.py)."""
+    import torch
+    import torch.nn.functional as F
+    from gecco_amd.models.feature_pyramid import ConvNeXtExtractor
+    m = ConvNeXtExtractor(n_stages=n, model="tiny", pretrained=False)
+    assert m.map_sizes(*hw) == maps
+    x = F.conv2d(torch.zeros(1, 3, *hw), torch.zeros(1, 3, 4, 4), stride=4)
+    sizes = [tuple(x.shape[2:])]
+    for _ in range(n - 1):
+        x = F.conv2d(x, torch.zeros(1, 1, 2, 2), stride=2)
+        sizes.append(tuple(x.shape[2:]))
+    assert sizes == maps
+    m.check_image_size(*hw)
+
+
+@pytest.mark.parametrize("n,hw", [(4, (20, 20)), (4, (64, 31)), (3, (15, 64)), (1, (3, 40))])
+def test_too_small_image_is_refused_before_any_launch(n, hw):
+    """An image whose pyramid would have an empty map is refused by the module, before it reaches a kernel (CPU tensors: the
+    refusal comes before the device is touched)."""
+    import torch
+    from gecco_amd.models.feature_pyramid import ConvNeXtExtractor
+    from gecco_amd.structs import Context3d
+    m = ConvNeXtExtractor(n_stages=n, model="tiny", pretrained=False)
+    ctx = Context3d(image=torch.rand(1, 3, *hw), K=torch.eye(3)[None])
+    for grad in (False, True):
+        with torch.set_grad_enabled(grad), pytest.raises(ValueError, match="empty"):
+            m(ctx)

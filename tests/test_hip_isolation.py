@@ -94,9 +94,10 @@ def test_conditional_forward_isolates_samples(B, N, d, hw, stages, L, precision)
             assert_same_bits(out[b0], ref[b0], f"sample {b0}, others {what}")
 
 
+@pytest.mark.parametrize("hw", [64, 137])
 @pytest.mark.parametrize("training", [False, True])
 @pytest.mark.parametrize("stages", [3, 4])
-def test_convnext_isolates_images(stages, training):
+def test_convnext_isolates_images(stages, training, hw):
     """The conditioner alone, inference and training forward (fp32 and split-bf16): image b0's features at every level are the same
     bits whatever the other images hold, NaN and +-1e30 included."""
     from gecco_amd import hip_ops
@@ -108,7 +109,7 @@ def test_convnext_isolates_images(stages, training):
     m = m.cuda().train(training)
     for q in m.parameters():
         q.requires_grad_(training)
-    B, hw = 3, 64
+    B = 3
     g = torch.Generator().manual_seed(stages)
     img = torch.rand(B, 3, hw, hw, generator=g)
     K = torch.eye(3).repeat(B, 1, 1).cuda()

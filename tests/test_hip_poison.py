@@ -27,8 +27,8 @@ COND_BARS = {"fp32": 1e-4, "bf16x3": 5e-4, "mixed": 5e-4, "w2": 1e-3, "fp16": 2e
 # (B, N, d, L): ragged tiles; the headline kernels (one-launch MLP at 6 groups, the inducer chain, unpool_outproj_h8); the two-pass
 # MLP (d = 512); the fp32 attention kernels (head dim 8); B N >= 32768 with B >= 4 (`hip_ops._fwd_parts`: two streams, uneven halves)
 UNCOND = [(3, 333, 128, 2), (2, 2048, 384, 2), (2, 1024, 512, 1), (2, 256, 64, 2), (5, 6600, 128, 1)]
-# (B, N, d, image side, ConvNeXt stages, L)
-COND = [(2, 333, 128, 64, 3, 2), (2, 2048, 384, 224, 3, 2), (3, 256, 384, 64, 4, 1)]
+# (B, N, d, image side, ConvNeXt stages, L); 137: the reference's ShapeNet images (maps 34, 17, 8: floored, odd downsample inputs)
+COND = [(2, 333, 128, 64, 3, 2), (2, 2048, 384, 224, 3, 2), (3, 256, 384, 64, 4, 1), (2, 333, 128, 137, 3, 2)]
 
 
 @pytest.fixture(scope="module", autouse=True)
