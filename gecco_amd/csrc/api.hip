@@ -2120,6 +2120,28 @@ int gecco_sinkhorn_f32(const float* C, float* f, float* g, float* rowcost, float
     return 0;
 }
 
+int gecco_emd_f32(const float* a, const float* b, int B, int N, int match_squared, int average_squared, float* out, int* assign,
+                  int* status, int max_rounds, void* stream) {
+    if (!a || !b || !out || !status) return fail(-1, "emd: null argument");
+    if (B <= 0) return fail(-2, "emd: empty batch");
+    if (N < 1 || N > GECCO_EMD_MAX_POINTS) return fail(-2, "emd: N = %d outside 1 .. %d (the LDS-resident limit)", N, GECCO_EMD_MAX_POINTS);
+    if (max_rounds < 0) return fail(-2, "emd: max_rounds %d < 0", max_rounds);
+    TRY(emd_auction_launch(a, b, out, assign, status, B, 1, 0, N, match_squared != 0, average_squared != 0,
+                           max_rounds ? max_rounds : GECCO_EMD_DEFAULT_ROUNDS, (hipStream_t)stream), "emd");
+    return 0;
+}
+int gecco_set_emd_f32(const float* a, const float* b, int S, int T, int N, int match_squared, int average_squared, float* out,
+                      int* status, int max_rounds, void* stream) {
+    if (!a || !b || !out || !status) return fail(-1, "set_emd: null argument");
+    if (S <= 0 || T <= 0) return fail(-2, "set_emd: empty set");
+    if ((long long)S * T > 0x7fffffffLL) return fail(-2, "set_emd: S * T = %lld pairs above 2^31 - 1", (long long)S * T);
+    if (N < 1 || N > GECCO_EMD_MAX_POINTS) return fail(-2, "set_emd: N = %d outside 1 .. %d (the LDS-resident limit)", N, GECCO_EMD_MAX_POINTS);
+    if (max_rounds < 0) return fail(-2, "set_emd: max_rounds %d < 0", max_rounds);
+    TRY(emd_auction_launch(a, b, out, nullptr, status, S * T, T, 1, N, match_squared != 0, average_squared != 0,
+                           max_rounds ? max_rounds : GECCO_EMD_DEFAULT_ROUNDS, (hipStream_t)stream), "set_emd");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- ConvNeXt conditioner (channels-last)
 int gecco_convnext_stem_f32(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out,
                             int B, int H, int W, int C, float eps, void* stream) {

@@ -449,6 +449,10 @@ int set_nearest_mean_launch(const float* A, const float* Bp, float* out, int S, 
 int set_metrics_launch(const float* ss, const float* sd, const float* dd, int n, float* out, int* flags, hipStream_t st);
 int sinkhorn_cost_launch(const float* C, const float* f, const float* g, float* rowcost, float* out, int B, int N, int M, float eps,
                          hipStream_t st);
+// emd.hip — exact EMD by an epsilon-scaling auction, one workgroup per pair: set_mode == 0 pairs (A[p], B[p]), else p = s * T + t pairs
+// (A[s], B[t]); out / status (pairs), assign (pairs, N) or null
+int emd_auction_launch(const float* A, const float* Bc, float* out, int* assign, int* status, int pairs, int T, int set_mode, int N,
+                       int match_sq, int avg_sq, int max_rounds, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

@@ -8,17 +8,9 @@
 // inner dimension is 3.
 #include "common.h"
 #include "kernels.h"
+#include "pair_dist.h"
 
 namespace {
-
-// d(a, b) exactly as the reference forms it: aa + bb - 2 ab, clamped at 0 (the clamp hides the cancellation noise of
-// that form for near-identical points), sqrt unless `squared`
-__device__ __forceinline__ float pair_dist(float ax, float ay, float az, float aa, float bx, float by, float bz, float bb,
-                                           bool squared) {
-    const float ab = ax * bx + ay * by + az * bz;
-    const float d2 = fmaxf(aa + bb - 2.f * ab, 0.f);
-    return squared ? d2 : sqrtf(d2);
-}
 
 // D[b, i, j] = dist(a[b, i], b[b, j]): a 256 x 256 tile per block, the thread owns COLUMN j (its b point in registers) and walks
 // the tile's a points in LDS (a broadcast read): every store instruction writes 256 consecutive floats of a row
@@ -31,10 +23,10 @@ __global__ __launch_bounds__(256) void dist_matrix_kernel(const float* __restric
         const float* a = A + ((size_t)b * N + min(i, N - 1)) * 3;
         const float ax = a[0], ay = a[1], az = a[2];
         sa[threadIdx.x * 4 + 0] = ax; sa[threadIdx.x * 4 + 1] = ay; sa[threadIdx.x * 4 + 2] = az;
-        sa[threadIdx.x * 4 + 3] = ax * ax + ay * ay + az * az;
+        sa[threadIdx.x * 4 + 3] = sq_norm(ax, ay, az);
     }
     const float* q = Bp + ((size_t)b * M + min(j, M - 1)) * 3;
-    const float bx = q[0], by = q[1], bz = q[2], bb = bx * bx + by * by + bz * bz;
+    const float bx = q[0], by = q[1], bz = q[2], bb = sq_norm(bx, by, bz);
     __syncthreads();
     if (j >= M) return;
     float* dcol = D + ((size_t)b * N + i0) * M + j;

@@ -4,7 +4,9 @@ API of gecco-jax/src/gecco_jax/metrics.py:92-156 and geometry.py:8-24, batched: 
 fp32 HIP tensors (or single (N, 3) clouds) and returns one value per sample; the JAX package vmaps single clouds.
 `scipy_emd` solves the assignment on the host with scipy, exactly as the reference does (its `_scipy_lsa` is a
 `jax.pure_callback` into `scipy.optimize.linear_sum_assignment`, metrics.py:108-121) on the distance matrix the device
-computed.  There is no CPU fallback for the device parts."""
+computed.  `emd` is its device twin: an exact epsilon-scaling auction, one workgroup per pair (csrc/emd.hip), whose assignment
+is optimal for the match cost quantised to 2^-24 of the pair's cost bound (include/gecco_hip.h); `pairwise_set_distance(
+kind="emd_exact")` runs it on every pair of two sets in one launch.  There is no CPU fallback for the device parts."""
 from __future__ import annotations
 
 import ctypes as C
@@ -70,6 +72,64 @@ def scipy_emd(p1: Tensor, p2: Tensor, match: str = "l1", average: str = "l1") ->
     return res[0] if single else res
 
 
+EMD_MAX_POINTS = 2048    # GECCO_EMD_MAX_POINTS: both clouds and the solver state of a pair stay in one CU's LDS
+EMD_Q = 24               # GECCO_EMD_Q: match costs are quantised to 2^-Q of the pair's cost bound c_max
+_SQUARED = {"l1": False, "l2": True}
+
+
+def _emd_args(a: Tensor, b: Tensor, match: str, average: str, max_rounds: int | None):
+    if match not in _SQUARED or average not in _SQUARED:
+        raise ValueError("match and average must be 'l1' or 'l2'")
+    N, M = a.shape[1], b.shape[1]
+    if N != M:
+        raise ValueError(f"the exact EMD needs clouds of equal size (got N = {N}, M = {M})")
+    if not 1 <= N <= EMD_MAX_POINTS:
+        raise ValueError(f"the exact EMD runs on 1 <= N <= {EMD_MAX_POINTS} points per cloud (got N = {N})")
+    if max_rounds is not None and int(max_rounds) < 1:
+        raise ValueError("max_rounds must be >= 1 (None: the library default)")
+    _ptr(a), _ptr(b)   # HIP tensors only: there is no CPU fallback
+    return int(_SQUARED[match]), int(_SQUARED[average]), 0 if max_rounds is None else int(max_rounds)
+
+
+def _emd_status(status: Tensor, max_rounds: int | None, what: str) -> None:
+    st = status.cpu()   # the one host read of the call
+    if bool((st == 1).any()):
+        raise ValueError(f"{what}: non-finite coordinates (or costs that overflow fp32) in pair(s) {_pairs(st == 1)}")
+    if bool((st == 2).any()):
+        cap = "the default cap" if max_rounds is None else f"max_rounds = {int(max_rounds)}"
+        raise _lib.GeccoHipError(f"{what}: the auction hit {cap} bidding rounds in pair(s) {_pairs(st == 2)}")
+
+
+def _pairs(mask: Tensor) -> list:
+    idx = mask.nonzero().tolist()
+    return [tuple(i) if len(i) > 1 else i[0] for i in idx]
+
+
+def emd(p1: Tensor, p2: Tensor, match: str = "l1", average: str = "l1", return_assignment: bool = False,
+        max_rounds: int | None = None):
+    """Exact earth mover's distance on the device: the twin of `scipy_emd` (gecco-jax metrics.py:114-142).  The assignment
+    minimises the `match` cost (quantised: within N * c_max * 2^-24 of scipy's optimum, include/gecco_hip.h), the value is
+    the mean `average` cost along it.  (B, N, 3) clouds give a (B,) tensor, (N, 3) clouds a scalar; with return_assignment
+    the int64 `cols` of scipy's (rows, cols) as well (rows = arange(N)).  A non-finite coordinate raises ValueError (as scipy
+    does on such a matrix); a pair that needs more than `max_rounds` bidding rounds raises GeccoHipError."""
+    a, b, single = _batched(p1, p2)
+    msq, asq, cap = _emd_args(a, b, match, average, max_rounds)
+    B, N, _ = a.shape
+    out = torch.empty(B, device=a.device, dtype=torch.float32)
+    status = torch.empty(B, device=a.device, dtype=torch.int32)
+    cols = torch.empty(B, N, device=a.device, dtype=torch.int32) if return_assignment else None
+    _lib.check(_lib.load().gecco_emd_f32(_ptr(a), _ptr(b), B, N, msq, asq, _ptr(out),
+                                         C.c_void_p(cols.data_ptr() if cols is not None else 0), C.c_void_p(status.data_ptr()),
+                                         cap, _stream()), "gecco_emd_f32")
+    _emd_status(status, max_rounds, "emd")
+    if single:
+        out = out[0]
+    if not return_assignment:
+        return out
+    cols = cols.long()
+    return out, (cols[0] if single else cols)
+
+
 def sinkhorn_emd(p1: Tensor, p2: Tensor, epsilon: float = 0.01, iterations: int = 200) -> Tensor:
     """Entropic OT cost <P, C> on the squared-Euclidean cost between uniform clouds (ott's PointCloud default cost), by
     `iterations` log-domain Sinkhorn sweeps on the device.  (ott stops on a marginal-error threshold; a fixed sweep count
@@ -91,7 +151,8 @@ def sinkhorn_emd(p1: Tensor, p2: Tensor, epsilon: float = 0.01, iterations: int 
 def pairwise_set_distance(a: Tensor, b: Tensor, kind: str = "chamfer", block_size: int = 16, epsilon: float = 0.1) -> Tensor:
     """(S, T) distances between EVERY cloud of a (S, N, 3) and every cloud of b (T, M, 3): gecco-jax benchmark.py:21-39
     (`batched_pairwise_distance`).  kind "chamfer" / "chamfer_squared": one HIP kernel per direction, no N x M matrix per pair;
-    "emd": the entropic `sinkhorn_emd(epsilon=0.1)` of BenchmarkCallback (:73-77) on blocks of `block_size` x `block_size` pairs."""
+    "emd": the entropic `sinkhorn_emd(epsilon=0.1)` of BenchmarkCallback (:73-77) on blocks of `block_size` x `block_size` pairs;
+    "emd_exact": the exact `emd` (l1 match and average, like `scipy_emd`'s defaults) of every pair in one launch."""
     if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3:
         raise ValueError("expected sets of clouds of shape (S, N, 3) and (T, M, 3)")
     a, b = a.float().contiguous(), b.float().contiguous()
@@ -102,8 +163,18 @@ def pairwise_set_distance(a: Tensor, b: Tensor, kind: str = "chamfer", block_siz
         _lib.check(_lib.load().gecco_set_chamfer_f32(_ptr(a), _ptr(b), _ptr(out), S, T, N, M, int(kind == "chamfer_squared"), _stream()),
                    "gecco_set_chamfer_f32")
         return out
+    if kind == "emd_exact":
+        msq, asq, cap = _emd_args(a, b, "l1", "l1", None)
+        if S * T > 2**31 - 1:
+            raise ValueError(f"S * T = {S * T} pairs above 2^31 - 1")
+        out = torch.empty(S, T, device=a.device, dtype=torch.float32)
+        status = torch.empty(S, T, device=a.device, dtype=torch.int32)
+        _lib.check(_lib.load().gecco_set_emd_f32(_ptr(a), _ptr(b), S, T, N, msq, asq, _ptr(out), C.c_void_p(status.data_ptr()), cap,
+                                                 _stream()), "gecco_set_emd_f32")
+        _emd_status(status, None, "pairwise_set_distance(kind='emd_exact')")
+        return out
     if kind != "emd":
-        raise ValueError("kind must be 'chamfer', 'chamfer_squared' or 'emd'")
+        raise ValueError("kind must be 'chamfer', 'chamfer_squared', 'emd' or 'emd_exact'")
     out = torch.empty(S, T, device=a.device, dtype=torch.float32)
     for s0 in range(0, S, block_size):
         for t0 in range(0, T, block_size):

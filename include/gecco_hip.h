@@ -777,6 +777,25 @@ int gecco_set_metrics_f32(const float* ss, const float* sd, const float* dd, int
  * P_ij = exp((f_i + g_j - C_ij) / epsilon) / (N M).  f (B, N), g (B, M), rowcost (B, N) are caller scratch / outputs. */
 int gecco_sinkhorn_f32(const float* C, float* f, float* g, float* rowcost, float* out, int B, int N, int M, float epsilon,
                        int iterations, void* stream);
+/* Exact earth mover's distance (gecco-jax metrics.py:114-142: `_scipy_lsa` = scipy's linear_sum_assignment on the distance
+ * matrix, then `scipy_emd`'s mean of the `average` distance along the assignment), solved on the device by an epsilon-scaling
+ * auction, one workgroup per pair, the whole state in LDS (csrc/emd.hip).  The match cost (squared != 0: l2) is quantised to
+ * k = rint(c * 2^GECCO_EMD_Q / c_max), c_max = 2^e with e the frexp exponent of the pair's largest match cost (at least 2^-100),
+ * and the integer problem is solved exactly: the assignment's match cost exceeds the optimum of the fp32 costs by at most
+ * N * c_max * 2^-GECCO_EMD_Q.  Value and assignment are deterministic (the same bits in any batch position).  Clouds have
+ * N == M points, 1 <= N <= GECCO_EMD_MAX_POINTS.  status[p]: 0 solved; 1 a non-finite coordinate (or costs that overflow
+ * fp32); 2 more than max_rounds bidding rounds (0: GECCO_EMD_DEFAULT_ROUNDS).  A pair with status != 0 gets NaN and an
+ * assignment of -1. */
+#define GECCO_EMD_MAX_POINTS 2048
+#define GECCO_EMD_Q 24
+#define GECCO_EMD_DEFAULT_ROUNDS (1 << 20)
+/* B pairs (a[p], b[p]), a and b (B, N, 3): out (B), assign (B, N) int32 (nullable: the column of each row), status (B) int32. */
+int gecco_emd_f32(const float* a, const float* b, int B, int N, int match_squared, int average_squared, float* out, int* assign,
+                  int* status, int max_rounds, void* stream);
+/* every pair of a (S, N, 3) set and a (T, N, 3) set in one launch (gecco-jax benchmark.py:21-39 `batched_pairwise_distance`
+ * with an exact EMD): out (S, T) row-major, status (S, T) int32; no expanded copies of the clouds. */
+int gecco_set_emd_f32(const float* a, const float* b, int S, int T, int N, int match_squared, int average_squared, float* out,
+                      int* status, int max_rounds, void* stream);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
