@@ -240,6 +240,9 @@ SIGNATURES = {
     "gecco_convnext_im2col4_f32": (i, [vp, vp, i, i, i, vp]),
     "gecco_adam_ema_step_f32": (i, [C.POINTER(GeccoAdamEma), vp]),
     "gecco_adam_ema_step_amp_f32": (i, [C.POINTER(GeccoAdamEma), vp, vp, vp, vp]),
+    "gecco_grad_norm_workspace_bytes": (sz, [sz]),
+    "gecco_grad_norm_f32": (i, [vp, sz, fl, vp, fl, vp, sz, vp, vp]),
+    "gecco_adam_ema_step_clip_f32": (i, [C.POINTER(GeccoAdamEma), i, fl, vp, vp, vp, vp, vp]),
     "gecco_ema_update_f32": (i, [vp, vp, sz, db, vp]),
 }
 

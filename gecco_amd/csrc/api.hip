@@ -2032,7 +2032,45 @@ int gecco_adam_ema_step_f32(const GeccoAdamEma* a, void* stream) {
     return gecco_adam_ema_step_amp_f32(a, nullptr, nullptr, nullptr, stream);
 }
 
+// the argument checks and the derived scalars of a step; algorithm GECCO_CLIP_NONE: the unclipped kernel
+static int adam_ema_step(const GeccoAdamEma* a, int algorithm, float clip_val, const float* stats, const float* amp_scale,
+                         const float* found_inf, int* skipped, void* stream);
+
 int gecco_adam_ema_step_amp_f32(const GeccoAdamEma* a, const float* amp_scale, const float* found_inf, int* skipped, void* stream) {
+    return adam_ema_step(a, GECCO_CLIP_NONE, 0.f, nullptr, amp_scale, found_inf, skipped, stream);
+}
+
+int gecco_adam_ema_step_clip_f32(const GeccoAdamEma* a, int algorithm, float clip_val, const float* stats, const float* amp_scale,
+                                 const float* found_inf, int* skipped, void* stream) {
+    if (algorithm != GECCO_CLIP_NORM && algorithm != GECCO_CLIP_VALUE)
+        return fail(-2, "adam_ema_clip: algorithm %d (1: norm, 2: value)", algorithm);
+    if (algorithm == GECCO_CLIP_NORM) {
+        if (!stats) return fail(-1, "adam_ema_clip: norm clipping reads stats[1] (gecco_grad_norm_f32 writes it)");
+        if ((uintptr_t)stats & 3) return fail(-2, "adam_ema_clip: stats must be 4-byte aligned");
+    } else if (!(clip_val >= 0.f) || !std::isfinite(clip_val)) {
+        return fail(-2, "adam_ema_clip: clip_val must be finite and >= 0");
+    }
+    return adam_ema_step(a, algorithm, clip_val, stats, amp_scale, found_inf, skipped, stream);
+}
+
+size_t gecco_grad_norm_workspace_bytes(size_t n) { return (size_t)grad_norm_blocks(n) * sizeof(double); }
+
+int gecco_grad_norm_f32(const float* g, size_t n, float grad_scale, const float* amp_scale, float max_norm, void* workspace,
+                        size_t workspace_bytes, float* stats, void* stream) {
+    if (!stats || (n && (!g || !workspace))) return fail(-1, "grad_norm: null argument");
+    if (n % 4) return fail(-2, "grad_norm: n must be a multiple of 4 (pad the flat buffer)");
+    if (((uintptr_t)g & 15) || ((uintptr_t)workspace & 7) || ((uintptr_t)stats & 3) || ((uintptr_t)amp_scale & 3))
+        return fail(-2, "grad_norm: g must be 16-byte, workspace 8-byte, stats / amp_scale 4-byte aligned");
+    if (n && workspace_bytes < gecco_grad_norm_workspace_bytes(n))
+        return fail(-2, "grad_norm: workspace of %zu bytes, %zu needed", workspace_bytes, gecco_grad_norm_workspace_bytes(n));
+    if (!std::isfinite(max_norm)) return fail(-2, "grad_norm: max_norm must be finite (<= 0: no clipping, coef = 1)");
+    if (!std::isfinite(grad_scale)) return fail(-2, "grad_norm: grad_scale must be finite");
+    TRY(grad_norm_launch(g, n, grad_scale, amp_scale, max_norm, (double*)workspace, stats, (hipStream_t)stream), "grad_norm");
+    return 0;
+}
+
+static int adam_ema_step(const GeccoAdamEma* a, int algorithm, float clip_val, const float* stats, const float* amp_scale,
+                         const float* found_inf, int* skipped, void* stream) {
     if (!a || !a->p || !a->g || !a->m || !a->v) return fail(-1, "adam_ema: null argument");
     if ((amp_scale || skipped) && !found_inf) return fail(-1, "adam_ema: amp_scale / skipped come with found_inf (the GradScaler protocol)");
     if (a->do_ema && !a->ema) return fail(-1, "adam_ema: do_ema needs the ema buffer");
@@ -2052,7 +2090,11 @@ int gecco_adam_ema_step_amp_f32(const GeccoAdamEma* a, const float* amp_scale, c
     k.grad_scale = a->grad_scale; k.ema_decay = (float)a->ema_decay; k.ema_w = (float)(1.0 - a->ema_decay); k.do_ema = a->do_ema;
     k.amp_scale = amp_scale; k.found_inf = found_inf; k.skipped = skipped;
     k.lr = a->lr; k.beta1 = a->beta1; k.beta2d = a->beta2; k.step = a->step;
-    TRY(adam_ema_launch(k, (hipStream_t)stream), "adam_ema");
+    if (algorithm == GECCO_CLIP_NONE) {
+        TRY(adam_ema_launch(k, (hipStream_t)stream), "adam_ema");
+    } else {
+        TRY(adam_ema_clip_launch(k, algorithm, stats, clip_val, (hipStream_t)stream), "adam_ema_clip");
+    }
     return 0;
 }
 int gecco_ema_update_f32(const float* p, float* ema, size_t n, double decay, void* stream) {

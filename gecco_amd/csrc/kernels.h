@@ -436,6 +436,17 @@ struct AdamEmaArgs {
     int step;
 };
 int adam_ema_launch(const AdamEmaArgs& a, hipStream_t st);
+// the same step with the gradient clipped while it is read: GECCO_CLIP_NORM multiplies by stats[1] (grad_norm_launch's coefficient),
+// GECCO_CLIP_VALUE clamps to +-clip_val; both before the weight decay term, as torch.nn.utils.clip_grad_* act on p.grad
+#define GECCO_CLIP_NONE 0
+#define GECCO_CLIP_NORM 1
+#define GECCO_CLIP_VALUE 2
+int adam_ema_clip_launch(const AdamEmaArgs& a, int algorithm, const float* stats, float clip_val, hipStream_t st);
+// 2-norm of g * grad_scale / *amp_scale (amp_scale null: 1) and the clip coefficient for max_norm: partial holds grad_norm_blocks(n)
+// doubles (one per block, added in a fixed order: deterministic), stats = {total_norm, clip_coef}
+unsigned grad_norm_blocks(size_t n);
+int grad_norm_launch(const float* g, size_t n, float grad_scale, const float* amp_scale, float max_norm, double* partial, float* stats,
+                     hipStream_t st);
 int ema_update_launch(const float* p, float* ema, size_t n, double decay, hipStream_t st);
 
 // metrics.hip — evaluation metrics on (B, N, 3) clouds (gecco-jax metrics.py:92-156, geometry.py:8-24)

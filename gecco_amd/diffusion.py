@@ -42,6 +42,18 @@ except Exception:  # pragma: no cover - depends on the environment
         def log(self, *args, **kwargs):
             pass
 
+        def configure_gradient_clipping(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
+            """What LightningModule's default amounts to for one optimizer on one device: clip the gradient tensors in place."""
+            if not gradient_clip_val:
+                return
+            params = [p for g in optimizer.param_groups for p in g["params"]]
+            if gradient_clip_algorithm in (None, "norm"):
+                torch.nn.utils.clip_grad_norm_(params, gradient_clip_val)
+            elif gradient_clip_algorithm == "value":
+                torch.nn.utils.clip_grad_value_(params, gradient_clip_val)
+            else:
+                raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', got {gradient_clip_algorithm!r}")
+
 
 def ones(n: int):
     return (1,) * n
@@ -236,6 +248,25 @@ class Diffusion(_Base):
 
     def configure_optimizers(self):
         return torch.optim.Adam(self.parameters(), lr=1e-4)
+
+    def configure_gradient_clipping(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
+        """Lightning's hook for `Trainer(gradient_clip_val=..., gradient_clip_algorithm=...)` (both shipped configs set 1.0:
+        example_configs/shapenet_airplane_unconditional.py:74-76 "value", taskonomy_conditional.py:102-104 "norm").  A
+        `FusedAdamEMA` takes the two values as its own clip settings (`set_gradient_clipping`; algorithm None is Lightning's default,
+        "norm") and clips inside its step kernel: no gradient tensor is touched here, and it works with amp_on_device=True, where the
+        gradients are still scaled at this point.  Any other optimizer gets the base class's behaviour (Lightning's
+        `clip_gradients`; without Lightning torch.nn.utils.clip_grad_norm_ / clip_grad_value_).
+
+        Lightning is not a dependency of this package's tests: the hook is tested by calling it directly.  That Lightning's
+        precision plugin calls it after `scaler.unscale_` and before `optimizer.step`, once per optimizer step, with the Trainer's
+        two values, and that its own `clip_gradients` refuses an optimizer with `_step_supports_amp_scaling`, is written from
+        memory of Lightning's source and has not been checked against an installed Lightning."""
+        from .optim import FusedAdamEMA
+        inner = getattr(optimizer, "optimizer", optimizer)   # (a LightningOptimizer wraps the real one as `.optimizer`)
+        if isinstance(inner, FusedAdamEMA):
+            inner.set_gradient_clipping(gradient_clip_val, gradient_clip_algorithm)
+            return
+        super().configure_gradient_clipping(optimizer, gradient_clip_val, gradient_clip_algorithm)
 
     def training_step(self, batch: Example, batch_idx):
         x, ctx = batch

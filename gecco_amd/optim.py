@@ -14,12 +14,19 @@ wraps it in `EMAOptimizer` (ema.py:61-75), whose `step()` runs the inner optimiz
   ema.py:369-388) and `load_state_dict` accepts it (or a bare Adam state dict), so Lightning checkpoints written by the
   reference resume here and vice versa (`gecco_amd/checkpoint.py`).
 
+Gradient clipping, which both of the reference's trainer settings ask for (example_configs/shapenet_airplane_unconditional.py:74-76
+`gradient_clip_val=1.0, gradient_clip_algorithm="value"`, taskonomy_conditional.py:102-104 the same with `"norm"`), is part of
+the step: `FusedAdamEMA(..., gradient_clip_val=1.0, gradient_clip_algorithm="norm")` clips while the kernel reads the gradient
+(`gecco_grad_norm_f32` + `gecco_adam_ema_step_clip_f32`), also inside the device-side GradScaler protocol, where the gradients
+are still scaled when `step()` runs and nobody else could clip them.
+
 There is no CPU fallback: parameters must live on the HIP device when `step()` runs.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from typing import Any, Iterable
 
 import torch
@@ -40,7 +47,8 @@ class FusedAdamEMA(torch.optim.Optimizer):
 
     def __init__(self, params: Iterable[Tensor] | Iterable[dict], lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, ema_decay: float | None = 0.9999, every_n_steps: int = 1,
-                 current_step: int = 0, missing_grad: str = "raise", amp_on_device: bool = False):
+                 current_step: int = 0, missing_grad: str = "raise", amp_on_device: bool = False,
+                 gradient_clip_val: float | None = None, gradient_clip_algorithm: str = "norm"):
         if ema_decay is not None and not 0.0 <= ema_decay <= 1.0:
             raise ValueError("EMA decay value must be between 0 and 1")
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
@@ -62,8 +70,10 @@ class FusedAdamEMA(torch.optim.Optimizer):
         # reference's trainer) treats the optimizer as unscaling internally: it skips `scaler.unscale_` and its `clip_gradients`
         # refuses a clip value — and both shipped configs combine precision="16-mixed" with gradient_clip_val=1.0
         # (example_configs/*.py).  The default (False) is therefore the host path every trainer knows: unscale -> clip -> step,
-        # found_inf read on the host by GradScaler.  amp_on_device=True: the scale and found_inf stay on the device (one launch, no
-        # host read; gradient clipping is then the caller's business, on unscaled gradients it does not have).
+        # found_inf read on the host by GradScaler.  amp_on_device=True: the scale and found_inf stay on the device (no host read).
+        # Nobody can clip between unscale and step then (the gradients are still scaled when step() runs): clip with this optimizer's
+        # own gradient_clip_val / gradient_clip_algorithm, which work in both paths (the norm pass divides by the scale it is handed);
+        # `Diffusion.configure_gradient_clipping` routes a Lightning Trainer's gradient_clip_val here.
         if amp_on_device:
             self._step_supports_amp_scaling = True
         self.amp_on_device = bool(amp_on_device)
@@ -75,6 +85,53 @@ class FusedAdamEMA(torch.optim.Optimizer):
         self.missing_grad = missing_grad
         self._missing_grad = 0
         self._missing_ids: set[int] = set()   # id(p) of the trainable parameters without a gradient this step
+        # Gradient clipping: a TRAINER setting in the reference (Lightning's names and meanings), so not part of state_dict().
+        self._norm_ws: Tensor | None = None      # one double per block of the sum-of-squares pass (allocated with the flat buffers)
+        self._norm_stats: Tensor | None = None   # fp32 {total_norm, clip_coef} of the last clipped step | the same of grad_norm()
+        self._norm_taken = False                 # a norm-clipped step has written its record
+        self.set_gradient_clipping(gradient_clip_val, gradient_clip_algorithm)
+
+    # ------------------------------------------------------------------------------------------ gradient clipping
+    def set_gradient_clipping(self, gradient_clip_val: float | None = None, gradient_clip_algorithm: str | None = "norm") -> None:
+        """Lightning's `Trainer(gradient_clip_val=..., gradient_clip_algorithm=...)`: "norm" is torch.nn.utils.clip_grad_norm_ with
+        the 2-norm over all parameters, "value" torch.nn.utils.clip_grad_value_.  None or 0: no clipping (the step then calls
+        exactly the entry points it calls without this feature).  Takes effect at the next step()."""
+        algorithm = "norm" if gradient_clip_algorithm is None else gradient_clip_algorithm
+        if algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', got {gradient_clip_algorithm!r}")
+        val = 0.0 if gradient_clip_val is None else float(gradient_clip_val)
+        if not math.isfinite(val) or val < 0.0:
+            raise ValueError(f"gradient_clip_val must be finite and >= 0 (None or 0: no clipping), got {gradient_clip_val!r}")
+        self.gradient_clip_val = val if val > 0.0 else None
+        self.gradient_clip_algorithm = algorithm
+
+    def _launch_grad_norm(self, max_norm: float, slot: int) -> Tensor:
+        """The norm pass on the flat gradient buffer as it stands (gecco_grad_norm_f32: two launches, no host read).  The scale the
+        gradients carry is this optimizer's `grad_scale` float and, inside scaler.step(), the GradScaler's scale tensor.  Returns
+        the record {total_norm, clip_coef} it wrote: slot 0 belongs to the clipped step, slot 1 to grad_norm()."""
+        f = self._flat
+        stats = self._norm_stats[2 * slot:2 * slot + 2]
+        scale = self._amp_scale.to(device=f["g"].device, dtype=torch.float32) if self._amp_scale is not None else None
+        _lib.check(_lib.load().gecco_grad_norm_f32(
+            C.c_void_p(f["g"].data_ptr()), f["g"].numel(), float(self.grad_scale), C.c_void_p(scale.data_ptr()) if scale is not None else None,
+            float(max_norm), C.c_void_p(self._norm_ws.data_ptr()), self._norm_ws.numel() * 8, C.c_void_p(stats.data_ptr()),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "gecco_grad_norm_f32")
+        return stats
+
+    @torch.no_grad()
+    def grad_norm(self) -> Tensor:
+        """The 2-norm of the current gradients over all parameters (after `grad_scale`, i.e. of the mean gradient behind a summing
+        all-reduce), a 0-dim fp32 tensor on the device: no host read, the same bits on every call.  Gradients held in tensors of
+        their own (zero_grad(set_to_none=True)) are gathered into the flat buffer first."""
+        self._ensure()
+        self._gather_foreign_grads()
+        return self._launch_grad_norm(0.0, 1)[0].clone()
+
+    @property
+    def last_grad_norm(self) -> Tensor | None:
+        """total_norm of the last norm-clipped step (what clip_grad_norm_ returns), a 0-dim view of the device record the next such
+        step overwrites; None before the first one.  inf / nan on a step whose gradients were not finite (a GradScaler skips it)."""
+        return self._norm_stats[0] if self._norm_stats is not None and self._norm_taken else None
 
     # ------------------------------------------------------------------------------------------ GradScaler protocol
     # torch.amp.GradScaler.step(optimizer) (the reference's `precision="16-mixed"` trainer: example_configs/*.py) has two paths.
@@ -144,6 +201,9 @@ class FusedAdamEMA(torch.optim.Optimizer):
                 p.data = flat["p"][o:o + k].view(p.shape)
                 p.grad = flat["g"][o:o + k].view(p.shape)
         self._flat, self._spans = flat, spans
+        self._norm_ws = torch.empty(_lib.load().gecco_grad_norm_workspace_bytes(n) // 8, dtype=torch.float64, device=dev)
+        self._norm_stats = torch.zeros(4, dtype=torch.float32, device=dev)
+        self._norm_taken = False
         self._span_of = None
         from .autograd import WEIGHT_IMAGES
         WEIGHT_IMAGES.invalidate()   # the parameters moved into the flat buffer
@@ -285,13 +345,17 @@ class FusedAdamEMA(torch.optim.Optimizer):
         return loss
 
     def launch(self, adam_step: int, do_ema: bool) -> None:
-        """The one kernel of a step (gecco_adam_ema_step_f32) on the current stream, no bookkeeping."""
+        """The kernel of a step (gecco_adam_ema_step_f32) on the current stream, no bookkeeping; with gradient clipping set, the
+        clipped step (gecco_adam_ema_step_clip_f32), behind the norm pass for the "norm" algorithm."""
         f, g = self._flat, self.param_groups[0]
         a = _lib.GeccoAdamEma(f["p"].data_ptr(), f["g"].data_ptr(), f["m"].data_ptr(), f["v"].data_ptr(),
                               f["ema"].data_ptr() if f["ema"] is not None else None, f["p"].numel(), float(g["lr"]),
                               float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                               float(self.decay if self.decay is not None else 0.0), float(self.grad_scale), adam_step,
                               int(do_ema))
+        if self.gradient_clip_val is not None:
+            self._launch_clipped(adam_step, do_ema, a)
+            return
         found_inf = self.__dict__.get("found_inf")   # set (and deleted again) by GradScaler.step around step()
         if found_inf is None:
             _lib.check(_lib.load().gecco_adam_ema_step_f32(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
@@ -305,6 +369,29 @@ class FusedAdamEMA(torch.optim.Optimizer):
                                                            C.c_void_p(found_inf.data_ptr()), C.c_void_p(self._amp_skipped.data_ptr()),
                                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                    "gecco_adam_ema_step_amp_f32")
+
+    def _launch_clipped(self, adam_step: int, do_ema: bool, a: "_lib.GeccoAdamEma") -> None:
+        """The clipped step for the argument record `launch` filled: the norm pass first for "norm", then
+        gecco_adam_ema_step_clip_f32, which also speaks the GradScaler protocol when found_inf is set."""
+        dev = self._flat["p"].device
+        stats = None
+        if self.gradient_clip_algorithm == "norm":
+            stats = self._launch_grad_norm(self.gradient_clip_val, 0)
+            self._norm_taken = True
+        found_inf = self.__dict__.get("found_inf")   # inside scaler.step(self) only (amp_on_device=True)
+        scale = skipped = None
+        if found_inf is not None:
+            if self._amp_skipped is None:
+                self._amp_skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+            skipped = self._amp_skipped
+            found_inf = found_inf.to(device=dev, dtype=torch.float32)
+            scale = self._amp_scale.to(device=dev, dtype=torch.float32) if self._amp_scale is not None else None
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(_lib.load().gecco_adam_ema_step_clip_f32(
+            C.byref(a), 1 if stats is not None else 2, float(self.gradient_clip_val), ptr(stats), ptr(scale), ptr(found_inf), ptr(skipped),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "gecco_adam_ema_step_clip_f32")
 
     # ------------------------------------------------------------------------------------------ EMA weight swap
     def join(self) -> None:   # EMAOptimizer API (its update runs on a side stream / thread; ours is in-stream)

@@ -742,6 +742,30 @@ int gecco_adam_ema_step_f32(const GeccoAdamEma* a, void* stream);
  * (torch skips optimizer.step(), and the EMA update inside it, then) and *skipped is incremented; the bias corrections use
  * step - *skipped, Adam's own step count.  All three are device scalars; the host never waits for the gradients. */
 int gecco_adam_ema_step_amp_f32(const GeccoAdamEma* a, const float* amp_scale, const float* found_inf, int* skipped, void* stream);
+/* Gradient clipping of the reference's trainer settings inside that step (example_configs/shapenet_airplane_unconditional.py:74-76:
+ * gradient_clip_val=1.0, gradient_clip_algorithm="value"; example_configs/taskonomy_conditional.py:102-104: the same with "norm";
+ * Lightning runs torch.nn.utils.clip_grad_value_ / clip_grad_norm_ for them, which are the definitions followed here).
+ *
+ * gecco_grad_norm_f32: the 2-norm of the flat gradient buffer g (n floats, n % 4 == 0, 16-byte aligned) as the TRUE gradients have
+ * it, stats[0] = total_norm = sqrt(sum g^2) * |grad_scale| / *amp_scale (amp_scale NULL: 1), and the coefficient
+ * clip_grad_norm_ multiplies every gradient by, stats[1] = clip_coef = min(1, max_norm / (total_norm + 1e-6)) in fp32 with torch's
+ * operations (reciprocal, times max_norm, clamp); max_norm <= 0: clip_coef = 1.  The squares are accumulated in double, one
+ * partial per block in `workspace` (gecco_grad_norm_workspace_bytes(n) bytes, 8-byte aligned, no initialisation needed), added in
+ * a fixed order: no floating-point atomics, the same bits on every run; the sum is non-finite exactly when a gradient is, and
+ * stats then holds inf / nan (also on a step the GradScaler protocol skips).  Zero pads and the zero gradients of frozen
+ * parameters do not change the norm.  Two launches on `stream`, no synchronisation. */
+size_t gecco_grad_norm_workspace_bytes(size_t n);
+int gecco_grad_norm_f32(const float* g, size_t n, float grad_scale, const float* amp_scale, float max_norm, void* workspace,
+                        size_t workspace_bytes, float* stats, void* stream);
+/* gecco_adam_ema_step_amp_f32 with the gradient clipped while it is read, BEFORE weight_decay * p is added (torch clips p.grad, Adam
+ * adds the decay): algorithm GECCO_CLIP_NORM: g' = (g * grad_scale / *amp_scale) * stats[1], stats as gecco_grad_norm_f32 wrote it
+ * earlier on the same stream (clip_val unused); GECCO_CLIP_VALUE: g' = clamp(g * grad_scale / *amp_scale, -clip_val, +clip_val)
+ * with torch.clamp's NaN behaviour (a NaN stays a NaN; stats unused, may be NULL), clip_val finite and >= 0.  amp_scale,
+ * found_inf and skipped as above, all may be NULL; a skipped step writes nothing. */
+#define GECCO_CLIP_NORM 1
+#define GECCO_CLIP_VALUE 2
+int gecco_adam_ema_step_clip_f32(const GeccoAdamEma* a, int algorithm, float clip_val, const float* stats, const float* amp_scale,
+                                 const float* found_inf, int* skipped, void* stream);
 /* ema = ema * decay + (1 - decay) * p alone (ema_update, ema.py:187-194), for optimizers other than the fused Adam. */
 int gecco_ema_update_f32(const float* p, float* ema, size_t n, double decay, void* stream);
 
