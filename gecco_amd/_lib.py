@@ -217,6 +217,9 @@ SIGNATURES = {
     "gecco_sampler_refresh_known_f64": (i, [vp, vp, vp, vp, vp, i, i, i, i, vp]),
     "gecco_distance_matrix_f32": (i, [vp, vp, vp, i, i, i, i, vp]),
     "gecco_chamfer_f32": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
+    "gecco_chamfer_idx_f32": (i, [vp, vp, vp, vp, vp, vp, i, i, i, i, vp]),
+    "gecco_chamfer_bwd_f32": (i, [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]),
+    "gecco_emd_bwd_f32": (i, [vp, vp, vp, vp, vp, vp, i, i, i, vp]),
     "gecco_set_chamfer_f32": (i, [vp, vp, vp, i, i, i, i, i, vp]),
     "gecco_set_metrics_f32": (i, [vp, vp, vp, i, vp, vp, vp]),
     "gecco_sinkhorn_f32": (i, [vp, vp, vp, vp, vp, i, i, i, fl, i, vp]),

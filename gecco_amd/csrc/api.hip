@@ -2151,6 +2151,41 @@ int gecco_chamfer_f32(const float* a, const float* b, float* out, float* ws, int
     TRY(row_mean_launch(min_ba, out, B, M, 0.5f, 1, s), "chamfer(mean b)");
     return 0;
 }
+int gecco_chamfer_idx_f32(const float* a, const float* b, float* out, float* ws, int* ia, int* ib, int B, int N, int M, int squared,
+                          void* stream) {
+    if (!a || !b || !out || !ws || !ia || !ib) return fail(-1, "chamfer_idx: null argument");
+    if (B < 1 || N < 1 || M < 1) return fail(-2, "chamfer_idx: B = %d, N = %d, M = %d must all be >= 1", B, N, M);
+    if (B > 65535) return fail(-2, "chamfer_idx: B = %d above 65535 (one grid row per sample)", B);
+    if (squared != 0 && squared != 1) return fail(-2, "chamfer_idx: squared = %d is not 0 / 1", squared);
+    hipStream_t s = (hipStream_t)stream;
+    float* min_ab = ws;                       // the layout and the launch order of gecco_chamfer_f32
+    float* min_ba = ws + (size_t)B * N;
+    TRY(nearest_idx_launch(a, b, min_ab, ia, B, N, M, squared, s), "chamfer_idx(a -> b)");
+    TRY(nearest_idx_launch(b, a, min_ba, ib, B, M, N, squared, s), "chamfer_idx(b -> a)");
+    TRY(row_mean_launch(min_ab, out, B, N, 0.5f, 0, s), "chamfer_idx(mean a)");
+    TRY(row_mean_launch(min_ba, out, B, M, 0.5f, 1, s), "chamfer_idx(mean b)");
+    return 0;
+}
+int gecco_chamfer_bwd_f32(const float* a, const float* b, const int* ia, const int* ib, const float* gout, float* da, float* db, int B,
+                          int N, int M, int squared, void* stream) {
+    if (!a || !b || !ia || !ib || !gout || (!da && !db)) return fail(-1, "chamfer_bwd: null argument");
+    if (B < 1 || N < 1 || M < 1) return fail(-2, "chamfer_bwd: B = %d, N = %d, M = %d must all be >= 1", B, N, M);
+    if (B > 65535) return fail(-2, "chamfer_bwd: B = %d above 65535 (one grid row per sample)", B);
+    if (squared != 0 && squared != 1) return fail(-2, "chamfer_bwd: squared = %d is not 0 / 1", squared);
+    hipStream_t s = (hipStream_t)stream;
+    if (da) TRY(chamfer_bwd_launch(a, b, ia, ib, gout, da, B, N, M, squared, s), "chamfer_bwd(da)");
+    if (db) TRY(chamfer_bwd_launch(b, a, ib, ia, gout, db, B, M, N, squared, s), "chamfer_bwd(db)");
+    return 0;
+}
+int gecco_emd_bwd_f32(const float* a, const float* b, const int* cols, const float* gout, float* da, float* db, int B, int N,
+                      int average_squared, void* stream) {
+    if (!a || !b || !cols || !gout || (!da && !db)) return fail(-1, "emd_bwd: null argument");
+    if (B < 1 || N < 1) return fail(-2, "emd_bwd: B = %d, N = %d must both be >= 1", B, N);
+    if (B > 65535) return fail(-2, "emd_bwd: B = %d above 65535 (one grid row per sample)", B);
+    if (average_squared != 0 && average_squared != 1) return fail(-2, "emd_bwd: average_squared = %d is not 0 / 1", average_squared);
+    TRY(emd_bwd_launch(a, b, cols, gout, da, db, B, N, average_squared, (hipStream_t)stream), "emd_bwd");
+    return 0;
+}
 int gecco_sinkhorn_f32(const float* C, float* f, float* g, float* rowcost, float* out, int B, int N, int M, float epsilon,
                        int iterations, void* stream) {
     if (!C || !f || !g || !rowcost || !out) return fail(-1, "sinkhorn: null argument");

@@ -453,6 +453,14 @@ int ema_update_launch(const float* p, float* ema, size_t n, double decay, hipStr
 int dist_matrix_launch(const float* A, const float* Bp, float* D, int B, int N, int M, int squared, hipStream_t st);
 int nearest_dist_launch(const float* A, const float* Bp, float* mins, int B, int N, int M, int squared, hipStream_t st);
 int row_mean_launch(const float* v, float* out, int B, int n, float scale, int accumulate, hipStream_t st);
+// the differentiable Chamfer / EMD: nearest_dist with the winner's index (the same `mins` bits, lowest index of equal minima); the Chamfer
+// gradient of ONE cloud P of a pair (ip (B, N): nearest q of every p, iq (B, M): nearest p of every q; a gather, no atomics); the EMD
+// gradient along an assignment (dA or dB may be null)
+int nearest_idx_launch(const float* A, const float* Bp, float* mins, int* idx, int B, int N, int M, int squared, hipStream_t st);
+int chamfer_bwd_launch(const float* P, const float* Q, const int* ip, const int* iq, const float* gout, float* dP, int B, int N, int M, int squared,
+                       hipStream_t st);
+int emd_bwd_launch(const float* A, const float* Bp, const int* cols, const float* gout, float* dA, float* dB, int B, int N, int squared,
+                   hipStream_t st);
 int sinkhorn_step_launch(const float* C, float* f, float* g, int B, int N, int M, float eps, hipStream_t st);
 // set-vs-set: out[s * ld_s + t * ld_t] (+)= scale * mean_i min_j d(a[s, i], b[t, j]) for every pair of S x T clouds; 1-NNA / MMD / COV
 int set_nearest_mean_launch(const float* A, const float* Bp, float* out, int S, int T, int N, int M, int squared, int ld_s, int ld_t, float scale,

@@ -61,6 +61,125 @@ __global__ __launch_bounds__(256) void nearest_dist_kernel(const float* __restri
     if (i < N) mins[(size_t)b * N + i] = squared ? best : sqrtf(best);
 }
 
+// nearest_dist_kernel that also records WHICH b point won: idx[b, i] = argmin_j, the lowest j of equal minima (numpy / jnp / torch argmin:
+// the scan runs j upwards and only a strictly smaller distance replaces the best).  `mins` must be the bits nearest_dist_kernel writes, so
+// the roundings that kernel is compiled to are spelled out here (contraction off, explicit FMAs, as in pair_dist.h).  Its inner loop is
+// vectorised two b points at a time: a pair gets pair_dist's form, a.b = fma(az, bz, fma(ax, bx, ay by)); the odd last point of a tile
+// (jn odd) goes through the vectoriser's scalar epilogue, where a.b = fma(ay, by, ax bx) + az bz.  Both end in fma(-2, a.b, |a|^2 + |b|^2).
+// `fminf(best, d2)` and `d2 < best ? d2 : best` agree on every input, NaN included (both keep `best`).
+__global__ __launch_bounds__(256) void nearest_idx_kernel(const float* __restrict__ A, const float* __restrict__ Bp,
+                                                          float* __restrict__ mins, int* __restrict__ idx, int N, int M, int squared) {
+#pragma clang fp contract(off)
+    __shared__ __attribute__((aligned(16))) float sb[256 * 4];
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const float* a = A + ((size_t)b * N + min(i, N - 1)) * 3;
+    const float ax = a[0], ay = a[1], az = a[2], aa = sq_norm(ax, ay, az);
+    float best = 3.0e38f;
+    int arg = 0;
+    for (int j0 = 0; j0 < M; j0 += 256) {
+        __syncthreads();
+        const int j = j0 + threadIdx.x;
+        const float* q = Bp + ((size_t)b * M + min(j, M - 1)) * 3;
+        const float bx = q[0], by = q[1], bz = q[2];
+        *reinterpret_cast<f32x4*>(sb + 4 * threadIdx.x) = f32x4{bx, by, bz, sq_norm(bx, by, bz)};
+        __syncthreads();
+        const int jn = min(256, M - j0), jpairs = jn & ~1;
+        for (int jj = 0; jj < jpairs; ++jj) {
+            const f32x4 p = *reinterpret_cast<const f32x4*>(sb + 4 * jj);
+            const float ab = __builtin_fmaf(az, p[2], __builtin_fmaf(ax, p[0], ay * p[1]));
+            const float d2 = fmaxf(__builtin_fmaf(-2.f, ab, aa + p[3]), 0.f);
+            if (d2 < best) { best = d2; arg = j0 + jj; }
+        }
+        if (jn & 1) {
+            const f32x4 p = *reinterpret_cast<const f32x4*>(sb + 4 * jpairs);
+            const float ab = __builtin_fmaf(ay, p[1], ax * p[0]) + az * p[2];
+            const float d2 = fmaxf(__builtin_fmaf(-2.f, ab, aa + p[3]), 0.f);
+            if (d2 < best) { best = d2; arg = j0 + jpairs; }
+        }
+    }
+    if (i < N) {
+        mins[(size_t)b * N + i] = squared ? best : sqrtf(best);
+        idx[(size_t)b * N + i] = arg;
+    }
+}
+
+// d/dp of d(p, q) on the coordinate difference e = p - q: 2 e for the squared distance, e / |e| otherwise, and 0 where |e| == 0 (the
+// reference's expanded form differentiates to NaN there, sqrt'(0) * 0; the subgradient 0 is this library's definition, include/gecco_hip.h)
+static __device__ __forceinline__ void dist_grad(float ex, float ey, float ez, bool squared, float& gx, float& gy, float& gz) {
+    if (squared) { gx = 2.f * ex; gy = 2.f * ey; gz = 2.f * ez; return; }
+    const float n = sqrtf(ex * ex + ey * ey + ez * ez);
+    const float r = n > 0.f ? 1.f / n : 0.f;
+    gx = ex * r; gy = ey * r; gz = ez * r;
+}
+
+// Chamfer backward for ONE cloud of the pair (the other by swapping the roles): with w = gout[b] / 2,
+//     dp[b, i] = (w / N) dist_grad(p_i - q_{ip[i]}) + (w / M) sum_{j : iq[j] == i} dist_grad(p_i - q_j)
+// one thread per p point.  The second sum is a GATHER: iq streams through LDS in tiles of 256 and every thread adds its matches in index
+// order (fp64 accumulators: a point may be the nearest neighbour of the whole other cloud) — N M integer compares per cloud, no atomics, the
+// same bits every run.  An index outside the other cloud (never the forward's output) is not dereferenced.
+__global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float* __restrict__ P, const float* __restrict__ Q, const int* __restrict__ ip,
+                                                          const int* __restrict__ iq, const float* __restrict__ gout, float* __restrict__ dP,
+                                                          int N, int M, int squared) {
+    __shared__ int sq[256];
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const float* p = P + ((size_t)b * N + min(i, N - 1)) * 3;
+    const float* Qb = Q + (size_t)b * M * 3;
+    const float px = p[0], py = p[1], pz = p[2];
+    const float w = 0.5f * gout[b];
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    const int own = ip[(size_t)b * N + min(i, N - 1)];
+    if (own >= 0 && own < M) dist_grad(px - Qb[own * 3], py - Qb[own * 3 + 1], pz - Qb[own * 3 + 2], squared != 0, gx, gy, gz);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int j0 = 0; j0 < M; j0 += 256) {
+        __syncthreads();
+        const int j = j0 + threadIdx.x;
+        sq[threadIdx.x] = j < M ? iq[(size_t)b * M + j] : -1;
+        __syncthreads();
+        const int jn = min(256, M - j0);
+        for (int jj = 0; jj < jn; ++jj) {
+            if (sq[jj] != i) continue;
+            const float* q = Qb + (size_t)(j0 + jj) * 3;
+            float hx, hy, hz;
+            dist_grad(px - q[0], py - q[1], pz - q[2], squared != 0, hx, hy, hz);
+            sx += (double)hx; sy += (double)hy; sz += (double)hz;
+        }
+    }
+    if (i >= N) return;
+    const float wn = w / (float)N, wm = w / (float)M;
+    float* d = dP + ((size_t)b * N + i) * 3;
+    d[0] = wn * gx + wm * (float)sx;
+    d[1] = wn * gy + wm * (float)sy;
+    d[2] = wn * gz + wm * (float)sz;
+}
+
+// EMD backward along a fixed assignment (gecco-jax metrics.py:130-142: the assignment comes out of a callback and is a constant of the
+// gradient): da[b, i] = (gout[b] / N) dist_grad(a_i - b_{cols[i]}), db[b, cols[i]] = -da[b, i].  cols is a permutation: every db row has one
+// writer.  A column outside [0, N) is not dereferenced: that da row is 0 and no db row is written for it.  da or db may be null.
+__global__ __launch_bounds__(256) void emd_bwd_kernel(const float* __restrict__ A, const float* __restrict__ Bp, const int* __restrict__ cols,
+                                                      const float* __restrict__ gout, float* __restrict__ dA, float* __restrict__ dB, int N,
+                                                      int squared) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int j = cols[(size_t)b * N + i];
+    const bool ok = j >= 0 && j < N;
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    if (ok) {
+        const float* a = A + ((size_t)b * N + i) * 3;
+        const float* q = Bp + ((size_t)b * N + j) * 3;
+        dist_grad(a[0] - q[0], a[1] - q[1], a[2] - q[2], squared != 0, gx, gy, gz);
+        const float w = gout[b] / (float)N;
+        gx *= w; gy *= w; gz *= w;
+    }
+    if (dA) {
+        float* d = dA + ((size_t)b * N + i) * 3;
+        d[0] = gx; d[1] = gy; d[2] = gz;
+    }
+    if (dB && ok) {
+        float* d = dB + ((size_t)b * N + j) * 3;
+        d[0] = -gx; d[1] = -gy; d[2] = -gz;
+    }
+}
+
 // out[b] = mean_i v[b, i] (fixed-order tree in one block per sample: deterministic)
 __global__ __launch_bounds__(256) void row_mean_kernel(const float* __restrict__ v, float* __restrict__ out, int n, float scale, int accumulate) {
     __shared__ double red[256];
@@ -300,6 +419,23 @@ int dist_matrix_launch(const float* A, const float* Bp, float* D, int B, int N, 
 int nearest_dist_launch(const float* A, const float* Bp, float* mins, int B, int N, int M, int squared, hipStream_t st) {
     if (B <= 0 || N <= 0 || M <= 0) return -2;
     hipLaunchKernelGGL(nearest_dist_kernel, dim3((N + 255) / 256, B), dim3(256), 0, st, A, Bp, mins, N, M, squared);
+    return (int)hipGetLastError();
+}
+int nearest_idx_launch(const float* A, const float* Bp, float* mins, int* idx, int B, int N, int M, int squared, hipStream_t st) {
+    if (B <= 0 || N <= 0 || M <= 0) return -2;
+    hipLaunchKernelGGL(nearest_idx_kernel, dim3((N + 255) / 256, B), dim3(256), 0, st, A, Bp, mins, idx, N, M, squared);
+    return (int)hipGetLastError();
+}
+int chamfer_bwd_launch(const float* P, const float* Q, const int* ip, const int* iq, const float* gout, float* dP, int B, int N, int M, int squared,
+                       hipStream_t st) {
+    if (B <= 0 || N <= 0 || M <= 0) return -2;
+    hipLaunchKernelGGL(chamfer_bwd_kernel, dim3((N + 255) / 256, B), dim3(256), 0, st, P, Q, ip, iq, gout, dP, N, M, squared);
+    return (int)hipGetLastError();
+}
+int emd_bwd_launch(const float* A, const float* Bp, const int* cols, const float* gout, float* dA, float* dB, int B, int N, int squared,
+                   hipStream_t st) {
+    if (B <= 0 || N <= 0) return -2;
+    hipLaunchKernelGGL(emd_bwd_kernel, dim3((N + 255) / 256, B), dim3(256), 0, st, A, Bp, cols, gout, dA, dB, N, squared);
     return (int)hipGetLastError();
 }
 int row_mean_launch(const float* v, float* out, int B, int n, float scale, int accumulate, hipStream_t st) {

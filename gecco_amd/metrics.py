@@ -6,13 +6,23 @@ fp32 HIP tensors (or single (N, 3) clouds) and returns one value per sample; the
 `jax.pure_callback` into `scipy.optimize.linear_sum_assignment`, metrics.py:108-121) on the distance matrix the device
 computed.  `emd` is its device twin: an exact epsilon-scaling auction, one workgroup per pair (csrc/emd.hip), whose assignment
 is optimal for the match cost quantised to 2^-24 of the pair's cost bound (include/gecco_hip.h); `pairwise_set_distance(
-kind="emd_exact")` runs it on every pair of two sets in one launch.  There is no CPU fallback for the device parts."""
+kind="emd_exact")` runs it on every pair of two sets in one launch.  There is no CPU fallback for the device parts.
+
+`chamfer_distance`, `chamfer_distance_squared` and `emd` are differentiable in both clouds, as the reference's are (metrics.py:92-142:
+jnp code, and a gather along an assignment that is a constant of the gradient): with an input that requires grad the forward records the
+nearest-neighbour indices (gecco_chamfer_idx_f32) or keeps the solver's assignment, and the backward is a HIP kernel
+(gecco_chamfer_bwd_f32: a deterministic gather, no float atomics; gecco_emd_bwd_f32).  The value is bit-identical either way, and a call
+without a gradient to record takes the plain path.  The derivative of a distance is taken on the coordinate difference, and is DEFINED
+as 0 where the distance is 0 (the reference's formula gives NaN there: sqrt'(0) * 0).  Once differentiable: a double backward raises.
+Out of scope: `sinkhorn_emd`, `scipy_emd`, `distance_matrix`, `pairwise_set_distance` and `set_metrics` return tensors without a graph,
+as before.  The metrics are 3-D."""
 from __future__ import annotations
 
 import ctypes as C
 
 import torch
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .hip_ops import _ptr, _stream
@@ -38,20 +48,81 @@ def distance_matrix(a: Tensor, b: Tensor, squared: bool = False) -> Tensor:
     return D[0] if single else D
 
 
-def chamfer_distance(a: Tensor, b: Tensor, squared: bool = False) -> Tensor:
-    """(mean_i min_j d(a_i, b_j) + mean_j min_i d(a_i, b_j)) / 2 per sample; the distance matrix is never materialised."""
-    a, b, single = _batched(a, b)
+def _wants_grad(a: Tensor, b: Tensor) -> bool:
+    return torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)
+
+
+def _grad_out(g: Tensor) -> Tensor:
+    return g.float().contiguous()   # (B,): a `.sum()` upstream hands an expanded scalar
+
+
+def _chamfer_idx(a: Tensor, b: Tensor, squared: bool):
     B, N, _ = a.shape
     M = b.shape[1]
     out = torch.empty(B, device=a.device, dtype=torch.float32)
     ws = torch.empty(B * (N + M), device=a.device, dtype=torch.float32)
-    _lib.check(_lib.load().gecco_chamfer_f32(_ptr(a), _ptr(b), _ptr(out), _ptr(ws), B, N, M, int(squared), _stream()),
-               "gecco_chamfer_f32")
-    return out[0] if single else out
+    ia = torch.empty(B, N, device=a.device, dtype=torch.int32)
+    ib = torch.empty(B, M, device=a.device, dtype=torch.int32)
+    _lib.check(_lib.load().gecco_chamfer_idx_f32(_ptr(a), _ptr(b), _ptr(out), _ptr(ws), C.c_void_p(ia.data_ptr()), C.c_void_p(ib.data_ptr()),
+                                                 B, N, M, int(squared), _stream()), "gecco_chamfer_idx_f32")
+    return out, ia, ib
 
 
-def chamfer_distance_squared(a: Tensor, b: Tensor) -> Tensor:
-    return chamfer_distance(a, b, squared=True)
+class ChamferFn(torch.autograd.Function):
+    """chamfer_distance on (B, N, 3) / (B, M, 3) fp32 clouds with the gradient at the recorded nearest neighbours (the argmin held fixed, as
+    the `min` rule of the reference's jnp code does, metrics.py:92-103).  Returns (value, ia, ib); the int32 indices carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, a, b, squared):
+        out, ia, ib = _chamfer_idx(a, b, squared)
+        ctx.save_for_backward(a, b, ia, ib)
+        ctx.squared = bool(squared)
+        ctx.mark_non_differentiable(ia, ib)
+        return out, ia, ib
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout, _gia, _gib):
+        a, b, ia, ib = ctx.saved_tensors
+        B, N, _ = a.shape
+        M = b.shape[1]
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is None and db is None:
+            return None, None, None
+        _lib.check(_lib.load().gecco_chamfer_bwd_f32(_ptr(a), _ptr(b), C.c_void_p(ia.data_ptr()), C.c_void_p(ib.data_ptr()),
+                                                     _ptr(_grad_out(gout)), _ptr(da), _ptr(db), B, N, M, int(ctx.squared), _stream()),
+                   "gecco_chamfer_bwd_f32")
+        return da, db, None
+
+
+def chamfer_distance(a: Tensor, b: Tensor, squared: bool = False, return_indices: bool = False):
+    """(mean_i min_j d(a_i, b_j) + mean_j min_i d(a_i, b_j)) / 2 per sample; the distance matrix is never materialised.  Differentiable in
+    a and b (the derivative is 0 where a nearest-neighbour distance is 0; see the module docstring); the value has the same bits with and
+    without a graph.  return_indices: (value, ia, ib) with the int64 index of every point's nearest neighbour in the other cloud, the
+    lowest index of equal minima."""
+    a, b, single = _batched(a, b)
+    if _wants_grad(a, b):
+        out, ia, ib = ChamferFn.apply(a, b, bool(squared))
+    elif return_indices:
+        out, ia, ib = _chamfer_idx(a, b, bool(squared))
+    else:
+        B, N, _ = a.shape
+        M = b.shape[1]
+        out = torch.empty(B, device=a.device, dtype=torch.float32)
+        ws = torch.empty(B * (N + M), device=a.device, dtype=torch.float32)
+        _lib.check(_lib.load().gecco_chamfer_f32(_ptr(a), _ptr(b), _ptr(out), _ptr(ws), B, N, M, int(squared), _stream()),
+                   "gecco_chamfer_f32")
+        return out[0] if single else out
+    out = out[0] if single else out
+    if not return_indices:
+        return out
+    ia, ib = ia.long(), ib.long()
+    return (out, ia[0], ib[0]) if single else (out, ia, ib)
+
+
+def chamfer_distance_squared(a: Tensor, b: Tensor, return_indices: bool = False):
+    return chamfer_distance(a, b, squared=True, return_indices=return_indices)
 
 
 def scipy_emd(p1: Tensor, p2: Tensor, match: str = "l1", average: str = "l1") -> Tensor:
@@ -105,23 +176,60 @@ def _pairs(mask: Tensor) -> list:
     return [tuple(i) if len(i) > 1 else i[0] for i in idx]
 
 
+def _emd_solve(a: Tensor, b: Tensor, msq: int, asq: int, cap: int, max_rounds: int | None, keep_assignment: bool):
+    B, N, _ = a.shape
+    out = torch.empty(B, device=a.device, dtype=torch.float32)
+    status = torch.empty(B, device=a.device, dtype=torch.int32)
+    cols = torch.empty(B, N, device=a.device, dtype=torch.int32) if keep_assignment else None
+    _lib.check(_lib.load().gecco_emd_f32(_ptr(a), _ptr(b), B, N, msq, asq, _ptr(out),
+                                         C.c_void_p(cols.data_ptr() if cols is not None else 0), C.c_void_p(status.data_ptr()),
+                                         cap, _stream()), "gecco_emd_f32")
+    _emd_status(status, max_rounds, "emd")
+    return out, cols
+
+
+class EmdFn(torch.autograd.Function):
+    """emd on (B, N, 3) fp32 clouds with the gradient along the solver's assignment, a constant of the gradient as in the reference
+    (metrics.py:130-142).  Returns (value, cols); the int32 assignment carries no gradient.  The solver's errors are raised in the forward,
+    before a graph is recorded."""
+
+    @staticmethod
+    def forward(ctx, a, b, msq, asq, cap, max_rounds):
+        out, cols = _emd_solve(a, b, msq, asq, cap, max_rounds, True)
+        ctx.save_for_backward(a, b, cols)
+        ctx.asq = asq
+        ctx.mark_non_differentiable(cols)
+        return out, cols
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout, _gcols):
+        a, b, cols = ctx.saved_tensors
+        B, N, _ = a.shape
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is None and db is None:
+            return (None,) * 6
+        _lib.check(_lib.load().gecco_emd_bwd_f32(_ptr(a), _ptr(b), C.c_void_p(cols.data_ptr()), _ptr(_grad_out(gout)), _ptr(da), _ptr(db),
+                                                 B, N, ctx.asq, _stream()), "gecco_emd_bwd_f32")
+        return da, db, None, None, None, None
+
+
 def emd(p1: Tensor, p2: Tensor, match: str = "l1", average: str = "l1", return_assignment: bool = False,
         max_rounds: int | None = None):
     """Exact earth mover's distance on the device: the twin of `scipy_emd` (gecco-jax metrics.py:114-142).  The assignment
     minimises the `match` cost (quantised: within N * c_max * 2^-24 of scipy's optimum, include/gecco_hip.h), the value is
     the mean `average` cost along it.  (B, N, 3) clouds give a (B,) tensor, (N, 3) clouds a scalar; with return_assignment
     the int64 `cols` of scipy's (rows, cols) as well (rows = arange(N)).  A non-finite coordinate raises ValueError (as scipy
-    does on such a matrix); a pair that needs more than `max_rounds` bidding rounds raises GeccoHipError."""
+    does on such a matrix); a pair that needs more than `max_rounds` bidding rounds raises GeccoHipError.  Differentiable in p1
+    and p2 along the assignment, which is a constant of the gradient (the derivative of the `average` distance is 0 where that
+    distance is 0; see the module docstring); the value has the same bits with and without a graph."""
     a, b, single = _batched(p1, p2)
     msq, asq, cap = _emd_args(a, b, match, average, max_rounds)
-    B, N, _ = a.shape
-    out = torch.empty(B, device=a.device, dtype=torch.float32)
-    status = torch.empty(B, device=a.device, dtype=torch.int32)
-    cols = torch.empty(B, N, device=a.device, dtype=torch.int32) if return_assignment else None
-    _lib.check(_lib.load().gecco_emd_f32(_ptr(a), _ptr(b), B, N, msq, asq, _ptr(out),
-                                         C.c_void_p(cols.data_ptr() if cols is not None else 0), C.c_void_p(status.data_ptr()),
-                                         cap, _stream()), "gecco_emd_f32")
-    _emd_status(status, max_rounds, "emd")
+    if _wants_grad(a, b):
+        out, cols = EmdFn.apply(a, b, msq, asq, cap, max_rounds)
+    else:
+        out, cols = _emd_solve(a, b, msq, asq, cap, max_rounds, return_assignment)
     if single:
         out = out[0]
     if not return_assignment:

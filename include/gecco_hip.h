@@ -786,6 +786,24 @@ int gecco_distance_matrix_f32(const float* a, const float* b, float* D, int B, i
 /* Chamfer distance per sample (gecco-jax metrics.py:92-103): out[b] = (mean_i min_j d(a_i, b_j) + mean_j min_i d) / 2.
  * ws: B * (N + M) floats. */
 int gecco_chamfer_f32(const float* a, const float* b, float* out, float* ws, int B, int N, int M, int squared, void* stream);
+/* The same forward, which also records the correspondences a gradient needs (gecco-jax metrics.py:92-103: the `jnp.min` over the
+ * distance matrix that JAX differentiates through its argmin): ia (B, N) / ib (B, M) int32, for every point the index of its nearest
+ * neighbour in the other cloud, the LOWEST index of equal minima (numpy / jnp / torch argmin).  `out` is bit-identical to
+ * gecco_chamfer_f32's on the same inputs (same distance formula, tile order and reduction); matrix-free like it.  ws: B * (N + M)
+ * floats.  B, N, M >= 1 (B <= 65535), squared 0 / 1. */
+int gecco_chamfer_idx_f32(const float* a, const float* b, float* out, float* ws, int* ia, int* ib, int B, int N, int M, int squared,
+                          void* stream);
+/* Chamfer backward at recorded correspondences (the gradient of metrics.py:92-103 with the argmin held fixed, which is what JAX's
+ * `min` rule computes).  With w = gout[b] / 2:
+ *   da[b, i] = (w / N) g(a_i, b_{ia[i]}) + (w / M) sum_{j : ib[j] == i} g(a_i, b_j),     db symmetrically,
+ * g(p, q) = d/dp d(p, q) taken on the coordinate difference e = p - q, not on the expanded |p|^2 + |q|^2 - 2 p.q: 2 e for
+ * squared != 0, e / |e| otherwise, and 0 WHERE |e| == 0: the reference's formula differentiates to NaN there (sqrt'(0) * 0); this
+ * library defines the subgradient 0.  Deterministic, no float atomics: the second sum is a gather — every point scans the other
+ * cloud's indices (staged through LDS) and adds its matches in index order — so gradients are bit-reproducible run to run.
+ * gout (B), da (B, N, 3), db (B, M, 3); da or db (not both) may be null: that gradient is not computed.  An index outside the
+ * other cloud is not dereferenced.  B, N, M >= 1 (B <= 65535), squared 0 / 1. */
+int gecco_chamfer_bwd_f32(const float* a, const float* b, const int* ia, const int* ib, const float* gout, float* da, float* db, int B,
+                          int N, int M, int squared, void* stream);
 /* Set-vs-set Chamfer distances (gecco-jax benchmark.py:21-39 `batched_pairwise_distance` with `chamfer_distance` / `_squared`):
  * out (S, T) row-major, out[s, t] = Chamfer(a[s], b[t]) for a (S, N, 3) and b (T, M, 3) — two launches (one per direction), no
  * N x M matrix anywhere.  The minimum is taken over |b|^2 - 2 a.b with |a|^2 added after it (the reference adds it before: equal up
@@ -816,6 +834,13 @@ int gecco_sinkhorn_f32(const float* C, float* f, float* g, float* rowcost, float
 /* B pairs (a[p], b[p]), a and b (B, N, 3): out (B), assign (B, N) int32 (nullable: the column of each row), status (B) int32. */
 int gecco_emd_f32(const float* a, const float* b, int B, int N, int match_squared, int average_squared, float* out, int* assign,
                   int* status, int max_rounds, void* stream);
+/* EMD backward along an assignment (gecco-jax metrics.py:130-142: `scipy_emd` gathers distance_matrix(...)[rows, cols] along an
+ * assignment that comes out of a callback, a constant of the gradient): da[b, i] = (gout[b] / N) g(a_i, b_{cols[i]}),
+ * db[b, cols[i]] = -da[b, i], g as in gecco_chamfer_bwd_f32 for the `average` distance (the same rule at distance 0).  cols (B, N)
+ * int32 is gecco_emd_f32's `assign`, a permutation: every db row has one writer, no atomics.  A column outside [0, N) is not
+ * dereferenced (its da row is 0, no db row is written for it).  da or db (not both) may be null.  B, N >= 1 (B <= 65535). */
+int gecco_emd_bwd_f32(const float* a, const float* b, const int* cols, const float* gout, float* da, float* db, int B, int N,
+                      int average_squared, void* stream);
 /* every pair of a (S, N, 3) set and a (T, N, 3) set in one launch (gecco-jax benchmark.py:21-39 `batched_pairwise_distance`
  * with an exact EMD): out (S, T) row-major, status (S, T) int32; no expanded copies of the clouds. */
 int gecco_set_emd_f32(const float* a, const float* b, int S, int T, int N, int match_squared, int average_squared, float* out,
