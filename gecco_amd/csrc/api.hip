@@ -2219,6 +2219,53 @@ int gecco_set_emd_f32(const float* a, const float* b, int S, int T, int N, int m
     return 0;
 }
 
+// matrix-free Sinkhorn (sinkhorn.hip).  form: 0 auto (resident within GECCO_SINKHORN_RESIDENT_MAX_POINTS), 1 resident, 2 streaming
+static int sinkhorn_common_checks(const char* who, int N, int M, float epsilon) {
+    if (N < 1 || M < 1) return fail(-2, "%s: N = %d, M = %d must both be >= 1", who, N, M);
+    if (!(epsilon > 0.f)) return fail(-2, "%s: epsilon = %g must be > 0", who, (double)epsilon);
+    return 0;
+}
+int gecco_sinkhorn_cloud_f32(const float* a, const float* b, float* f, float* g, float* ws, float* out, int B, int N, int M, float epsilon,
+                             int iterations, int form, void* stream) {
+    if (!a || !b || !out) return fail(-1, "sinkhorn_cloud: null argument");
+    if (B < 1) return fail(-2, "sinkhorn_cloud: empty batch");
+    if (int rc = sinkhorn_common_checks("sinkhorn_cloud", N, M, epsilon)) return rc;
+    if (iterations < 1) return fail(-2, "sinkhorn_cloud: iterations = %d must be >= 1", iterations);
+    if (form < 0 || form > 2) return fail(-2, "sinkhorn_cloud: form = %d is not 0 (auto), 1 (resident) or 2 (streaming)", form);
+    const bool fits = (long long)N + M <= GECCO_SINKHORN_RESIDENT_MAX_POINTS;
+    if (form == 1 && !fits)
+        return fail(-2, "sinkhorn_cloud: the resident form takes N + M <= %d (got %d + %d)", GECCO_SINKHORN_RESIDENT_MAX_POINTS, N, M);
+    if (form == 1 || (form == 0 && fits)) {
+        TRY(sinkhorn_resident_launch(a, b, f, g, out, B, 1, 0, N, M, epsilon, iterations, (hipStream_t)stream), "sinkhorn_cloud(resident)");
+        return 0;
+    }
+    if (!f || !g || !ws) return fail(-1, "sinkhorn_cloud: the streaming form needs f, g and ws");
+    if (B > 65535) return fail(-2, "sinkhorn_cloud: B = %d above 65535 (one grid row per sample)", B);
+    TRY(sinkhorn_stream_launch(a, b, f, g, ws, out, B, N, M, epsilon, iterations, (hipStream_t)stream), "sinkhorn_cloud(streaming)");
+    return 0;
+}
+int gecco_set_sinkhorn_f32(const float* a, const float* b, float* out, int S, int T, int N, int M, float epsilon, int iterations,
+                           void* stream) {
+    if (!a || !b || !out) return fail(-1, "set_sinkhorn: null argument");
+    if (S <= 0 || T <= 0) return fail(-2, "set_sinkhorn: empty set");
+    if ((long long)S * T > 0x7fffffffLL) return fail(-2, "set_sinkhorn: S * T = %lld pairs above 2^31 - 1", (long long)S * T);
+    if (int rc = sinkhorn_common_checks("set_sinkhorn", N, M, epsilon)) return rc;
+    if (iterations < 1) return fail(-2, "set_sinkhorn: iterations = %d must be >= 1", iterations);
+    if ((long long)N + M > GECCO_SINKHORN_RESIDENT_MAX_POINTS)
+        return fail(-2, "set_sinkhorn: the resident form takes N + M <= %d (got %d + %d)", GECCO_SINKHORN_RESIDENT_MAX_POINTS, N, M);
+    TRY(sinkhorn_resident_launch(a, b, nullptr, nullptr, out, S * T, T, 1, N, M, epsilon, iterations, (hipStream_t)stream), "set_sinkhorn");
+    return 0;
+}
+int gecco_sinkhorn_cloud_bwd_f32(const float* a, const float* b, const float* f, const float* g, const float* gout, float* da, float* db,
+                                 int B, int N, int M, float epsilon, void* stream) {
+    if (!a || !b || !f || !g || !gout || (!da && !db)) return fail(-1, "sinkhorn_cloud_bwd: null argument");
+    if (B < 1) return fail(-2, "sinkhorn_cloud_bwd: empty batch");
+    if (B > 65535) return fail(-2, "sinkhorn_cloud_bwd: B = %d above 65535 (one grid row per sample)", B);
+    if (int rc = sinkhorn_common_checks("sinkhorn_cloud_bwd", N, M, epsilon)) return rc;
+    TRY(sinkhorn_bwd_launch(a, b, f, g, gout, da, db, B, N, M, epsilon, (hipStream_t)stream), "sinkhorn_cloud_bwd");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- ConvNeXt conditioner (channels-last)
 int gecco_convnext_stem_f32(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out,
                             int B, int H, int W, int C, float eps, void* stream) {

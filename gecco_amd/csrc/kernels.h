@@ -472,6 +472,15 @@ int sinkhorn_cost_launch(const float* C, const float* f, const float* g, float* 
 // (A[s], B[t]); out / status (pairs), assign (pairs, N) or null
 int emd_auction_launch(const float* A, const float* Bc, float* out, int* assign, int* status, int pairs, int T, int set_mode, int N,
                        int match_sq, int avg_sq, int max_rounds, hipStream_t st);
+// sinkhorn.hip — matrix-free log-domain Sinkhorn between clouds (costs recomputed from the coordinates).  resident: one workgroup per pair,
+// the whole solve in one launch (N + M <= GECCO_SINKHORN_RESIDENT_MAX_POINTS; set_mode as emd_auction_launch; f, g null or (pairs, N) /
+// (pairs, M)); stream: any size, 2 * iterations row-pass launches on f (B, N), g (B, M), ws (B, N); bwd: the gradient rows on saved f, g
+int sinkhorn_resident_launch(const float* A, const float* Bc, float* f, float* g, float* out, int pairs, int T, int set_mode, int N, int M,
+                             float eps, int iterations, hipStream_t st);
+int sinkhorn_stream_launch(const float* A, const float* Bc, float* f, float* g, float* ws, float* out, int B, int N, int M, float eps,
+                           int iterations, hipStream_t st);
+int sinkhorn_bwd_launch(const float* A, const float* Bc, const float* f, const float* g, const float* gout, float* dA, float* dB, int B, int N,
+                        int M, float eps, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

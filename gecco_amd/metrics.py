@@ -15,7 +15,14 @@ nearest-neighbour indices (gecco_chamfer_idx_f32) or keeps the solver's assignme
 without a gradient to record takes the plain path.  The derivative of a distance is taken on the coordinate difference, and is DEFINED
 as 0 where the distance is 0 (the reference's formula gives NaN there: sqrt'(0) * 0).  Once differentiable: a double backward raises.
 Out of scope: `sinkhorn_emd`, `scipy_emd`, `distance_matrix`, `pairwise_set_distance` and `set_metrics` return tensors without a graph,
-as before.  The metrics are 3-D."""
+as before.  The metrics are 3-D.
+
+`sinkhorn_cost` is the matrix-free twin of `sinkhorn_emd` (csrc/sinkhorn.hip): the same fixed-sweep log-domain iteration, with every cost
+recomputed from the coordinates, so no (N, M) matrix exists and clouds of any, also unequal, size run — one workgroup and one launch per pair
+while N + M <= SINKHORN_RESIDENT_MAX_POINTS (clouds and potentials in LDS), a streaming row-pass kernel above.  It is differentiable in both
+clouds along the fixed plan (`SinkhornFn`, gecco_sinkhorn_cloud_bwd_f32: fixed-order sums, no float atomics), `sinkhorn_divergence` composes
+the debiased OT(a, b) - OT(a, a) / 2 - OT(b, b) / 2 from it, and `pairwise_set_distance(kind="sinkhorn")` runs every pair of two sets in one
+launch with no scratch."""
 from __future__ import annotations
 
 import ctypes as C
@@ -255,12 +262,108 @@ def sinkhorn_emd(p1: Tensor, p2: Tensor, epsilon: float = 0.01, iterations: int 
     return out[0] if single else out
 
 
+SINKHORN_RESIDENT_MAX_POINTS = 7768   # GECCO_SINKHORN_RESIDENT_MAX_POINTS: N + M of a pair whose clouds and potentials fit one CU's LDS
+_SINKHORN_FORMS = {None: 0, "resident": 1, "streaming": 2}
+
+
+def _sinkhorn_args(N: int, M: int, epsilon: float, iterations: int, form):
+    if form not in _SINKHORN_FORMS:
+        raise ValueError("form must be None, 'resident' or 'streaming'")
+    if not float(epsilon) > 0.0:
+        raise ValueError("epsilon must be > 0")
+    if int(iterations) < 1:
+        raise ValueError("iterations must be >= 1")
+    fits = N + M <= SINKHORN_RESIDENT_MAX_POINTS
+    if form == "resident" and not fits:
+        raise ValueError(f"the resident form takes N + M <= {SINKHORN_RESIDENT_MAX_POINTS} points (got {N} + {M})")
+    return 1 if (form == "resident" or (form is None and fits)) else 2
+
+
+def _sinkhorn_solve(a: Tensor, b: Tensor, epsilon: float, iterations: int, form: int, keep_potentials: bool):
+    B, N, _ = a.shape
+    M = b.shape[1]
+    pa, pb = _ptr(a), _ptr(b)   # HIP tensors only: there is no CPU fallback
+    out = torch.empty(B, device=a.device, dtype=torch.float32)
+    f = g = ws = None
+    if keep_potentials or form == 2:
+        f = torch.empty(B, N, device=a.device, dtype=torch.float32)
+        g = torch.empty(B, M, device=a.device, dtype=torch.float32)
+    if form == 2:
+        ws = torch.empty(B, N, device=a.device, dtype=torch.float32)
+    _lib.check(_lib.load().gecco_sinkhorn_cloud_f32(pa, pb, _ptr(f), _ptr(g), _ptr(ws), _ptr(out), B, N, M, float(epsilon), int(iterations),
+                                                    form, _stream()), "gecco_sinkhorn_cloud_f32")
+    return out, f, g
+
+
+class SinkhornFn(torch.autograd.Function):
+    """sinkhorn_cost on (B, N, 3) / (B, M, 3) fp32 clouds with the gradient along the plan of the potentials the forward ended on, a constant
+    of the gradient.  Returns (value, f, g); the potentials carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, a, b, epsilon, iterations, form):
+        out, f, g = _sinkhorn_solve(a, b, epsilon, iterations, form, True)
+        ctx.save_for_backward(a, b, f, g)
+        ctx.epsilon = float(epsilon)
+        ctx.mark_non_differentiable(f, g)
+        return out, f, g
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout, _gf, _gg):
+        a, b, f, g = ctx.saved_tensors
+        B, N, _ = a.shape
+        M = b.shape[1]
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is None and db is None:
+            return (None,) * 5
+        _lib.check(_lib.load().gecco_sinkhorn_cloud_bwd_f32(_ptr(a), _ptr(b), _ptr(f), _ptr(g), _ptr(_grad_out(gout)), _ptr(da), _ptr(db),
+                                                            B, N, M, ctx.epsilon, _stream()), "gecco_sinkhorn_cloud_bwd_f32")
+        return da, db, None, None, None
+
+
+def sinkhorn_cost(p1: Tensor, p2: Tensor, epsilon: float = 0.01, iterations: int = 200, return_potentials: bool = False, form: str | None = None):
+    """Entropic OT cost <P, C> of `sinkhorn_emd` without the cost matrix: the same `iterations` log-domain sweeps from g = 0 on the squared
+    distance between uniform clouds, every cost recomputed from the coordinates on the device.  (B, N, 3) and (B, M, 3) clouds give a (B,)
+    tensor, (N, 3) and (M, 3) a scalar; N and M are free.  form None: the resident kernel (one launch per call) while N + M <=
+    SINKHORN_RESIDENT_MAX_POINTS, the streaming kernel above; "resident" (ValueError above the limit) or "streaming" force one.  With
+    return_potentials: (value, f, g), the dual potentials (B, N), (B, M) the sweeps ended on.
+
+    Differentiable in p1 and p2 with the plan P_ij = exp((f_i + g_j - C_ij) / epsilon) / (N M) held constant, as the exact EMD's assignment
+    is: d value / d a_i = sum_j P_ij 2 (a_i - b_j), d value / d b_j = sum_i P_ij 2 (b_j - a_i).  This is also the envelope gradient of the
+    entropic cost, but it is exact only once the sweeps have converged, and at epsilon = 0.01 and 100 sweeps they have not (on random unit
+    clouds the plan's row marginals were still off by up to 0.5 in an fp64 restatement): this is the gradient of a FIXED-SWEEP definition, not
+    ott's.  The sums have a fixed order and use no float atomics, so gradients are the same bits run to run; the value has the same bits
+    with and without a graph.  Once differentiable."""
+    a, b, single = _batched(p1, p2)
+    fm = _sinkhorn_args(a.shape[1], b.shape[1], epsilon, iterations, form)
+    if _wants_grad(a, b):
+        out, f, g = SinkhornFn.apply(a, b, float(epsilon), int(iterations), fm)
+    else:
+        out, f, g = _sinkhorn_solve(a, b, epsilon, iterations, fm, return_potentials)
+    if single:
+        out = out[0]
+    if not return_potentials:
+        return out
+    return (out, f[0], g[0]) if single else (out, f, g)
+
+
+def sinkhorn_divergence(p1: Tensor, p2: Tensor, epsilon: float = 0.01, iterations: int = 200) -> Tensor:
+    """The debiased entropic cost OT(a, b) - OT(a, a) / 2 - OT(b, b) / 2 of three `sinkhorn_cost` calls: 0 for equal clouds.  Differentiable
+    like `sinkhorn_cost`; a tensor given in both slots of a self term receives both parts of that term's gradient."""
+    return (sinkhorn_cost(p1, p2, epsilon, iterations) - 0.5 * sinkhorn_cost(p1, p1, epsilon, iterations)
+            - 0.5 * sinkhorn_cost(p2, p2, epsilon, iterations))
+
+
 # ----------------------------------------------------------------------------------------------- set against set
-def pairwise_set_distance(a: Tensor, b: Tensor, kind: str = "chamfer", block_size: int = 16, epsilon: float = 0.1) -> Tensor:
+def pairwise_set_distance(a: Tensor, b: Tensor, kind: str = "chamfer", block_size: int = 16, epsilon: float = 0.1,
+                          iterations: int | None = None) -> Tensor:
     """(S, T) distances between EVERY cloud of a (S, N, 3) and every cloud of b (T, M, 3): gecco-jax benchmark.py:21-39
     (`batched_pairwise_distance`).  kind "chamfer" / "chamfer_squared": one HIP kernel per direction, no N x M matrix per pair;
     "emd": the entropic `sinkhorn_emd(epsilon=0.1)` of BenchmarkCallback (:73-77) on blocks of `block_size` x `block_size` pairs;
-    "emd_exact": the exact `emd` (l1 match and average, like `scipy_emd`'s defaults) of every pair in one launch."""
+    "emd_exact": the exact `emd` (l1 match and average, like `scipy_emd`'s defaults) of every pair in one launch; "sinkhorn": the matrix-free
+    `sinkhorn_cost(epsilon, iterations)` (iterations None: its default, 200) of every pair in one launch of the resident kernel, no scratch
+    beyond the output (ValueError when N + M is above SINKHORN_RESIDENT_MAX_POINTS).  `iterations` belongs to "sinkhorn" alone."""
     if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3:
         raise ValueError("expected sets of clouds of shape (S, N, 3) and (T, M, 3)")
     a, b = a.float().contiguous(), b.float().contiguous()
@@ -281,8 +384,17 @@ def pairwise_set_distance(a: Tensor, b: Tensor, kind: str = "chamfer", block_siz
                                                  _stream()), "gecco_set_emd_f32")
         _emd_status(status, None, "pairwise_set_distance(kind='emd_exact')")
         return out
+    if kind == "sinkhorn":
+        its = 200 if iterations is None else int(iterations)
+        _sinkhorn_args(N, M, epsilon, its, "resident")
+        if S * T > 2**31 - 1:
+            raise ValueError(f"S * T = {S * T} pairs above 2^31 - 1")
+        out = torch.empty(S, T, device=a.device, dtype=torch.float32)
+        _lib.check(_lib.load().gecco_set_sinkhorn_f32(_ptr(a), _ptr(b), _ptr(out), S, T, N, M, float(epsilon), its, _stream()),
+                   "gecco_set_sinkhorn_f32")
+        return out
     if kind != "emd":
-        raise ValueError("kind must be 'chamfer', 'chamfer_squared', 'emd' or 'emd_exact'")
+        raise ValueError("kind must be 'chamfer', 'chamfer_squared', 'emd', 'emd_exact' or 'sinkhorn'")
     out = torch.empty(S, T, device=a.device, dtype=torch.float32)
     for s0 in range(0, S, block_size):
         for t0 in range(0, T, block_size):

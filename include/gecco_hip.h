@@ -845,6 +845,35 @@ int gecco_emd_bwd_f32(const float* a, const float* b, const int* cols, const flo
  * with an exact EMD): out (S, T) row-major, status (S, T) int32; no expanded copies of the clouds. */
 int gecco_set_emd_f32(const float* a, const float* b, int S, int T, int N, int match_squared, int average_squared, float* out,
                       int* status, int max_rounds, void* stream);
+/* Matrix-free entropic optimal transport between uniform clouds a (B, N, 3), b (B, M, 3) (gecco-jax metrics.py:144-156: `sinkhorn_emd`,
+ * ott's Sinkhorn on the squared-Euclidean point-cloud cost), csrc/sinkhorn.hip.  The iteration is gecco_sinkhorn_f32's, with the costs
+ * recomputed from the coordinates instead of read from a matrix: C_ij = max(|a_i|^2 + |b_j|^2 - 2 a_i.b_j, 0) (the bits
+ * gecco_distance_matrix_f32(squared = 1) writes), g = 0, then `iterations` sweeps f_i = -eps LSE_j((g_j - C_ij) / eps - log M),
+ * g_j = -eps LSE_i((f_i - C_ij) / eps - log N); P_ij = exp((f_i + g_j - C_ij) / eps) / (N M); out[b] = sum_ij P_ij C_ij.  The sweep count
+ * is fixed and nothing is read back.  form 0: auto (resident when it fits), 1: resident (one workgroup per pair and one launch per solve,
+ * clouds and potentials in LDS, N + M <= GECCO_SINKHORN_RESIDENT_MAX_POINTS), 2: streaming (any N, M; 2 * iterations + 2 launches).
+ * f (B, N), g (B, M): the potentials on return; ws (B, N): scratch.  The resident form takes null f, g, ws (f and g are written when
+ * given); the streaming form needs all three.  Gradient rule: the plan P is a constant of the gradient (gecco_sinkhorn_cloud_bwd_f32).
+ * Every reduction has a fixed order, no float atomics: the same bits run to run and in any batch position.  A non-finite coordinate makes
+ * its own pair NaN.  The limit: (160 KiB of LDS - 8 KiB of merge scratch - 256 B) / 20 B per point, rounded down to a multiple of 8. */
+#define GECCO_SINKHORN_RESIDENT_MAX_POINTS 7768
+int gecco_sinkhorn_cloud_f32(const float* a, const float* b, float* f, float* g, float* ws, float* out, int B, int N, int M, float epsilon,
+                             int iterations, int form, void* stream);
+/* every pair of a (S, N, 3) set and a (T, M, 3) set in one launch of the resident form (gecco-jax benchmark.py:21-39
+ * `batched_pairwise_distance` over metrics.py:144-156 `sinkhorn_emd`; BenchmarkCallback uses epsilon = 0.1): out (S, T) row-major,
+ * out[s, t] = the value of gecco_sinkhorn_cloud_f32 (same definition, same bits as its resident form) for (a[s], b[t]); no scratch, no
+ * expanded copies of the clouds.  N + M <= GECCO_SINKHORN_RESIDENT_MAX_POINTS.  The plan is a constant of the gradient (fixed-plan rule
+ * of gecco_sinkhorn_cloud_bwd_f32); fixed-order reductions, no float atomics. */
+int gecco_set_sinkhorn_f32(const float* a, const float* b, float* out, int S, int T, int N, int M, float epsilon, int iterations,
+                           void* stream);
+/* Backward of gecco_sinkhorn_cloud_f32 (gecco-jax metrics.py:144-156) along the FIXED plan P_ij = exp((f_i + g_j - C_ij) / eps) / (N M) of
+ * the saved potentials f (B, N), g (B, M) (same definition of C as above): da[b, i] = gout[b] sum_j P_ij 2 (a_i - b_j),
+ * db[b, j] = gout[b] sum_i P_ij 2 (b_j - a_i).  The plan is a constant of the gradient, as the exact EMD's assignment is; this is also the
+ * envelope gradient of the entropic cost, exact only once the sweeps have converged.  Any N, M (the streaming kernel in gradient mode,
+ * one launch per gradient); every row has one writer and a fixed summation order, no float atomics: bit-reproducible.  da or db (not
+ * both) may be null.  B, N, M >= 1 (B <= 65535). */
+int gecco_sinkhorn_cloud_bwd_f32(const float* a, const float* b, const float* f, const float* g, const float* gout, float* da, float* db,
+                                 int B, int N, int M, float epsilon, void* stream);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
