@@ -217,6 +217,41 @@ def _image_ok(rows: int, K: int, Nout: int, prec: str = "bf16x3") -> bool:
     return bool(lib.gecco_linear_image_ok_f16(rows, K, Nout, 0) if prec == "fp16" else lib.gecco_linear_image_ok(rows, K, Nout, 0))
 
 
+def _w_operand(kind: str, W: Tensor, prec: str, dev, lookup: bool = True, half: bool = False):
+    """(W, wsplit, keep) as an LDS-DMA entry point takes them: the step's ready image of W ("n") or W^T ("t") -> (None, image); else a
+    contiguous / transposed copy and scratch for its image (fp32-sized planes; half: the fp16-sized ones of `gecco_linear_act_keep_h16`),
+    none for "fp32" (which has no images: its lookup is a plain None).  lookup False: the shape takes no ready image (the caller's
+    `_image_ok`).  keep: what the pointers point into.  (A "pair" W1 | W2 goes through hip_ops.linear_pair, which owns its scratch:
+    `_linear_pair_img`; the A-stationary kernels' streams: `_a16_stream`, `_h8_stream`.)"""
+    img = WEIGHT_IMAGES.lookup(kind, W, prec=prec) if lookup else None
+    if img is not None:
+        return None, C.c_void_p(img.data_ptr()), img
+    Wp = W.t().contiguous() if kind == "t" else _f(W)
+    if prec == "fp32":
+        return _ptr(Wp), None, Wp
+    ws = hip_ops._ws((Wp.shape[0] + 127) // 128 * 128 * Wp.shape[1] * (2 if half else 4), dev)
+    return _ptr(Wp), C.c_void_p(ws.data_ptr()), (Wp, ws)
+
+
+def _alpha_ptr(alpha: Tensor | None, kind: int):
+    """GaussianActivation's alpha for the kinds that have one (1 / 2: normalized / raw)."""
+    return _ptr(alpha) if kind in (1, 2) else None
+
+
+def _stats_out(ctx, out, want_stats: bool):
+    """The end of a forward that may also return its output's GroupNorm partial sums, out = (y, stats): they carry no gradient, and
+    with materialize off the backward is not handed a zero-filled (B, T, 2, Nout) tensor for them (one fill launch per call)."""
+    if want_stats:
+        ctx.mark_non_differentiable(out[1])
+        ctx.set_materialize_grads(False)
+    return out
+
+
+def _no_grads(ctx):
+    """(materialize off) only the statistics of such a forward were used: no gradient for any input."""
+    return (None,) * len(ctx.needs_input_grad)
+
+
 # ------------------------------------------------------------------------------------------- Linear
 def _linear_dx_dot(dy: Tensor, W: Tensor, x: Tensor, prec: str | None = None, residual: Tensor | None = None):
     """(dx, gst): dx = dy W and the partial sums {sum dx, sum dx * x} per (sample, row tile, column) that the AdaGN backward of the
@@ -229,10 +264,9 @@ def _linear_dx_dot(dy: Tensor, W: Tensor, x: Tensor, prec: str | None = None, re
     if dy.dtype == torch.float16:   # du stored as halves (`_du16_ok` checked the shape): the fp16 kernel reads its tiles as they are
         dx = _new(B, R, K, like=x)
         gst = _new(B, lib.gecco_linear_row_tiles(R), 2, K, like=x)
-        img = WEIGHT_IMAGES.lookup("t", W, prec="fp16")
-        Wt, ws = (None, img) if img is not None else (W.t().contiguous(), hip_ops._ws((K + 127) // 128 * 128 * Nout * 4, dy.device))
-        _lib.check(lib.gecco_linear_dotstats_a16_f32(hip_ops._ptr16(dy), _ptr(Wt), _ptr(x), _ptr(residual), _ptr(dx), _ptr(gst), B, R, Nout, K,
-                                                     C.c_void_p(ws.data_ptr()), _stream()), "gecco_linear_dotstats_a16_f32")
+        Wt, ws, _keep = _w_operand("t", W, "fp16", dy.device)
+        _lib.check(lib.gecco_linear_dotstats_a16_f32(hip_ops._ptr16(dy), Wt, _ptr(x), _ptr(residual), _ptr(dx), _ptr(gst), B, R, Nout, K,
+                                                     ws, _stream()), "gecco_linear_dotstats_a16_f32")
         return dx, gst
     assert residual is None, "a residual with the partials: fp16 dy only"
     prec = _resolve(prec, R, Nout, K)
@@ -241,14 +275,9 @@ def _linear_dx_dot(dy: Tensor, W: Tensor, x: Tensor, prec: str | None = None, re
         return _linear_dx(dy, W, prec=prec), None
     dx = _new(B, R, K, like=dy)
     gst = _new(B, lib.gecco_linear_row_tiles(R), 2, K, like=dy)
-    img = WEIGHT_IMAGES.lookup("t", W, prec=prec) if prec in ("bf16x3", "fp16") else None
-    if img is not None:
-        Wt, ws = None, img
-    else:
-        Wt = W.t().contiguous()
-        ws = hip_ops._ws((K + 127) // 128 * 128 * Nout * 4, dy.device) if prec != "fp32" else None
-    _lib.check(lib.gecco_linear_dotstats_f32(_ptr(dy), _ptr(Wt), _ptr(x), _ptr(dx), _ptr(gst), B, R, Nout, K, hip_ops.PRECISIONS[prec],
-                                             C.c_void_p(ws.data_ptr()) if ws is not None else None, _stream()), "gecco_linear_dotstats_f32")
+    Wt, ws, _keep = _w_operand("t", W, prec, dy.device)
+    _lib.check(lib.gecco_linear_dotstats_f32(_ptr(dy), Wt, _ptr(x), _ptr(dx), _ptr(gst), B, R, Nout, K, hip_ops.PRECISIONS[prec],
+                                             ws, _stream()), "gecco_linear_dotstats_f32")
     return dx, gst
 
 
@@ -281,9 +310,8 @@ def _linear_dx(dy: Tensor, W: Tensor, residual: Tensor | None = None, prec: str 
         # linear(dy, W^T): the fused LDS-DMA GEMM; the image of W^T comes ready from the step's batched launch when it is
         # there (WeightImages), else from a transposed copy of the (small) weight
         img = WEIGHT_IMAGES.lookup("t", W, prec=prec) if _image_ok(R, Nout, K, prec) else None
-        if img is not None:
-            return hip_ops.linear(dy, None, residual=residual, precision=prec, w_image=img, w_shape=(K, Nout))
-        return hip_ops.linear(dy, W.t().contiguous(), residual=residual, precision=prec)
+        return hip_ops.linear(dy, None if img is not None else W.t().contiguous(), residual=residual, precision=prec, w_image=img,
+                              w_shape=(K, Nout))
     dx = _gemm(dy, W, _new(B, R, K, like=dy), Z=1, zdiv=1, M=B * R, N=K, K=Nout, lda=Nout, ldb=K, ldc=K, b_km=True)  # W read k-major
     return dx if residual is None else dx + residual
 
@@ -378,7 +406,7 @@ _TN_CTR: dict = {}
 
 
 def _tn_counters(dev, tiles: int) -> Tensor:
-    """`tiles` zeroed counters for one weight-gradient launch (gecco_gemm_tn_f16_ex_f32 leaves them zero again): slots of one ring per
+    """`tiles` zeroed counters for one weight-gradient launch (which leaves them zero again): slots of one ring per
     device, handed out round-robin — a slot comes round again thousands of launches later, long after its launch has finished."""
     key = (dev.type, dev.index)
     st = _TN_CTR.get(key)
@@ -392,117 +420,91 @@ def _tn_counters(dev, tiles: int) -> Tensor:
     return st[0][off:off + tiles]
 
 
+def _dw_groups(B: int, tiles: int) -> tuple[int, int]:
+    """(G, group): a weight-gradient launch forms one partial per group of `group` samples, groups sized so that G groups x `tiles`
+    output tiles come to ~_DW_BLOCKS blocks (enough to fill the chip)."""
+    G = min(B, max(1, -(-_DW_BLOCKS // tiles)))
+    group = -(-B // G)
+    return -(-B // group), group
+
+
+def _dw_long_rows(dy: Tensor, x: Tensor):
+    """One long row block (the conditioner's texel matrix) cut into groups of rows for the per-group partials — enough of them that
+    groups x output tiles fill the chip (a 96 x 384 gradient has three tiles)."""
+    R, Nout, K = x.shape[1], dy.shape[2], x.shape[2]
+    cap = max(64, 768 // (-(-Nout // 128) * -(-K // 128)))
+    g = max((d for d in range(1, cap + 1) if R % (32 * d) == 0), default=1)
+    return (dy.view(g, R // g, Nout), x.view(g, R // g, K)) if g > 1 else (dy, x)
+
+
 def _linear_dw_main(dy: Tensor, x: Tensor, want_db: bool = False, pro=None, prec: str | None = None):
     """dW = dy^T x: both operands read k-major (contraction over their rows); partials summed in a fixed order.
-    want_db: also the bias gradient db = column sums of dy -> (dW, db); the split-bf16 kernel forms it from the dy tiles
-    it stages anyway.  pro = (a, o): the linear's input was AdaGN(x) = a x + o (per sample and column) — the split-bf16 kernel
-    applies it while it stages x; elsewhere the normalised tensor is formed first.  prec "fp16": the same kernel with one fp16
-    plane per operand (`gecco_gemm_tn_f16_f32`)."""
+    want_db: also the bias gradient db = column sums of dy -> (dW, db); the tn kernels form it from the dy tiles they stage anyway.
+    pro = (a, o): the linear's input was AdaGN(x) = a x + o (per sample and column) — the tn kernels apply it while they stage x;
+    elsewhere the normalised tensor is formed first.  Three routes: the split-bf16 MFMA kernel with transposed LDS reads
+    (gemm_tn_x3.hip), under prec "fp16" the same kernel with one fp16 plane per operand (either operand may be an fp16 tensor: du of
+    `_du16_ok`, the hidden layer of `_keep_h16`, both with `_y16_ok`), and the general GEMM for every other precision or shape."""
+    lib = _lib.load()
     B, R, K = x.shape
     Nout = dy.shape[2]
     prec = _train_precision() if prec is None else prec
+    a16, b16 = dy.dtype == torch.float16, x.dtype == torch.float16
     assert dy.dtype == torch.float32 or (prec == "fp16" and R % 32 == 0 and Nout % 8 == 0 and K % 4 == 0), "fp16 gradients exist only on the fp16 path"
-    tn_ok = prec in ("bf16x3", "fp16") and R % 32 == 0 and Nout % 4 == 0 and K % 4 == 0
-    if pro is not None and not tn_ok:
+    tn = prec in ("bf16x3", "fp16") and R % 32 == 0 and Nout % 4 == 0 and K % 4 == 0
+    if pro is not None and not tn:
         x, pro = hip_ops.affine_apply(x, pro[0], pro[1]), None
-    if tn_ok and prec == "fp16":
-        if B == 1 and R >= 4096:   # one long row block: groups of rows (see below)
-            cap = max(64, 768 // (-(-Nout // 128) * -(-K // 128)))
-            g = max((d for d in range(1, cap + 1) if R % (32 * d) == 0), default=1)
-            if g > 1 and pro is None:
-                dy, x = dy.view(g, R // g, Nout), x.view(g, R // g, K)
-                B, R = g, R // g
-        tiles = _lib.load().gecco_gemm_tn_f16_tiles(Nout, K)
-        G = min(B, max(1, -(-_DW_BLOCKS // tiles)))
-        group = -(-B // G)
-        G = -(-B // group)
-        parts = _new(G, Nout, K, like=x)
-        cparts = _new(G, Nout, like=x) if want_db else None
-        if os.environ.get("GECCO_TRAIN_DW_REDUCE", "launch") == "kernel":
-            # OPT-IN (measured and lost, profiles/r06_negative_results.txt): the fixed-order sum of the group partials inside the launch —
-            # the last block to finish a tile adds them in group order, the bits `_reduce` gives without its ~100 launches per step.  One
-            # block per tile then reads 24 x 64 KiB behind everybody else (18 CUs busy, 238 idle): 16.75 -> 21.4 ms per step; the separate
-            # reduction spreads the same bytes over the whole chip in ~10 us
-            dW = _new(Nout, K, like=x)
-            db = _new(Nout, like=x) if want_db else None
-            ctr = _tn_counters(x.device, tiles)
-            a16, b16 = dy.dtype == torch.float16, x.dtype == torch.float16
-            assert not (b16 and pro is not None)
-            _lib.check(_lib.load().gecco_gemm_tn_f16_ex_f32(
-                C.c_void_p(dy.data_ptr()), int(a16), C.c_void_p(x.data_ptr()), int(b16), _ptr(pro[0]) if pro is not None else None,
-                _ptr(pro[1]) if pro is not None else None, _ptr(parts), _ptr(cparts), _ptr(dW), _ptr(db), C.c_void_p(ctr.data_ptr()),
-                B, R, Nout, K, group, _stream()), "gecco_gemm_tn_f16_ex_f32")
-            return (dW, db) if want_db else dW
-        if dy.dtype == torch.float16 and x.dtype == torch.float16:   # both operands fp16 tensors (`_y16_ok`): slabs by DMA
-            assert pro is None
-            _lib.check(_lib.load().gecco_gemm_tn_f16_ex_f32(C.c_void_p(dy.data_ptr()), 1, C.c_void_p(x.data_ptr()), 1, None, None, _ptr(parts),
-                                                            _ptr(cparts), None, None, None, B, R, Nout, K, group, _stream()),
-                       "gecco_gemm_tn_f16_ex_f32")
-        elif dy.dtype == torch.float16:   # du of an MLP's backward stored as halves (`_du16_ok`)
-            assert x.dtype == torch.float32
-            _lib.check(_lib.load().gecco_gemm_tn_f16_a16_f32(hip_ops._ptr16(dy), _ptr(x), _ptr(pro[0]) if pro is not None else None,
-                                                             _ptr(pro[1]) if pro is not None else None, _ptr(parts), _ptr(cparts), B, R,
-                                                             Nout, K, group, _stream()), "gecco_gemm_tn_f16_a16_f32")
-        elif x.dtype == torch.float16:   # the fp16 hidden layer of an MLP (_keep_h16): its tiles go to LDS as they are
-            assert pro is None
-            _lib.check(_lib.load().gecco_gemm_tn_f16_b16_f32(_ptr(dy), hip_ops._ptr16(x), _ptr(parts), _ptr(cparts), B, R, Nout, K, group,
-                                                             _stream()), "gecco_gemm_tn_f16_b16_f32")
-        else:
-            _lib.check(_lib.load().gecco_gemm_tn_f16_f32(_ptr(dy), _ptr(x), _ptr(pro[0]) if pro is not None else None,
-                                                         _ptr(pro[1]) if pro is not None else None, _ptr(parts), _ptr(cparts), B, R,
-                                                         Nout, K, group, _stream()), "gecco_gemm_tn_f16_f32")
-        dW = _reduce(parts, Nout * K, G, Nout * K).reshape(Nout, K)
-        return (dW, _reduce(cparts, Nout, G, Nout)) if want_db else dW
-    if pro is not None:
-        tiles = -(-Nout // 128) * -(-K // 128)
-        G = min(B, max(1, -(-_DW_BLOCKS // tiles)))
-        group = -(-B // G)
-        G = -(-B // group)
-        parts = _new(G, Nout, K, like=x)
-        cparts = _new(G, Nout, like=x) if want_db else None
-        _lib.check(_lib.load().gecco_gemm_tn_x3_pro_f32(_ptr(dy), _ptr(x), _ptr(pro[0]), _ptr(pro[1]), _ptr(parts), _ptr(cparts), B, R,
-                                                        Nout, K, group, _stream()), "gecco_gemm_tn_x3_pro_f32")
-        dW = _reduce(parts, Nout * K, G, Nout * K).reshape(Nout, K)
-        return (dW, _reduce(cparts, Nout, G, Nout)) if want_db else dW
-    if B == 1 and R >= 4096:
-        # one long row block (the conditioner's texel matrix): cut it into groups for the per-group partials below — enough of
-        # them that groups x output tiles fill the chip (a 96 x 384 gradient has three tiles)
-        cap = max(64, 768 // (-(-Nout // 128) * -(-K // 128)))
-        g = max((d for d in range(1, cap + 1) if R % (32 * d) == 0), default=1)
-        if g > 1:
-            dy, x = dy.view(g, R // g, Nout), x.view(g, R // g, K)
-            B, R = g, R // g
-    if want_db:
-        if not (prec == "bf16x3" and R % 32 == 0 and Nout % 4 == 0 and K % 4 == 0):
+    if B == 1 and R >= 4096 and pro is None:
+        dy, x = _dw_long_rows(dy, x)
+        B, R = x.shape[0], x.shape[1]
+    if not tn:
+        if want_db:
             return _linear_dw_main(dy, x, prec=prec), _linear_db(dy)
-        tiles = -(-Nout // 128) * -(-K // 128)
-        G = min(B, max(1, -(-_DW_BLOCKS // tiles)))
-        group = -(-B // G)
-        G = -(-B // group)
-        parts, cparts = _new(G, Nout, K, like=x), _new(G, Nout, like=x)
-        _lib.check(_lib.load().gecco_gemm_tn_x3_bias_f32(_ptr(dy), _ptr(x), _ptr(parts), _ptr(cparts), B, R, Nout, K, group,
-                                                         _stream()), "gecco_gemm_tn_x3_bias_f32")
-        return _reduce(parts, Nout * K, G, Nout * K).reshape(Nout, K), _reduce(cparts, Nout, G, Nout)
-    if prec == "bf16x3" and R % 32 == 0 and Nout % 4 == 0 and K % 4 == 0:
-        # split-bf16 MFMA with transposed LDS reads (gemm_tn_x3.hip); one partial per group of samples, groups
-        # sized so that ~1000 blocks fill the chip
-        tiles = -(-Nout // 128) * -(-K // 128)
-        G = min(B, max(1, -(-_DW_BLOCKS // tiles)))
-        group = -(-B // G)
-        G = -(-B // group)
+        G = B
+        parts = _gemm(dy, x, _new(B, Nout, K, like=x), Z=B, zdiv=1, M=Nout, N=K, K=R, lda=Nout, ldb=K, ldc=K,
+                      sA=(R * Nout, 0), sB=(R * K, 0), sC=(Nout * K, 0), a_km=True, b_km=True)
+    else:
+        tiles = lib.gecco_gemm_tn_f16_tiles(Nout, K) if prec == "fp16" else -(-Nout // 128) * -(-K // 128)
+        G, group = _dw_groups(B, tiles)
         parts = _new(G, Nout, K, like=x)
-        _lib.check(_lib.load().gecco_gemm_tn_x3_f32(_ptr(dy), _ptr(x), _ptr(parts), B, R, Nout, K, group, _stream()),
-                   "gecco_gemm_tn_x3_f32")
-        return _reduce(parts, Nout * K, G, Nout * K).reshape(Nout, K)
-    parts = _gemm(dy, x, _new(B, Nout, K, like=x), Z=B, zdiv=1, M=Nout, N=K, K=R, lda=Nout, ldb=K, ldc=K,
-                  sA=(R * Nout, 0), sB=(R * K, 0), sC=(Nout * K, 0), a_km=True, b_km=True)
-    return _reduce(parts, Nout * K, B, Nout * K).reshape(Nout, K)
+        cparts = _new(G, Nout, like=x) if want_db else None
+        pa, po = (_ptr(pro[0]), _ptr(pro[1])) if pro is not None else (None, None)
+        if prec == "fp16":
+            assert not (b16 and pro is not None)
+            dW = db = ctr = None
+            if os.environ.get("GECCO_TRAIN_DW_REDUCE", "launch") == "kernel":
+                # OPT-IN (measured and lost, profiles/r06_negative_results.txt): the fixed-order sum of the group partials inside the launch —
+                # the last block to finish a tile adds them in group order, the bits `_reduce` gives without its ~100 launches per step.  One
+                # block per tile then reads 24 x 64 KiB behind everybody else (18 CUs busy, 238 idle): 16.75 -> 21.4 ms per step; the separate
+                # reduction spreads the same bytes over the whole chip in ~10 us
+                dW = _new(Nout, K, like=x)
+                db = _new(Nout, like=x) if want_db else None
+                ctr = C.c_void_p(_tn_counters(x.device, tiles).data_ptr())
+            # (one entry point for fp32 / fp16 tensors on either side: both fp16 takes the slabs by DMA)
+            _lib.check(lib.gecco_gemm_tn_f16_ex_f32(hip_ops._ptr_io(dy), int(a16), hip_ops._ptr_io(x), int(b16), pa, po, _ptr(parts), _ptr(cparts),
+                                                    _ptr(dW), _ptr(db), ctr, B, R, Nout, K, group, _stream()), "gecco_gemm_tn_f16_ex_f32")
+            if ctr is not None:
+                return (dW, db) if want_db else dW
+        else:
+            _lib.check(lib.gecco_gemm_tn_x3_pro_f32(_ptr(dy), _ptr(x), pa, po, _ptr(parts), _ptr(cparts), B, R, Nout, K, group, _stream()),
+                       "gecco_gemm_tn_x3_pro_f32")
+    dW = _reduce(parts, Nout * K, G, Nout * K).reshape(Nout, K)
+    return (dW, _reduce(cparts, Nout, G, Nout)) if want_db else dW
 
 
 def _linear_db(dy: Tensor) -> Tensor:
     st = hip_ops.col_stats(dy)  # (B, T, 2, Nout): [..., 0, :] = column sums
     Nout = dy.shape[2]
     return _reduce(st, Nout, st.shape[0] * st.shape[1], 2 * Nout)
+
+
+def _wgrads(dy: Tensor, x: Tensor, W: Tensor, b, need_w: bool, need_b: bool, prec: str, pro=None, side_ok: bool = False):
+    """(dW, db) of y = x' W^T + b from dy, each None unless needed: both from one weight-gradient launch, else whichever is wanted.
+    W, b: the parameters they are for; pro, side_ok: `_linear_dw`'s."""
+    if need_w and need_b:
+        return _linear_dw(dy, x, want_db=True, pro=pro, leaf=W, prec=prec, side_ok=side_ok, bias=b)
+    if need_w:
+        return _linear_dw(dy, x, pro=pro, leaf=W, prec=prec, side_ok=side_ok), None
+    return None, (_linear_db(dy if dy.dtype == torch.float32 else dy.float()) if need_b else None)
 
 
 class LinearFn(torch.autograd.Function):
@@ -520,43 +522,29 @@ class LinearFn(torch.autograd.Function):
         ctx.inproj = getattr(W, "_gecco_inproj", None)   # a third of a packed in_proj: (W, b) packed (`InProjSplitFn`)
         prec = ctx.prec = _lin_precision()
         res = None if residual is None else _f(residual)
-        if x.dtype == torch.float16:   # an fp16 tensor of an `_io16_ok` layer (the unpool attention's output): fp16 A tiles, fp32 result
-            img = WEIGHT_IMAGES.lookup("n", W, prec="fp16")
-            out = hip_ops.linear_f16io(x, None if img is not None else W, b, residual=res, want_stats=want_stats, w_image=img,
-                                       w_shape=tuple(W.shape))
-            if want_stats:
-                ctx.mark_non_differentiable(out[1])
-                ctx.set_materialize_grads(False)
-            return out
-        img = WEIGHT_IMAGES.lookup("n", W, prec=prec) if _image_ok(x.shape[1], W.shape[1], W.shape[0], prec) else None
-        kw = dict(precision=prec, w_image=img, w_shape=tuple(W.shape)) if img is not None else dict(precision=prec)
-        if want_stats:
-            y, st = hip_ops.linear(x, None if img is not None else W, b, residual=res, want_stats=True, **kw)
-            ctx.mark_non_differentiable(st)
-            ctx.set_materialize_grads(False)   # else backward is handed a zero-filled (B, T, 2, Nout) tensor for st: one fill launch per call
-            return y, st
-        return hip_ops.linear(x, None if img is not None else W, b, residual=res, **kw)
+        # (x an fp16 tensor of an `_io16_ok` layer — the unpool attention's output: fp16 A tiles, fp32 result)
+        return _stats_out(ctx, _linear_img(x, W, b, res, want_stats, prec), want_stats)
 
     @staticmethod
     def backward(ctx, dy, _dstats=None):
-        if dy is None:   # (materialize off) only the statistics were used: they carry no gradient
-            return (None,) * len(ctx.needs_input_grad)
+        if dy is None:
+            return _no_grads(ctx)
         x, W = ctx.saved_tensors
         dy = _f(dy)
         prec = ctx.prec
         # (an fp16 input's gradient leaves as an fp16 tensor: its consumer — the attention backward — reads it as an fp16 operand)
         dx = _linear_dx(dy, W, prec=prec, out_f16=x.dtype == torch.float16) if ctx.needs_input_grad[0] else None
-        dW = db = None
         side_ok = ctx.inproj is not None and _inproj_side_ok(*ctx.inproj)
-        if ctx.has_bias and ctx.needs_input_grad[2] and ctx.needs_input_grad[1]:
-            dW, db = _linear_dw(dy, x, want_db=True, leaf=W, prec=prec, side_ok=side_ok, bias=ctx.b)
-        elif ctx.needs_input_grad[1]:
-            dW = _linear_dw(dy, x, leaf=W, prec=prec, side_ok=side_ok)
-        elif ctx.has_bias and ctx.needs_input_grad[2]:
-            db = _linear_db(dy)
+        dW, db = _wgrads(dy, x, W, ctx.b, ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2], prec, side_ok=side_ok)
         n = len(ctx.needs_input_grad)        # 3 .. 5: called without / with a residual (and the statistics flag)
         dres = dy if n > 3 and ctx.needs_input_grad[3] else None
         return (dx, dW, db, dres, None)[:n]
+
+
+def _linear_pair_img(x: Tensor, W1: Tensor, b1, W2: Tensor, b2, pro, prec: str, lookup: bool = True):
+    """hip_ops.linear_pair with the step's ready image of W1 | W2 when there is one (lookup False: the shape takes none)."""
+    img = WEIGHT_IMAGES.lookup("pair", W1, W2, prec=prec) if lookup else None
+    return hip_ops.linear_pair(x, W1, b1, W2 if img is not None else _f(W2), b2, pro=pro, precision=prec, w_image=img)
 
 
 class LinearPairFn(torch.autograd.Function):
@@ -571,12 +559,8 @@ class LinearPairFn(torch.autograd.Function):
         ctx.bias = (b1 is not None, b2 is not None)
         ctx.b = (b1, b2)
         prec = ctx.prec = _lin_precision()
-        img = None
-        if W1.shape[0] % 128 == 0 and W2.shape[0] % 128 == 0 and _image_ok(x.shape[1], W1.shape[1], W1.shape[0] + W2.shape[0], prec):
-            img = WEIGHT_IMAGES.lookup("pair", W1, W2, prec=prec)
-        if img is not None:
-            return hip_ops.linear_pair(x, W1, b1, W2, b2, precision=prec, w_image=img)
-        return hip_ops.linear_pair(x, W1, b1, _f(W2), b2, precision=prec)
+        ok = W1.shape[0] % 128 == 0 and W2.shape[0] % 128 == 0 and _image_ok(x.shape[1], W1.shape[1], W1.shape[0] + W2.shape[0], prec)
+        return _linear_pair_img(x, W1, b1, W2, b2, None, prec, ok)
 
     @staticmethod
     def backward(ctx, d1, d2):
@@ -585,13 +569,8 @@ class LinearPairFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         prec = ctx.prec
         dx = _linear_dx(d2, W2, residual=_linear_dx(d1, W1, prec=prec), prec=prec) if need[0] else None
-        out = [dx]
-        for d, has_b, iw, Wl, bl in ((d1, ctx.bias[0], 1, W1, ctx.b[0]), (d2, ctx.bias[1], 3, W2, ctx.b[1])):
-            if need[iw] and has_b and need[iw + 1]:
-                out += list(_linear_dw(d, x, want_db=True, leaf=Wl, prec=prec, bias=bl))
-            else:
-                out += [_linear_dw(d, x, leaf=Wl, prec=prec) if need[iw] else None, _linear_db(d) if has_b and need[iw + 1] else None]
-        return tuple(out)
+        return (dx, *_wgrads(d1, x, W1, ctx.b[0], need[1], ctx.bias[0] and need[2], prec),
+                *_wgrads(d2, x, W2, ctx.b[1], need[3], ctx.bias[1] and need[4], prec))
 
 
 # ------------------------------------------------------------------------------------------- AdaGN / GroupNorm
@@ -698,7 +677,7 @@ class AdaGNPairFn(torch.autograd.Function):
     """(KV, q, x) = (AdaGN(x) Wkv^T, AdaGN(x) Wq^T + bq, x): broadcast_norm and the two projections of its output
     (models/set_transformer.py:161-162 -> :49, :112) as ONE Function.  AdaGN(x) is never materialised: the pair GEMM applies
     a x + o on its A fragments (as the inference path does), the weight-gradient kernel applies it while staging x
-    (`gecco_gemm_tn_x3_pro_f32`), and the backward continues into the AdaGN backward with the two dX products' sum.  The third
+    (`_linear_dw_main(pro=)`), and the backward continues into the AdaGN backward with the two dX products' sum.  The third
     output hands x to the skip connection; the gradient returning through it is added inside the AdaGN backward kernel."""
 
     @staticmethod
@@ -710,37 +689,26 @@ class AdaGNPairFn(torch.autograd.Function):
         ctx.inproj2, ctx.b2 = getattr(W2, "_gecco_inproj", None), b2
         B, R, K = x.shape
         N1, N2 = W1.shape[0], W2.shape[0]
+        y16 = None
         if io16:   # (`_io16_ok`) K | V and q as fp16 tensors: the same A-stationary kernel, its fp16 row-major epilogue
             ws, ready = _a16_stream("pair", W1, W2, dev=x.device)
             y16 = torch.empty(B, R, K, device=x.device, dtype=torch.float16) if _y16_ok(R, K, N1) and _y16_ok(R, K, N2) else None
             KV, q = hip_ops.linear_kvq_f16(x, (a, o), W1, None, _f(W2), b2, lo=(0, 0), head_dim=0, wsplit=ws, image_ready=ready, y16=y16)
-            ctx.save_for_backward(x, stats, t2, sw, sb, a, o, W1, W2, bw, y16 if y16 is not None else x.new_empty(0))
-            ctx.G, ctx.eps, ctx.has_b2, ctx.t_shape = G, eps, b2 is not None, tuple(t.shape)
-            return KV, q, x
-        if _a16_ok(prec, R, K, N1 + N2) and N1 % 64 == 0 and N2 % 64 == 0:
+        elif _a16_ok(prec, R, K, N1 + N2) and N1 % 64 == 0 and N2 % 64 == 0:
             KV, q = _new(B, R, N1, like=x), _new(B, R, N2, like=x)
             ws, ready = _a16_stream("pair", W1, W2, dev=x.device)
             _lib.check(_lib.load().gecco_linear_astat16_f32(_ptr(x), _ptr(a), _ptr(o), None if ready else _ptr(_f(W1)), None, N1, _ptr(KV),
                                                             None if ready else _ptr(_f(W2)), _ptr(b2), N2, _ptr(q), None, 0, B, R, K,
                                                             C.c_void_p(ws.data_ptr()), _stream()), "gecco_linear_astat16_f32")
-            ctx.save_for_backward(x, stats, t2, sw, sb, a, o, W1, W2, bw, x.new_empty(0))
-            ctx.G, ctx.eps, ctx.has_b2, ctx.t_shape = G, eps, b2 is not None, tuple(t.shape)
-            return KV, q, x
-        if _h8_ok(prec, R, K, N1 + N2) and N1 % 64 == 0 and N2 % 64 == 0:
+        elif _h8_ok(prec, R, K, N1 + N2) and N1 % 64 == 0 and N2 % 64 == 0:
             KV, q = _new(B, R, N1, like=x), _new(B, R, N2, like=x)
             ws, ready = _h8_stream("pair", W1, W2, dev=x.device)
             _lib.check(_lib.load().gecco_linear_h8_train_f32(_ptr(x), _ptr(a), _ptr(o), None if ready else _ptr(_f(W1)), None, N1, _ptr(KV),
                                                              None if ready else _ptr(_f(W2)), _ptr(b2), N2, _ptr(q), None, 0, None, B, R, K,
                                                              C.c_void_p(ws.data_ptr()), _stream()), "gecco_linear_h8_train_f32")
-            ctx.save_for_backward(x, stats, t2, sw, sb, a, o, W1, W2, bw, x.new_empty(0))
-            ctx.G, ctx.eps, ctx.has_b2, ctx.t_shape = G, eps, b2 is not None, tuple(t.shape)
-            return KV, q, x
-        img = WEIGHT_IMAGES.lookup("pair", W1, W2, prec=prec)
-        if img is not None:
-            KV, q = hip_ops.linear_pair(x, W1, None, W2, b2, pro=(a, o), precision=prec, w_image=img)
         else:
-            KV, q = hip_ops.linear_pair(x, W1, None, _f(W2), b2, pro=(a, o), precision=prec)
-        ctx.save_for_backward(x, stats, t2, sw, sb, a, o, W1, W2, bw, x.new_empty(0))
+            KV, q = _linear_pair_img(x, W1, None, W2, b2, (a, o), prec)
+        ctx.save_for_backward(x, stats, t2, sw, sb, a, o, W1, W2, bw, y16 if y16 is not None else x.new_empty(0))
         ctx.G, ctx.eps, ctx.has_b2, ctx.t_shape = G, eps, b2 is not None, tuple(t.shape)
         return KV, q, x
 
@@ -763,14 +731,8 @@ class AdaGNPairFn(torch.autograd.Function):
         # X of the two weight gradients: the fp16 operand the forward stored (both operands fp16: the DMA form), else x with the AdaGN apply
         xw, prow = (y16, None) if (y16.numel() and dKV.dtype == torch.float16 and dq.dtype == torch.float16) else (x, (a, o))
         dW1 = _linear_dw(dKV, xw, pro=prow, leaf=W1, prec=prec) if need[9] else None
-        dW2 = db2 = None
         side2 = ctx.inproj2 is not None and _inproj_side_ok(*ctx.inproj2)
-        if need[10] and ctx.has_b2 and need[11]:
-            dW2, db2 = _linear_dw(dq, xw, want_db=True, pro=prow, leaf=W2, prec=prec, side_ok=side2, bias=ctx.b2)
-        elif need[10]:
-            dW2 = _linear_dw(dq, xw, pro=prow, leaf=W2, prec=prec, side_ok=side2)
-        elif ctx.has_b2 and need[11]:
-            db2 = _linear_db(dq.float() if dq.dtype != torch.float32 else dq)
+        dW2, db2 = _wgrads(dq, xw, W2, ctx.b2, need[10], ctx.has_b2 and need[11], prec, pro=prow, side_ok=side2)
         dx, dsw, dsb, dbw, dbb, dt = _adagn_backward(x, stats, t2, sw, sb, dY, dskip, ctx.G, ctx.eps, True, gst=gst, bw=bw if need[1] else None)
         return dx, (dt.reshape(ctx.t_shape) if dt is not None else None), dsw, dsb, dbw, dbb, None, None, None, dW1, dW2, db2, None
 
@@ -800,30 +762,23 @@ class AdaGNMlpFn(torch.autograd.Function):
             u, h = _new(B, R, N0, like=x), _new(B, R, N0, like=x)
             ws, ready = _h8_stream("n", W0, dev=x.device)
             _lib.check(lib.gecco_linear_h8_train_f32(_ptr(x), _ptr(a), _ptr(o), None if ready else _ptr(_f(W0)), _ptr(b0), N0, _ptr(h),
-                                                     None, None, 0, None, _ptr(alpha) if kind in (1, 2) else None, kind, _ptr(u), B, R, K0,
+                                                     None, None, 0, None, _alpha_ptr(alpha, kind), kind, _ptr(u), B, R, K0,
                                                      C.c_void_p(ws.data_ptr()), _stream()), "gecco_linear_h8_train_f32")
         else:
             u, h = _new(B, R, N0, like=x), _new(B, R, N0, like=x)
-            img = WEIGHT_IMAGES.lookup("n", W0, prec=prec)
-            Wp, ws = (None, img) if img is not None else (_f(W0), hip_ops._ws((N0 + 127) // 128 * 128 * K0 * 4, x.device))
-            _lib.check(lib.gecco_linear_act_keep_pro_f32(_ptr(x), _ptr(Wp), _ptr(b0), _ptr(a), _ptr(o), _ptr(alpha) if kind in (1, 2) else None,
-                                                         kind, _ptr(u), _ptr(h), B, R, K0, N0, hip_ops.PRECISIONS[prec],
-                                                         C.c_void_p(ws.data_ptr()), _stream()),
-                       "gecco_linear_act_keep_pro_f32")
+            Wp, ws, _keep = _w_operand("n", W0, prec, x.device)
+            _lib.check(lib.gecco_linear_act_keep_pro_f32(_ptr(x), Wp, _ptr(b0), _ptr(a), _ptr(o), _alpha_ptr(alpha, kind), kind, _ptr(u), _ptr(h),
+                                                         B, R, K0, N0, hip_ops.PRECISIONS[prec], ws, _stream()), "gecco_linear_act_keep_pro_f32")
         ctx.save_for_backward(x, stats, t2, sw, sb, a, o, u, h, alpha if alpha is not None else x.new_empty(0), W0, W2, bw,
                               y16 if y16 is not None else x.new_empty(0))
         ctx.G, ctx.eps, ctx.kind, ctx.bias, ctx.t_shape = G, eps, kind, (b0 is not None, b2 is not None), tuple(t.shape)
         ctx.b = (b0, b2)
-        out = _linear_fwd_h16(h, W2, b2, x, want_stats) if h16 else _linear_fwd(h, W2, b2, x, want_stats, prec)
-        if want_stats:
-            ctx.mark_non_differentiable(out[1])
-            ctx.set_materialize_grads(False)   # no zero-filled gradient tensor for the statistics
-        return out
+        return _stats_out(ctx, _linear_fwd(h, W2, b2, x, want_stats, prec), want_stats)
 
     @staticmethod
     def backward(ctx, dout, _dstats=None):
-        if dout is None:   # (materialize off) only the statistics were used: they carry no gradient
-            return (None,) * len(ctx.needs_input_grad)
+        if dout is None:
+            return _no_grads(ctx)
         x, stats, t2, sw, sb, a, o, u, h, alpha, W0, W2, bw, y16 = ctx.saved_tensors
         need = ctx.needs_input_grad
         dout = _f(dout)
@@ -832,16 +787,10 @@ class AdaGNMlpFn(torch.autograd.Function):
         du16 = (ctx.kind in (1, 2, 3) and need[0] and (need[9] or not (ctx.bias[0] and need[10]))
                 and _du16_ok(prec, x.shape[1], W2.shape[0], W2.shape[1], x.shape[2]))
         du, dalpha = _act_linear_dx(dout, u, h, alpha, W2, ctx.kind, need[11], prec, du16=du16)
-
-        def wgrads(g, act_in, has_b, iw, ib, Wl, bl, pro=None):
-            if has_b and need[ib] and need[iw]:
-                return _linear_dw(g, act_in, want_db=True, pro=pro, leaf=Wl, prec=prec, bias=bl)
-            return (_linear_dw(g, act_in, pro=pro, leaf=Wl, prec=prec) if need[iw] else None), (_linear_db(g) if has_b and need[ib] else None)
-        dW2, db2 = wgrads(dout, h, ctx.bias[1], 12, 13, W2, ctx.b[1])
-        if du.dtype == torch.float16 and y16.numel():   # both operands as fp16 images: the DMA form of the weight-gradient kernel
-            dW0, db0 = wgrads(du, y16, ctx.bias[0], 9, 10, W0, ctx.b[0])
-        else:
-            dW0, db0 = wgrads(du, x, ctx.bias[0], 9, 10, W0, ctx.b[0], pro=(a, o))
+        dW2, db2 = _wgrads(dout, h, W2, ctx.b[1], need[12], ctx.bias[1] and need[13], prec)
+        # (du and the y16 the forward kept: both operands as fp16 images, the DMA form of the weight-gradient kernel)
+        xw, prow = (y16, None) if du.dtype == torch.float16 and y16.numel() else (x, (a, o))
+        dW0, db0 = _wgrads(du, xw, W0, ctx.b[0], need[9], ctx.bias[0] and need[10], prec, pro=prow)
         dY, gst = _linear_dx_dot(du, W0, x, prec=prec)
         dx, dsw, dsb, dbw, dbb, dt = _adagn_backward(x, stats, t2, sw, sb, dY, dout, ctx.G, ctx.eps, True, gst=gst, bw=bw if need[1] else None)
         return dx, (dt.reshape(ctx.t_shape) if dt is not None else None), dsw, dsb, dbw, dbb, None, None, None, dW0, db0, dalpha, dW2, db2, None, None
@@ -902,11 +851,11 @@ def _act_linear_dx(dy: Tensor, u: Tensor, h: Tensor, alpha: Tensor, W: Tensor, k
         parts = _new(B * R // 128, like=u) if kind in (1, 2) else None
         ws, ready = _a16_stream("t", W, dev=u.device)
         if du16:
-            _lib.check(lib.gecco_linear_astat16_actbwd_h16(_ptr(dy), None if ready else _ptr(_f(W)), _ptr(u), _ptr(alpha) if kind in (1, 2) else None,
-                                                           kind, C.c_void_p(du.data_ptr()), _ptr(parts), B, R, Nout, K, C.c_void_p(ws.data_ptr()),
+            _lib.check(lib.gecco_linear_astat16_actbwd_h16(_ptr(dy), None if ready else _ptr(_f(W)), _ptr(u), _alpha_ptr(alpha, kind), kind,
+                                                           C.c_void_p(du.data_ptr()), _ptr(parts), B, R, Nout, K, C.c_void_p(ws.data_ptr()),
                                                            _stream()), "gecco_linear_astat16_actbwd_h16")
         else:
-            _lib.check(lib.gecco_linear_astat16_actbwd(_ptr(dy), None if ready else _ptr(_f(W)), _ptr(u), _ptr(alpha) if kind in (1, 2) else None, kind,
+            _lib.check(lib.gecco_linear_astat16_actbwd(_ptr(dy), None if ready else _ptr(_f(W)), _ptr(u), _alpha_ptr(alpha, kind), kind,
                                                        _ptr(du), _ptr(parts), B, R, Nout, K, C.c_void_p(ws.data_ptr()), _stream()),
                        "gecco_linear_astat16_actbwd")
         if kind in (1, 2) and want_alpha:
@@ -917,16 +866,9 @@ def _act_linear_dx(dy: Tensor, u: Tensor, h: Tensor, alpha: Tensor, W: Tensor, k
         du = torch.empty_like(u)
         nt = lib.gecco_linear_actbwd_tiles(B, R, K)
         parts = torch.zeros(nt, device=u.device, dtype=torch.float32) if kind in (1, 2) else None
-        img = WEIGHT_IMAGES.lookup("t", W, prec=prec) if prec in ("bf16x3", "fp16") else None
-        if img is not None:
-            Wt, ws = None, img
-        else:
-            Wt = W.t().contiguous()
-            ws = hip_ops._ws((K + 127) // 128 * 128 * Nout * 4, u.device) if prec != "fp32" else None
-        _lib.check(lib.gecco_linear_actbwd_f32(_ptr(dy), _ptr(Wt), _ptr(u), _ptr(alpha) if kind in (1, 2) else None, kind, None,
-                                               _ptr(du), _ptr(parts), B, R, Nout, K, hip_ops.PRECISIONS[prec],
-                                               C.c_void_p(ws.data_ptr()) if ws is not None else None, _stream()),
-                   "gecco_linear_actbwd_f32")
+        Wt, ws, _keep = _w_operand("t", W, prec, u.device)
+        _lib.check(lib.gecco_linear_actbwd_f32(_ptr(dy), Wt, _ptr(u), _alpha_ptr(alpha, kind), kind, None, _ptr(du), _ptr(parts), B, R, Nout, K,
+                                               hip_ops.PRECISIONS[prec], ws, _stream()), "gecco_linear_actbwd_f32")
         if kind in (1, 2) and want_alpha:
             dalpha = _reduce(parts, 1, nt, 1).reshape(alpha.shape)
         return du, dalpha
@@ -955,13 +897,20 @@ def _act_forward(u: Tensor, alpha: Tensor | None, kind: int) -> Tensor:
     return h
 
 
-def _linear_fwd(x: Tensor, W: Tensor, b, res, want_stats: bool, prec: str | None = None):
-    """hip_ops.linear in the training precision (prec: the Function's `_lin_precision()`), with the step's ready weight image when
-    there is one."""
-    prec = _resolve(prec, x.shape[1], W.shape[1], W.shape[0])
+def _linear_img(x: Tensor, W: Tensor, b, res, want_stats: bool, prec: str):
+    """x W^T + b (+ res; with want_stats -> (y, stats)) in `prec` with the step's ready image of W when there is one.  x an fp16 tensor
+    (an `_io16_ok` layer's attention output, an MLP's hidden layer of `_keep_h16`): fp16 A tiles, fp32 output."""
+    if x.dtype == torch.float16:
+        return hip_ops.linear_f16io(x, W, b, residual=res, want_stats=want_stats, w_image=WEIGHT_IMAGES.lookup("n", W, prec="fp16"))
     img = WEIGHT_IMAGES.lookup("n", W, prec=prec) if _image_ok(x.shape[1], W.shape[1], W.shape[0], prec) else None
-    kw = dict(precision=prec, w_image=img, w_shape=tuple(W.shape)) if img is not None else dict(precision=prec)
-    return hip_ops.linear(x, None if img is not None else W, b, residual=res, want_stats=want_stats, **kw)
+    return hip_ops.linear(x, W, b, residual=res, want_stats=want_stats, precision=prec, w_image=img)
+
+
+def _linear_fwd(x: Tensor, W: Tensor, b, res, want_stats: bool, prec: str | None = None):
+    """`_linear_img` in the training precision: prec is the Function's `_lin_precision()`, resolved for this shape (`_resolve`)."""
+    if x.dtype != torch.float16:
+        prec = _resolve(prec, x.shape[1], W.shape[1], W.shape[0])
+    return _linear_img(x, W, b, res, want_stats, prec)
 
 
 def _a16_ok(prec: str, R: int, K: int, Nout: int) -> bool:
@@ -1031,26 +980,18 @@ def _keep_h16(x: Tensor, W0: Tensor, b0, pro, alpha, kind: int, want_y16: bool =
         ws, ready = _a16_stream("n", W0, dev=x.device)
         y16 = torch.empty(B, R, K0, device=x.device, dtype=torch.float16) if want_y16 else None
         _lib.check(lib.gecco_linear_astat16_keep_y16(_ptr(x), _ptr(pro[0]) if pro else None, _ptr(pro[1]) if pro else None,
-                                                     None if ready else _ptr(_f(W0)), _ptr(b0), _ptr(alpha) if kind in (1, 2) else None, kind,
+                                                     None if ready else _ptr(_f(W0)), _ptr(b0), _alpha_ptr(alpha, kind), kind,
                                                      _ptr(u), C.c_void_p(h.data_ptr()), C.c_void_p(y16.data_ptr()) if want_y16 else None,
                                                      B, R, K0, N0, C.c_void_p(ws.data_ptr()), _stream()),
                    "gecco_linear_astat16_keep_y16")
         return (u, h, y16) if want_y16 else (u, h)
     if want_y16:
         return (*_keep_h16(x, W0, b0, pro, alpha, kind), None)
-    img = WEIGHT_IMAGES.lookup("n", W0, prec="fp16")
-    Wp, ws = (None, img) if img is not None else (_f(W0), hip_ops._ws((N0 + 127) // 128 * 128 * K0 * 2, x.device))
-    _lib.check(lib.gecco_linear_act_keep_h16(_ptr(x), _ptr(Wp), _ptr(b0), _ptr(pro[0]) if pro else None, _ptr(pro[1]) if pro else None,
-                                             _ptr(alpha) if kind in (1, 2) else None, kind, _ptr(u), C.c_void_p(h.data_ptr()), B, R, K0, N0,
-                                             C.c_void_p(ws.data_ptr()), _stream()), "gecco_linear_act_keep_h16")
+    Wp, ws, _keep = _w_operand("n", W0, "fp16", x.device, half=True)
+    _lib.check(lib.gecco_linear_act_keep_h16(_ptr(x), Wp, _ptr(b0), _ptr(pro[0]) if pro else None, _ptr(pro[1]) if pro else None,
+                                             _alpha_ptr(alpha, kind), kind, _ptr(u), C.c_void_p(h.data_ptr()), B, R, K0, N0, ws, _stream()),
+               "gecco_linear_act_keep_h16")
     return u, h
-
-
-def _linear_fwd_h16(h: Tensor, W: Tensor, b, res, want_stats: bool):
-    """The second linear of such an MLP: fp16 A tensor, fp32 output (+ residual, + statistics)."""
-    img = WEIGHT_IMAGES.lookup("n", W, prec="fp16")
-    return hip_ops.linear_f16io(h, None if img is not None else W, b, residual=res, want_stats=want_stats, w_image=img,
-                                w_shape=tuple(W.shape))
 
 
 class LinearActLinearFn(torch.autograd.Function):
@@ -1073,44 +1014,28 @@ class LinearActLinearFn(torch.autograd.Function):
             u, h = _keep_h16(x, W0, b0, None, alpha, kind)
         elif keep:
             u, h = _new(B, R, N0, like=x), _new(B, R, N0, like=x)
-            img = WEIGHT_IMAGES.lookup("n", W0, prec=prec) if prec in ("bf16x3", "fp16") and _image_ok(R, K0, N0, prec) else None
-            if img is not None:
-                Wp, ws = None, img
-            else:
-                Wp = _f(W0)
-                ws = hip_ops._ws((N0 + 127) // 128 * 128 * K0 * 4, x.device) if prec != "fp32" else None
-            _lib.check(lib.gecco_linear_act_keep_f32(_ptr(x), _ptr(Wp), _ptr(b0), _ptr(alpha) if kind in (1, 2) else None, kind,
-                                                     _ptr(u), _ptr(h), B, R, K0, N0, hip_ops.PRECISIONS[prec],
-                                                     C.c_void_p(ws.data_ptr()) if ws is not None else None, _stream()),
-                       "gecco_linear_act_keep_f32")
+            Wp, ws, _keep = _w_operand("n", W0, prec, x.device, lookup=prec != "fp32" and _image_ok(R, K0, N0, prec))
+            _lib.check(lib.gecco_linear_act_keep_f32(_ptr(x), Wp, _ptr(b0), _alpha_ptr(alpha, kind), kind, _ptr(u), _ptr(h), B, R, K0, N0,
+                                                     hip_ops.PRECISIONS[prec], ws, _stream()), "gecco_linear_act_keep_f32")
         else:
             u = _linear_fwd(x, W0, b0, None, False, prec)
             h = _act_forward(u, alpha, kind)
         ctx.save_for_backward(x, u, h, alpha if alpha is not None else x.new_empty(0), W0, W2)
         ctx.kind, ctx.bias, ctx.b = kind, (b0 is not None, b2 is not None), (b0, b2)
         res = None if residual is None else _f(residual)
-        out = _linear_fwd_h16(h, W2, b2, res, want_stats) if h16 else _linear_fwd(h, W2, b2, res, want_stats, prec)
-        if want_stats:
-            ctx.mark_non_differentiable(out[1])
-            ctx.set_materialize_grads(False)   # no zero-filled gradient tensor for the statistics
-        return out
+        return _stats_out(ctx, _linear_fwd(h, W2, b2, res, want_stats, prec), want_stats)
 
     @staticmethod
     def backward(ctx, dy, _dstats=None):
-        if dy is None:   # (materialize off) only the statistics were used: they carry no gradient
-            return (None,) * len(ctx.needs_input_grad)
+        if dy is None:
+            return _no_grads(ctx)
         x, u, h, alpha, W0, W2 = ctx.saved_tensors
         need = ctx.needs_input_grad
         dy = _f(dy)
         prec = ctx.prec
         du, dalpha = _act_linear_dx(dy, u, h, alpha, W2, ctx.kind, need[3], prec)
-
-        def wgrads(g, a, has_b, iw, ib, Wl, bl):
-            if has_b and need[ib] and need[iw]:
-                return _linear_dw(g, a, want_db=True, leaf=Wl, prec=prec, bias=bl)
-            return (_linear_dw(g, a, leaf=Wl, prec=prec) if need[iw] else None), (_linear_db(g) if has_b and need[ib] else None)
-        dW2, db2 = wgrads(dy, h, ctx.bias[1], 4, 5, W2, ctx.b[1])
-        dW0, db0 = wgrads(du, x, ctx.bias[0], 1, 2, W0, ctx.b[0])
+        dW2, db2 = _wgrads(dy, h, W2, ctx.b[1], need[4], ctx.bias[1] and need[5], prec)
+        dW0, db0 = _wgrads(du, x, W0, ctx.b[0], need[1], ctx.bias[0] and need[2], prec)
         dx = _linear_dx(du, W0, prec=prec) if need[0] else None
         return dx, dW0, db0, dalpha, dW2, db2, (dy if need[6] else None), None, None
 
@@ -1130,27 +1055,17 @@ class ActLinearFn(torch.autograd.Function):
         ctx.kind, ctx.has_bias, ctx.b = kind, b is not None, b
         prec = ctx.prec = _lin_precision()
         res = None if residual is None else _f(residual)
-        out = _linear_fwd(h, W, b, res, want_stats, prec)
-        if want_stats:
-            ctx.mark_non_differentiable(out[1])
-            ctx.set_materialize_grads(False)   # no zero-filled gradient tensor for the statistics
-        return out
+        return _stats_out(ctx, _linear_fwd(h, W, b, res, want_stats, prec), want_stats)
 
     @staticmethod
     def backward(ctx, dy, _dstats=None):
-        if dy is None:   # (materialize off) only the statistics were used: they carry no gradient
-            return (None,) * len(ctx.needs_input_grad)
+        if dy is None:
+            return _no_grads(ctx)
         u, h, alpha, W = ctx.saved_tensors
         dy = _f(dy)
         prec = ctx.prec
         du, dalpha = _act_linear_dx(dy, u, h, alpha, W, ctx.kind, ctx.needs_input_grad[1], prec)
-        dW = db = None
-        if ctx.has_bias and ctx.needs_input_grad[3] and ctx.needs_input_grad[2]:
-            dW, db = _linear_dw(dy, h, want_db=True, leaf=W, prec=prec, bias=ctx.b)
-        elif ctx.needs_input_grad[2]:
-            dW = _linear_dw(dy, h, leaf=W, prec=prec)
-        elif ctx.has_bias and ctx.needs_input_grad[3]:
-            db = _linear_db(dy)
+        dW, db = _wgrads(dy, h, W, ctx.b, ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3], prec)
         dres = dy if ctx.needs_input_grad[4] else None
         return du, dalpha, dW, db, dres, None, None
 
@@ -1691,12 +1606,9 @@ class CnxBlockFn(torch.autograd.Function):
         prec = _resolve(ctx.prec, rows, Cc, N1)
         if prec in ("fp32", "bf16x3", "fp16") and lib.gecco_linear_actbwd_ok(rows, Cc, N1, hip_ops.PRECISIONS[prec]):
             u, h = _new(1, rows, N1, like=x), _new(1, rows, N1, like=x)
-            img = WEIGHT_IMAGES.lookup("n", W1, prec=prec) if prec in ("bf16x3", "fp16") and _image_ok(rows, Cc, N1, prec) else None
-            Wp, ws = (None, img) if img is not None else (
-                _f(W1), hip_ops._ws((N1 + 127) // 128 * 128 * Cc * 4, x.device) if prec != "fp32" else None)
-            _lib.check(lib.gecco_linear_act_keep_f32(_ptr(y3), _ptr(Wp), _ptr(b1), None, 4, _ptr(u), _ptr(h), 1, rows, Cc, N1,
-                                                     hip_ops.PRECISIONS[prec], C.c_void_p(ws.data_ptr()) if ws is not None else None,
-                                                     _stream()), "gecco_linear_act_keep_f32")
+            Wp, ws, _keep = _w_operand("n", W1, prec, x.device, lookup=prec != "fp32" and _image_ok(rows, Cc, N1, prec))
+            _lib.check(lib.gecco_linear_act_keep_f32(_ptr(y3), Wp, _ptr(b1), None, 4, _ptr(u), _ptr(h), 1, rows, Cc, N1,
+                                                     hip_ops.PRECISIONS[prec], ws, _stream()), "gecco_linear_act_keep_f32")
         else:
             u = _linear_fwd(y3, W1, b1, None, False, ctx.prec)
             h = _act_forward(u, None, 4)
@@ -1853,21 +1765,25 @@ def adagn(mod, x, t, passthrough=False, stats=None):
                          passthrough, stats)
 
 
+def _act_kind(act) -> tuple[int, Tensor | None]:
+    """(kind, alpha) of an activation module the training path has a backward for: 1 / 2 GaussianActivation normalized / raw, 3 ReLU,
+    0 Identity (the inference path's `hip_ops.module_act` takes more)."""
+    from .models.activation import GaussianActivation
+    if isinstance(act, GaussianActivation):
+        return (1 if act.normalized else 2), act.alpha
+    if isinstance(act, torch.nn.ReLU):
+        return 3, None
+    if isinstance(act, torch.nn.Identity):
+        return 0, None
+    raise NotImplementedError(f"training on HIP: no backward for activation {type(act).__name__}")
+
+
 def mlp(mod, x, residual=None, want_stats=False):
     """nn.Sequential(Linear, act, Linear, ...) (reference models/mlp.py); `residual` is added by the last Linear's epilogue,
     which with `want_stats` also leaves the next norm's partial sums: returns (y, stats)."""
-    from .models.activation import GaussianActivation
     mods = list(mod)   # Linear, act, Linear[, act, Linear ...] (models/mlp.py)
     n = len(mods)
-    def kind_of(act):
-        if isinstance(act, GaussianActivation):
-            return (1 if act.normalized else 2), act.alpha
-        if isinstance(act, torch.nn.ReLU):
-            return 3, None
-        if isinstance(act, torch.nn.Identity):
-            return 0, None
-        raise NotImplementedError(f"training on HIP: no backward for activation {type(act).__name__}")
-    k0, a0 = kind_of(mods[1]) if n >= 3 else (0, None)
+    k0, a0 = _act_kind(mods[1]) if n >= 3 else (0, None)
     if k0:   # Linear -> act -> Linear: one Function (the forward keeps u from the first GEMM's epilogue, the backward runs act'
         # as the epilogue of the second linear's dX product)
         x = LinearActLinearFn.apply(x, mods[0].weight, mods[0].bias, a0, mods[2].weight, mods[2].bias, residual if n == 3 else None,
@@ -1879,7 +1795,7 @@ def mlp(mod, x, residual=None, want_stats=False):
     while i + 1 < n:
         act, lin = mods[i], mods[i + 1]
         last = i + 2 >= n
-        kind, alpha = kind_of(act)
+        kind, alpha = _act_kind(act)
         if kind:   # activation + the linear after it: one Function whose backward runs act' as the dX product's epilogue
             x = ActLinearFn.apply(x, alpha, lin.weight, lin.bias, residual if last else None, kind, want_stats and last)
         else:
@@ -1928,8 +1844,7 @@ def broadcasting_layer(layer, x, t, h=None, stats=None, want_stats=False):
     n2, mods = layer.mlp_norm, list(layer.mlp)
     if len(mods) == 3 and isinstance(mods[1], (GaussianActivation, torch.nn.ReLU)) and _pro_ok(R, Cc, mods[0].weight.shape[0]):
         # x + mlp(mlp_norm(x)) as one Function: the norm is the first GEMM's prologue, the skip the second's epilogue
-        act = mods[1]
-        kind, alpha = ((1 if act.normalized else 2), act.alpha) if isinstance(act, GaussianActivation) else (3, None)
+        kind, alpha = _act_kind(mods[1])
         out = AdaGNMlpFn.apply(x, t, n2.scale.weight, n2.scale.bias, n2.bias.weight, n2.bias.bias, n2.gn.num_groups, n2.gn.eps, st,
                                mods[0].weight, mods[0].bias, alpha, mods[2].weight, mods[2].bias, kind, want_stats)
         return (out[0], h, out[1]) if want_stats else (out, h)
@@ -1966,14 +1881,20 @@ def ray_network(net, geometry, t, K, features, do_cache=False, cache=None):
     return Linear3Fn.apply(group_norm(feats, gn2.num_groups, gn2.eps), lin2.weight, lin2.bias), out_cache
 
 
-def ray_network_edm(net, x, sigma, sigma_data, K, features, do_cache=False, cache=None):
-    """EDMPrecond(RayNetwork).forward with autograd (reference diffusion.py:46-57)."""
+def _edm_coeffs(sigma, sigma_data):
+    """(c_skip, c_out, c_in, c_noise) of EDM preconditioning per sample, (B, 1, 1) (reference diffusion.py:46-57)."""
     sigma = sigma.reshape(-1, 1, 1).float()
     sd = float(sigma_data)
     c_skip = sd ** 2 / (sigma ** 2 + sd ** 2)
     c_out = sigma * sd / (sigma ** 2 + sd ** 2).sqrt()
     c_in = 1 / (sd ** 2 + sigma ** 2).sqrt()
     c_noise = sigma.log() / 4
+    return c_skip, c_out, c_in, c_noise
+
+
+def ray_network_edm(net, x, sigma, sigma_data, K, features, do_cache=False, cache=None):
+    """EDMPrecond(RayNetwork).forward with autograd (reference diffusion.py:46-57)."""
+    c_skip, c_out, c_in, c_noise = _edm_coeffs(sigma, sigma_data)
     F_x, out_cache = ray_network(net, c_in * x, c_noise, K, features, do_cache, cache)
     den = c_skip * x + c_out * F_x
     return (den, out_cache) if do_cache else den
@@ -1981,12 +1902,7 @@ def ray_network_edm(net, x, sigma, sigma_data, K, features, do_cache=False, cach
 
 def linear_lift_edm(net, x, sigma, sigma_data, do_cache=False, cache=None):
     """EDMPrecond(LinearLift).forward with autograd (reference diffusion.py:46-57, linear_lift.py:44-46)."""
-    sigma = sigma.reshape(-1, 1, 1).float()
-    sd = float(sigma_data)
-    c_skip = sd ** 2 / (sigma ** 2 + sd ** 2)
-    c_out = sigma * sd / (sigma ** 2 + sd ** 2).sqrt()
-    c_in = 1 / (sd ** 2 + sigma ** 2).sqrt()
-    c_noise = sigma.log() / 4
+    c_skip, c_out, c_in, c_noise = _edm_coeffs(sigma, sigma_data)
     feats = LiftFn.apply(c_in * x, net.lift.weight, net.lift.bias)
     feats, out_cache = set_transformer(net.inner, feats, c_noise, do_cache, cache)
     F_x = lower(net, feats)
