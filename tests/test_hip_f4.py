@@ -168,8 +168,18 @@ def test_set_distance_shapes_and_symmetry():
         Daa = metrics.pairwise_set_distance(a, a, kind)
         assert torch.equal(Daa, Daa.t().contiguous()) or (Daa - Daa.t()).abs().max().item() <= 1e-6 * Daa.max().item()
         assert Daa.diagonal().abs().max().item() <= 1e-3   # a cloud against itself: the clamp hides the cancellation noise of |a|^2 + |b|^2 - 2ab
-    E = metrics.pairwise_set_distance(a[:3, :64], b[:2, :64], "emd", block_size=2)
-    assert E.shape == (3, 2) and torch.isfinite(E).all()
+    # the blocked entropic kind: 5 x 3 pairs in blocks of 2 x 2 (ragged last blocks in both directions), every entry against the fp64
+    # Sinkhorn of that pair (a transposed or misplaced block fails), and the same bits whatever the blocking
+    ea, eb = a[:5, :64].contiguous(), b[:3, :64].contiguous()
+    E = metrics.pairwise_set_distance(ea, eb, "emd", block_size=2)
+    assert E.shape == (5, 3) and torch.isfinite(E).all()
+    pa = ea.cpu().double()[:, None].expand(5, 3, 64, 3).reshape(-1, 64, 3)
+    pb = eb.cpu().double()[None].expand(5, 3, 64, 3).reshape(-1, 64, 3)
+    eref = cpu_ref.sinkhorn_cost(cpu_ref.distance_matrix(pa, pb, squared=True), 0.1, 200).reshape(5, 3)
+    erel = ((E.cpu().double() - eref).abs() / eref).max().item()
+    print("blocked sinkhorn_emd(epsilon = 0.1, 200 sweeps) vs fp64, worst relative error", erel)
+    assert erel <= 1e-4   # test_hip_poison.py::test_metrics_from_poisoned_memory's bar at this epsilon
+    assert torch.equal(metrics.pairwise_set_distance(ea, eb, "emd", block_size=16), E)
 
 
 def test_evaluate_logp_vs_oracle(model):

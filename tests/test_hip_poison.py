@@ -354,3 +354,41 @@ def test_metrics_from_poisoned_memory(N, M):
         else:
             _close(ref, cpu_ref.sinkhorn_cost(cpu_ref.distance_matrix(a[0].double(), b[0].double(), squared=True), 0.1, 50).float(),
                    1e-4, name)
+
+
+@pytest.mark.parametrize("kind", ["chamfer", "chamfer_squared"])
+@pytest.mark.parametrize("S,T,N,M", [(70, 5, 130, 2049), (3, 67, 300, 100)])
+def test_set_chamfer_from_poisoned_memory(S, T, N, M, kind):
+    """pairwise_set_distance: the second launch (b -> a, grouped at (70, 5); at (3, 67) the first is) ADDS its half to what the first
+    wrote into a `torch.empty` output: an entry the first launch skipped would keep the poison."""
+    from gecco_amd import metrics
+    from tests import _set_protocol as sp
+    a, b = sp.chamfer_sets(S, T, N, M)
+    a2, b2 = sp.chamfer_sets(S, T, N, M, seed=N + M)
+    ref = metrics.pairwise_set_distance(a.cuda(), b.cuda(), kind).clone()
+    assert torch.isfinite(ref).all()
+    metrics.pairwise_set_distance(a2.cuda(), b2.cuda(), kind)
+    poison_free_memory()
+    assert_same_bits(metrics.pairwise_set_distance(a.cuda(), b.cuda(), kind), ref, kind)
+    want = sp.set_chamfer_fp64(a, b)[int(kind == "chamfer_squared")]
+    assert (ref.cpu().double() - want).abs().max().item() <= 2e-5 * want.max().item()   # test_hip_f4.py::test_set_distance_shapes_and_symmetry
+
+
+def test_set_metrics_from_poisoned_memory():
+    """set_metrics at n = 129 on an integer-valued matrix full of ties: the kernel zeroes the `torch.empty` coverage flags it then
+    counts, and a thread strides over more than one column."""
+    from gecco_amd import metrics
+    from tests import _set_protocol as sp
+    n = 129
+    A = [torch.from_numpy(m).cuda() for m in sp.metric_matrices("integer", n)]
+    Bm = [torch.from_numpy(m).cuda() for m in sp.metric_matrices("random", n)]
+    ref = {k: v.clone() for k, v in metrics.set_metrics(*A).items()}
+    metrics.set_metrics(*Bm)
+    poison_free_memory()
+    again = metrics.set_metrics(*A)
+    for k in ref:
+        assert torch.isfinite(ref[k]).all(), k
+        assert_same_bits(again[k], ref[k], k)
+    want = cpu_ref.set_metrics(*sp.metric_matrices("integer", n))
+    assert round(float(ref["1-nn"]) * 2 * n) == round(want["1-nn"] * 2 * n) and round(float(ref["cov"]) * n) == round(want["cov"] * n)
+    assert float(ref["mmd"]) == want["mmd"]
