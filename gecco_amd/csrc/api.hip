@@ -5,6 +5,7 @@
 #include "../../include/gecco_hip.h"
 #include "kernels.h"
 
+#include <atomic>
 #include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
@@ -210,7 +211,7 @@ int linear_pair(const Lin& a, const float* W2, const float* b2, int Nout2, float
 
 // Path switches for A/B runs and tests: gecco_set_option, or the environment (GECCO_ASTAT, GECCO_CHAIN) on first use.
 enum { OPT_ASTAT = 0, OPT_CHAIN = 1, OPT_HEADMAJOR = 2, OPT_MLPFUSED = 3, OPT_UNPOOLFUSED = 4, OPT_LO8 = 5, OPT_ACTIMG = 6, OPT_H8 = 7, OPT_KVQ64 = 8, OPT_H8AREG = 9, OPT_CHAIN2 = 10, OPT_UNPOOLH8 = 11, OPT_MLPW = 12, OPT_CHAINCL = 13, OPT_H6 = 14, OPT_KVFOLD = 15, OPT_MLPWSHARE = 16, OPT_KVQPERM = 17, OPT_IMGPROJ16 = 18, OPT_COUNT = 19 };
-int g_options[OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+std::atomic<int> g_options[OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 const char* const g_option_names[OPT_COUNT] = {"astat", "chain", "headmajor", "mlpfused", "unpoolfused", "lo8", "actimg", "h8", "kvq64", "h8areg", "chain2", "unpoolh8", "mlpw", "chaincl", "h6", "kvfold", "mlpwshare", "kvqperm", "imgproj16"};
 const char* const g_option_env[OPT_COUNT] = {"GECCO_ASTAT", "GECCO_CHAIN", "GECCO_HEADMAJOR", "GECCO_MLPFUSED", "GECCO_UNPOOLFUSED", "GECCO_LO8",
                                              "GECCO_ACTIMG", "GECCO_H8", "GECCO_KVQ64", "GECCO_H8AREG", "GECCO_CHAIN2", "GECCO_UNPOOLH8", "GECCO_MLPW", "GECCO_CHAINCL", "GECCO_H6", "GECCO_KVFOLD", "GECCO_MLPWSHARE",
@@ -225,14 +226,17 @@ struct PlanScope {
 };
 int option(int which) {
     if (t_plan && ((t_plan->opt_mask >> which) & 1u)) return (int)((t_plan->opt_vals >> which) & 1u);
-    if (g_options[which] < 0) {
+    int v = g_options[which].load(std::memory_order_relaxed);
+    if (v < 0) {
         const char* e = getenv(g_option_env[which]);
         // "mlpwshare" (the one-launch MLP leaves CUs to a second stream's kernels) is off unless the caller runs two streams: hip_ops.py
         // sets it around a two-stream evaluation
         // "imgproj16" (img_feature_proj on one-term fp16 operands) is opt-in: 2 % of a C3 evaluation for a fifth of the w2 mode's error budget
-        g_options[which] = e ? (atoi(e) != 0) : (which != OPT_MLPWSHARE && which != OPT_IMGPROJ16);
+        const int fill = e ? (atoi(e) != 0) : (which != OPT_MLPWSHARE && which != OPT_IMGPROJ16);
+        // concurrent first reads fill in the same value; a gecco_set_option that got in between wins (v then holds its value)
+        if (g_options[which].compare_exchange_strong(v, fill, std::memory_order_relaxed)) v = fill;
     }
-    return g_options[which];
+    return v;
 }
 
 // fp16 mode: C16 (| C2_16) = fp16(act(fp16(x * pa + po) W^T + bias)) in one pass over x (gemm_f16_astat.hip).
@@ -758,7 +762,7 @@ int gecco_set_option(const char* name, int value) {
     if (!name) return fail(-1, "set_option: null name");
     for (int i = 0; i < OPT_COUNT; ++i)
         if (!strcmp(name, g_option_names[i])) {
-            g_options[i] = value < 0 ? -1 : (value != 0);   // < 0: back to the environment / default
+            g_options[i].store(value < 0 ? -1 : (value != 0), std::memory_order_relaxed);   // < 0: back to the environment / default
             return 0;
         }
     return fail(-2, "set_option: unknown option '%s' (astat, chain, headmajor, mlpfused, unpoolfused, lo8, actimg, h8, kvq64, h8areg, chain2, unpoolh8, mlpw, chaincl, h6, kvfold, mlpwshare, kvqperm, imgproj16)", name);

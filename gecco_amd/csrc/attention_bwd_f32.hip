@@ -20,6 +20,7 @@
 // fixed order by reduce_batch_kernel — no float atomics.
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 namespace {
 
@@ -459,11 +460,7 @@ int pool_bwd_t(const float* KV, const float* ind, const float* O, const float* l
     constexpr int KP = HD + 4;
     const size_t a = (size_t)2 * 64 * KP + 128 + 4 * (2 * 32 * KP + 32 * 68), c = (size_t)4 * HD * 64;
     const size_t lds = (a > c ? a : c) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pool_attn_bwd_kernel<HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (const hipError_t e = lds_opt_in<pool_attn_bwd_kernel<HD>>(lds)) return (int)e;
     hipLaunchKernelGGL((pool_attn_bwd_kernel<HD>), dim3(B * H * nsplit), dim3(256), lds, st, KV, ind, O, lse, dO, dKV, dQp, B, N, C, H, nsplit);
     return (int)hipGetLastError();
 }
@@ -474,11 +471,7 @@ int unpool_bwd_t(const float* q, const float* kvh, const float* dO, float* dq, f
     constexpr int KP = HD + 4;
     const size_t a = (size_t)2 * 64 * KP + 4 * (2 * 32 * KP + 64 * 36), c = (size_t)8 * 64 * HD;
     const size_t lds = (a > c ? a : c) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(unpool_attn_bwd_kernel<HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (const hipError_t e = lds_opt_in<unpool_attn_bwd_kernel<HD>>(lds)) return (int)e;
     hipLaunchKernelGGL((unpool_attn_bwd_kernel<HD>), dim3(B * H * nchunk), dim3(256), lds, st, q, kvh, dO, dq, part, B, N, C, H, tpw, nchunk);
     return (int)hipGetLastError();
 }

@@ -26,6 +26,7 @@
 // the bytes of six crossings of HBM per layer.  Inducer-side tensors (queries, k | v of the inducers, their gradients) stay fp32.
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 namespace {
 
@@ -641,11 +642,7 @@ int pool_bwd_x3_t(const float* KV, const float* ind, const float* O, const float
     constexpr int DT = (HD + 31) / 32, NPL = F16 ? 1 : 2;
     const size_t a = (size_t)NPL * (2 * 16 * DT * 128 + 4 * (2 * 8 * DT * 128 + (DT == 2 ? 0 : 16 * 128))) * 2 + 128 * 4, c = (size_t)4 * HD * 64 * 4;
     const size_t lds = a > c ? a : c;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pool_attn_bwd_x3_kernel<HD, F16, IO16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (const hipError_t e = lds_opt_in<pool_attn_bwd_x3_kernel<HD, F16, IO16>>(lds)) return (int)e;
     hipLaunchKernelGGL((pool_attn_bwd_x3_kernel<HD, F16, IO16>), dim3(B * H * nsplit), dim3(256), lds, st, KV, ind, O, lse, dO, dKV, dQp, B, N, C, H, nsplit);
     return (int)hipGetLastError();
 }
@@ -656,11 +653,7 @@ int unpool_bwd_x3_t(const float* q, const float* kvh, const float* dO, float* dq
     constexpr int DT = (HD + 31) / 32, NPL = F16 ? 1 : 2;
     const size_t a = (size_t)NPL * (2 * 16 * DT * 128 + 4 * (8 * 2 * 128 + 2 * 8 * DT * 128)) * 2, c = (size_t)4 * 64 * HD * 4;
     const size_t lds = a > c ? a : c;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(unpool_attn_bwd_x3_kernel<HD, F16, IO16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (const hipError_t e = lds_opt_in<unpool_attn_bwd_x3_kernel<HD, F16, IO16>>(lds)) return (int)e;
     hipLaunchKernelGGL((unpool_attn_bwd_x3_kernel<HD, F16, IO16>), dim3(B * H * nchunk), dim3(256), lds, st, q, kvh, dO, dq, part, B, N, C, H, tpw, nchunk);
     return (int)hipGetLastError();
 }

@@ -13,6 +13,7 @@
 // Softmax runs in the log2 domain (queries pre-scaled by log2(e)/sqrt(hd)).
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -355,12 +356,7 @@ int pool_launch_t(const float* KV, const float* ind, float* po, float* pml, int 
     constexpr int KP = HD + 4;
     const size_t a = (size_t)64 * KP + 4 * (32 * KP + 32 * HD), c = (size_t)4 * HD * 64 + 512;
     const size_t lds = (a > c ? a : c) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pool_attn_kernel<HD>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (const hipError_t e = lds_opt_in<pool_attn_kernel<HD>>(lds)) return (int)e;
     hipLaunchKernelGGL((pool_attn_kernel<HD>), dim3(B * H * nsplit), dim3(256), lds, st, KV, ind, po, pml, B, N, C, H,
                        nsplit);
     return (int)hipGetLastError();
@@ -374,12 +370,7 @@ int unpool_launch_t(const float* q, const float* kvh, float* out, int B, int N, 
     int tpw = 1;
     while (tpw < 4 && (long)B * H * ((tiles + tpw * 2 - 1) / (tpw * 2)) >= 2048) tpw *= 2;
     const int nchunk = (tiles + tpw - 1) / tpw;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(unpool_attn_kernel<HD>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (const hipError_t e = lds_opt_in<unpool_attn_kernel<HD>>(lds)) return (int)e;
     hipLaunchKernelGGL((unpool_attn_kernel<HD>), dim3(B * H * nchunk), dim3(256), lds, st, q, kvh, out, B, N, C, H, tpw,
                        nchunk);
     return (int)hipGetLastError();
@@ -391,14 +382,11 @@ int pool_attn_nsplit(int B, int N, int H) {
     // A function of N only: the key-split (hence the summation order) must not depend on the batch
     // size, so a sample's result is bit-identical whatever batch (or GPU shard) it is evaluated in.
     (void)B; (void)H;
-    static int keys = 0;
-    if (!keys) {
-        // keys per split below which a cloud is not split further.  2048 since the inducer chain merges the partials in every block of
-        // its cluster (three times per sample at d = 384): one split at N = 2048 instead of two — C2 4.873 / 4.882 -> 4.842 / 4.844 ms,
-        // the other shapes and the training step unchanged (1024 before: profiles/r04d_negative_results.txt had it neutral then)
-        const char* e = getenv("GECCO_POOL_SPLIT_KEYS");
-        keys = e && atoi(e) >= 32 ? atoi(e) : 2048;
-    }
+    // keys per split below which a cloud is not split further.  2048 since the inducer chain merges the partials in every block of
+    // its cluster (three times per sample at d = 384): one split at N = 2048 instead of two — C2 4.873 / 4.882 -> 4.842 / 4.844 ms,
+    // the other shapes and the training step unchanged (1024 before: profiles/r04d_negative_results.txt had it neutral then)
+    static const int keys_env = env_int("GECCO_POOL_SPLIT_KEYS", 2048);
+    const int keys = keys_env >= 32 ? keys_env : 2048;
     int ns = 1;
     while (ns < 8 && N / (ns * 2) >= keys) ns *= 2;
     return ns;

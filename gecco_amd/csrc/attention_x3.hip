@@ -17,6 +17,7 @@
 #include "common.h"
 #include "h8_scales.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 namespace {
 
@@ -647,12 +648,7 @@ int pool_x3_launch_t(const float* KV, const float* ind, float* po, float* pml, i
     constexpr int KS = HD + 8, DT = (HD + 31) / 32, VT = 8 * DT * 128, NP = F16 ? 1 : 2;
     const size_t a = ((size_t)NP * 64 * KS + 4 * NP * (32 * KS + VT)) * 2, c = ((size_t)4 * HD * 64 + 512) * 4;
     const size_t lds = a > c ? a : c;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pool_attn_x3_kernel<HD, F16, IO16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (const hipError_t e = lds_opt_in<pool_attn_x3_kernel<HD, F16, IO16>>(lds)) return (int)e;
     hipLaunchKernelGGL((pool_attn_x3_kernel<HD, F16, IO16>), dim3(B * H * nsplit), dim3(256), lds, st, KV, ind, po, pml, B, N, C,
                        H, nsplit, hm);
     return (int)hipGetLastError();
@@ -667,12 +663,7 @@ int unpool_x3_launch_t(const float* q, const float* kvh, float* out, int B, int 
     int tpw = 1;
     while (tpw < 4 && (long)B * H * ((tiles + tpw * 2 - 1) / (tpw * 2)) >= 2048) tpw *= 2;
     const int nchunk = (tiles + tpw - 1) / tpw;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(unpool_attn_x3_kernel<HD, F16, IO16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (const hipError_t e = lds_opt_in<unpool_attn_x3_kernel<HD, F16, IO16>>(lds)) return (int)e;
     hipLaunchKernelGGL((unpool_attn_x3_kernel<HD, F16, IO16>), dim3(B * H * nchunk), dim3(256), lds, st, q, kvh, out, B, N, C, H,
                        tpw, nchunk, hm, out32);
     return (int)hipGetLastError();

@@ -4,6 +4,7 @@
 // (reduce_batch_kernel): gradients are bitwise reproducible.
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 namespace {
 
@@ -628,12 +629,7 @@ int lower_bwd_launch(const float* feat, const float* dF, const float* W, float* 
         default: break;
     }
     const size_t lds = (size_t)(12 * C + 12) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lower_bwd_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    if (const hipError_t e = lds_opt_in<lower_bwd_kernel>(lds)) return (int)e;
     hipLaunchKernelGGL(lower_bwd_kernel, dim3((unsigned)lower_bwd_blocks(rows)), dim3(256), lds, st, feat, dF, W, dfeat,
                        partial, rows, C, eps, 128);
     return (int)hipGetLastError();
@@ -657,32 +653,30 @@ namespace {
 constexpr int LOWER_G_BWD_ROWS = 128;   // rows per block: 8 tiles of 16
 
 template <int CPL, int P, bool NORM>
-void lower_g_bwd_go(unsigned nblk, size_t lds, hipStream_t st, const float* feat, const float* dF, const float* W, float* dfeat,
+int lower_g_bwd_go(unsigned nblk, size_t lds, hipStream_t st, const float* feat, const float* dF, const float* W, float* dfeat,
                     float* partial, size_t rows, int C, int G, float eps) {
-    static size_t attr = 0;   // (G + 16) C + 256 floats: 66.5 KB at G = 16, C = 512, above the 64 KB default
-    if (lds > 64 * 1024 && lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lower_g_bwd_kernel<CPL, P, NORM>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
+    if (lds > 64 * 1024) {   // (G + 16) C + 256 floats: 66.5 KB at G = 16, C = 512, above the 64 KB default
+        if (const hipError_t e = lds_opt_in<lower_g_bwd_kernel<CPL, P, NORM>>(lds)) return (int)e;
     }
     hipLaunchKernelGGL((lower_g_bwd_kernel<CPL, P, NORM>), dim3(nblk), dim3(256), lds, st, feat, dF, W, dfeat, partial, rows, C, G,
                        eps, LOWER_G_BWD_ROWS);
+    return (int)hipGetLastError();
 }
 template <int CPL, int P>
-void lower_g_bwd_norm(bool norm, unsigned nblk, size_t lds, hipStream_t st, const float* feat, const float* dF, const float* W,
+int lower_g_bwd_norm(bool norm, unsigned nblk, size_t lds, hipStream_t st, const float* feat, const float* dF, const float* W,
                       float* dfeat, float* partial, size_t rows, int C, int G, float eps) {
-    if (norm) lower_g_bwd_go<CPL, P, true>(nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
-    else lower_g_bwd_go<CPL, P, false>(nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
+    return norm ? lower_g_bwd_go<CPL, P, true>(nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps)
+                : lower_g_bwd_go<CPL, P, false>(nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
 }
 template <int CPL>
-void lower_g_bwd_p(int P, bool norm, unsigned nblk, size_t lds, hipStream_t st, const float* feat, const float* dF, const float* W,
+int lower_g_bwd_p(int P, bool norm, unsigned nblk, size_t lds, hipStream_t st, const float* feat, const float* dF, const float* W,
                    float* dfeat, float* partial, size_t rows, int C, int G, float eps) {
     switch (P) {
-        case 1: lower_g_bwd_norm<CPL, 1>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
-        case 2: lower_g_bwd_norm<CPL, 2>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
-        case 4: lower_g_bwd_norm<CPL, 4>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
-        case 8: lower_g_bwd_norm<CPL, 8>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
-        default: lower_g_bwd_norm<CPL, 16>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
+        case 1: return lower_g_bwd_norm<CPL, 1>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
+        case 2: return lower_g_bwd_norm<CPL, 2>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
+        case 4: return lower_g_bwd_norm<CPL, 4>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
+        case 8: return lower_g_bwd_norm<CPL, 8>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
+        default: return lower_g_bwd_norm<CPL, 16>(norm, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
     }
 }
 }  // namespace
@@ -696,7 +690,7 @@ int lower_g_bwd_launch(const float* feat, const float* dF, const float* W, float
     const size_t lds = ((size_t)(G + 16) * C + 256) * sizeof(float);
     const int cpl = (C / 4 + 15) / 16, P = geometry_pow2(G);
     switch (cpl) {
-#define LOWER_G_BWD(CPL) case CPL: lower_g_bwd_p<CPL>(P, do_norm != 0, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps); break;
+#define LOWER_G_BWD(CPL) case CPL: return lower_g_bwd_p<CPL>(P, do_norm != 0, nblk, lds, st, feat, dF, W, dfeat, partial, rows, C, G, eps);
         LOWER_G_BWD(1) LOWER_G_BWD(2) LOWER_G_BWD(3) LOWER_G_BWD(4) LOWER_G_BWD(5) LOWER_G_BWD(6) LOWER_G_BWD(7) LOWER_G_BWD(8)
 #undef LOWER_G_BWD
     }

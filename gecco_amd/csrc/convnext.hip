@@ -12,6 +12,7 @@
 // layer_scale fold.  LayerNorm statistics are per texel over its channels (fp32 sums over <= 768 values).
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 namespace {
 
@@ -348,12 +349,7 @@ int cnx_dwconv_ln_launch(const float* x, const float* w, const float* bias, cons
 #define CNX_DW(CV)                                                                                                          \
     case CV: {                                                                                                              \
         constexpr int NCH = dw_chunks(CV);                                                                                  \
-        static bool attr = false;                                                                                           \
-        if (!attr) {                                                                                                        \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv7_ln_kernel<CV, NCH>),                            \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-            attr = true;                                                                                                    \
-        }                                                                                                                   \
+        if (const hipError_t e = lds_opt_in<dwconv7_ln_kernel<CV, NCH>>(lds)) return (int)e;                                \
         hipLaunchKernelGGL((dwconv7_ln_kernel<CV, NCH>), dim3(grid), dim3(256), lds, st, x, w, bias, ln_w, ln_b, out, zout, B, H, W, eps, iters, addp, flip); \
         break;                                                                                                              \
     }

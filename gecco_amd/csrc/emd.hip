@@ -34,6 +34,7 @@
 #include "../../include/gecco_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 #include "pair_dist.h"
 
 namespace {
@@ -184,9 +185,7 @@ __global__ __launch_bounds__(EMD_THREADS) void emd_auction_kernel(const float* _
 int emd_auction_launch(const float* A, const float* Bc, float* out, int* assign, int* status, int pairs, int T, int set_mode, int N,
                        int match_sq, int avg_sq, int max_rounds, hipStream_t st) {
     if (pairs <= 0 || N < 1 || N > EMD_MAX_N || (set_mode && T <= 0) || max_rounds < 1) return -2;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(emd_auction_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(EMD_LDS_PER_POINT * EMD_MAX_N));
-    if (attr != hipSuccess) return (int)attr;
+    if (const hipError_t e = lds_opt_in<emd_auction_kernel>(EMD_LDS_PER_POINT * EMD_MAX_N)) return (int)e;
     hipLaunchKernelGGL(emd_auction_kernel, dim3(pairs), dim3(EMD_THREADS), EMD_LDS_PER_POINT * N, st, A, Bc, out, assign, status, N, T,
                        set_mode, match_sq, avg_sq, max_rounds);
     return (int)hipGetLastError();

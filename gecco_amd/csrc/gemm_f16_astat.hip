@@ -23,6 +23,7 @@
 // which sit in the in-order vmcnt queue behind the DMA pieces already in flight; the K-steps after an epilogue whose
 // awaited piece was issued before it wait with that count added instead of draining the stores.
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 #include "h8_scales.h"
 
 #include <stdlib.h>
@@ -390,12 +391,7 @@ __global__ __launch_bounds__(S_NT, 2) void gemm_f16_astat_kernel(GemmArgs g) {
 template <int NK, int NS, int WS>
 int astat_launch_ws(const GemmArgs& g, hipStream_t st) {
     const size_t lds = ((size_t)NS * S_TILE + g.Nout + 2 * g.K) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_astat_kernel<NK, NS, WS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    if (const hipError_t e = lds_opt_in<gemm_f16_astat_kernel<NK, NS, WS>>(lds)) return (int)e;
     hipLaunchKernelGGL((gemm_f16_astat_kernel<NK, NS, WS>), dim3(g.B * (g.rows / 128)), dim3(S_NT), lds, st, g);
     return (int)hipGetLastError();
 }

@@ -19,6 +19,7 @@
 // Ring of DNS stages with the K-step being multiplied held in registers (two fragment sets), counted vmcnt waits and
 // one raw s_barrier per K-step as in the split-bf16 kernel.  Requires K % 32 == 0, Nout % 4 == 0, rows >= 64.
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -393,25 +394,13 @@ template <int DNS, int BM, bool A16, bool C16>
 int f16_launch_t(const GemmArgs& g, hipStream_t st) {
     const int tilesM = (g.rows + BM - 1) / BM, tilesN = (g.Nout + DBN - 1) / DBN;
     const size_t lds = (size_t)(f_main_floats(DNS, BM, A16) + (g.pro_a ? 2 * g.K : 0)) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        if (!A16)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<DNS, !A16, BM, A16, C16>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<DNS, false, BM, A16, C16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    // (with A16 there is no prologue form: both names are the one kernel)
+    if (const hipError_t e = lds_opt_in<gemm_f16_kernel<DNS, !A16, BM, A16, C16>, gemm_f16_kernel<DNS, false, BM, A16, C16>>(lds)) return (int)e;
     const dim3 grid(g.B * tilesM * tilesN);
     if (g.dot_x && (g.mul_u || g.pre_out || !g.stats || g.C2 || C16 || (g.residual && !A16))) return -9;
     if constexpr (A16 && !C16) {
         if (g.dot_x) {   // (with or without a residual: gemm_dma_common.h res_and_dot)   // the dX product of an MLP's first linear from du stored as halves (autograd.py `_du16_ok`), with the AdaGN backward's partials
-            static size_t attr3 = 0;
-            if (lds > attr3) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<DNS, false, BM, true, false, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                attr3 = lds;
-            }
+            if (const hipError_t e = lds_opt_in<gemm_f16_kernel<DNS, false, BM, true, false, true>>(lds)) return (int)e;
             hipLaunchKernelGGL((gemm_f16_kernel<DNS, false, BM, true, false, true>), grid, dim3(DNT), lds, st, g);
             return (int)hipGetLastError();
         }
@@ -421,14 +410,7 @@ int f16_launch_t(const GemmArgs& g, hipStream_t st) {
         // reads again — as an fp16 operand either way) beside the fp32 pre-activation
         if (A16 || (C16 && g.mul_u) || (g.mul_u && g.pro_a) || g.c_img) return -9;
         if constexpr (!A16) {
-            static size_t attr2 = 0;
-            if (lds > attr2) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<DNS, true, BM, false, C16, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_kernel<DNS, false, BM, false, C16, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                attr2 = lds;
-            }
+            if (const hipError_t e = lds_opt_in<gemm_f16_kernel<DNS, true, BM, false, C16, true>, gemm_f16_kernel<DNS, false, BM, false, C16, true>>(lds)) return (int)e;
             if (g.pro_a) hipLaunchKernelGGL((gemm_f16_kernel<DNS, true, BM, false, C16, true>), grid, dim3(DNT), lds, st, g);
             else hipLaunchKernelGGL((gemm_f16_kernel<DNS, false, BM, false, C16, true>), grid, dim3(DNT), lds, st, g);
         }
@@ -457,11 +439,7 @@ bool gemm_f16_dma_supported(const GemmArgs& g) {
 
 int gemm_f16_dma_launch(const GemmArgs& g, hipStream_t st) {
     if (!g.w_img) return -9;
-    static int ns = 0;
-    if (!ns) {
-        const char* e = getenv("GECCO_GEMM_F16_STAGES");
-        ns = (e && atoi(e) == 2) ? 2 : 3;
-    }
+    static const int ns = env_int("GECCO_GEMM_F16_STAGES", 3) == 2 ? 2 : 3;
     if (g.a_f16 && g.c_f16) return f16_launch_t<3, 128, true, true>(g, st);
     if (g.a_f16) return f16_launch_t<3, 128, true, false>(g, st);
     if (g.c_f16) return f16_launch_t<3, 128, false, true>(g, st);

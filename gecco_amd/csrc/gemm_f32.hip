@@ -21,6 +21,7 @@
 // and the epilogue's stores drain behind the next tile's main loop.
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -343,21 +344,10 @@ int launch(const GemmArgs& g, hipStream_t st) {
     constexpr int LDP = BK + 4;
     const int tilesM = (g.rows + BM - 1) / BM, tilesN = (g.Nout + BN - 1) / BN;
     const size_t lds = 2 * (BM + BN) * LDP * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<BM, BN, WM, WN, BK, HAS_PRO>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    if (const hipError_t e = lds_opt_in<gemm_f32_kernel<BM, BN, WM, WN, BK, HAS_PRO>>(lds)) return (int)e;
     // persistent grid: one block per resident slot, a multiple of 8 (one share per XCD)
-    static int slots = 0;
-    if (!slots) {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const int per_cu = (160 * 1024) / (int)lds < 2 ? (160 * 1024) / (int)lds : 2;
-        slots = cus * (per_cu > 0 ? per_cu : 1);
-    }
+    const int per_cu = (160 * 1024) / (int)lds < 2 ? (160 * 1024) / (int)lds : 2;
+    const int slots = device_cus() * (per_cu > 0 ? per_cu : 1);
     const int nblk = g.B * tilesM * tilesN;
     int grid = nblk < slots ? nblk : slots;
     grid = (grid + 7) / 8 * 8;
@@ -373,11 +363,7 @@ int gemm_f32_launch(const GemmArgs& g, hipStream_t st) {
     if (g.K % 4 || g.lda % 4 || g.ldw % 4) return -2;  // 16-byte vector loads
     if (g.precision == 2 && g.w_img && gemm_f16_dma_supported(g)) return gemm_f16_dma_launch(g, st);
     {
-        static int use_dma = -1;  // GECCO_GEMM_DMA=0 forces the register-staged kernel (A/B runs)
-        if (use_dma < 0) {
-            const char* e = getenv("GECCO_GEMM_DMA");
-            use_dma = e ? atoi(e) : 1;
-        }
+        static const int use_dma = env_int("GECCO_GEMM_DMA", 1);  // 0 forces the register-staged kernel (A/B runs)
         if (use_dma && gemm_f32_dma_supported(g)) return gemm_f32_dma_launch(g, st);
     }
     if (!g.W) return -9;   // a ready weight image without the matrix itself: only the LDS-DMA kernel reads images

@@ -24,6 +24,7 @@
 //               after the AdaGN affine.
 // Requires K % 16 == 0, Nout % 4 == 0, rows >= 128; everything else runs on gemm_f32.hip.
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -360,12 +361,7 @@ template <int BM>
 int dma_launch_aimg(const GemmArgs& g, hipStream_t st) {
     const int tilesM = (g.rows + BM - 1) / BM, tilesN = (g.Nout + DBN - 1) / DBN;
     const size_t lds = (size_t)(d_main_floats(3, BM) + 2 * g.K) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_dma_kernel<3, false, true, BM, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    if (const hipError_t e = lds_opt_in<gemm_dma_kernel<3, false, true, BM, true>>(lds)) return (int)e;
     hipLaunchKernelGGL((gemm_dma_kernel<3, false, true, BM, true>), dim3(g.B * tilesM * tilesN), dim3(DNT), lds, st, g);
     return (int)hipGetLastError();
 }
@@ -374,25 +370,11 @@ template <int DNS, bool X3, int BM = 128>
 int dma_launch_t(const GemmArgs& g, hipStream_t st) {
     const int tilesM = (g.rows + BM - 1) / BM, tilesN = (g.Nout + DBN - 1) / DBN;
     const size_t lds = (size_t)(d_main_floats(DNS, BM) + (g.pro_a ? 2 * g.K : 0)) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_dma_kernel<DNS, true, X3, BM>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_dma_kernel<DNS, false, X3, BM>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    if (const hipError_t e = lds_opt_in<gemm_dma_kernel<DNS, true, X3, BM>, gemm_dma_kernel<DNS, false, X3, BM>>(lds)) return (int)e;
     const dim3 grid(g.B * tilesM * tilesN);
     if (g.mul_u || g.pre_out || g.dot_x) {   // the training path's epilogue forms: their own kernel instantiations
         if ((g.mul_u && g.pro_a) || (g.pre_out && g.c_img) || (g.dot_x && (g.residual || g.mul_u || g.pre_out || !g.stats || g.C2 || g.c_img))) return -9;
-        static size_t attr2 = 0;
-        if (lds > attr2) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_dma_kernel<DNS, false, X3, BM, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_dma_kernel<DNS, true, X3, BM, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr2 = lds;
-        }
+        if (const hipError_t e = lds_opt_in<gemm_dma_kernel<DNS, false, X3, BM, false, true>, gemm_dma_kernel<DNS, true, X3, BM, false, true>>(lds)) return (int)e;
         if (g.pro_a) hipLaunchKernelGGL((gemm_dma_kernel<DNS, true, X3, BM, false, true>), grid, dim3(DNT), lds, st, g);
         else hipLaunchKernelGGL((gemm_dma_kernel<DNS, false, X3, BM, false, true>), grid, dim3(DNT), lds, st, g);
     } else if (g.pro_a) hipLaunchKernelGGL((gemm_dma_kernel<DNS, true, X3, BM>), grid, dim3(DNT), lds, st, g);
@@ -413,18 +395,11 @@ bool gemm_f32_dma_supported(const GemmArgs& g, int precision) {
 }
 
 int gemm_f32_dma_launch(const GemmArgs& g, hipStream_t st) {
-    static int ns3 = -1;
-    if (ns3 < 0) {
-        const char* e = getenv("GECCO_GEMM_STAGES");   // 3 stages = 51 KB LDS = three blocks per CU (measured best)
-        ns3 = (e && atoi(e) == 4) ? 0 : 1;
-    }
+    static const int stages = env_int("GECCO_GEMM_STAGES", 3);   // 3 stages = 51 KB LDS = three blocks per CU (measured best)
+    const bool ns3 = stages != 4;
     if (g.a_img) {
         if (!(g.precision == 1 && g.w_img && !g.pro_a && g.rows >= 128 && g.rows % 128 == 0)) return -9;
-        static int areg = -1;
-        if (areg < 0) {
-            const char* e = getenv("GECCO_AREG");   // 0: the image through the LDS ring (A/B runs)
-            areg = (e && atoi(e) == 0) ? 0 : 1;
-        }
+        static const int areg = env_int("GECCO_AREG", 1);   // 0: the image through the LDS ring (A/B runs)
         if (areg && gemm_x3_areg_supported(g)) return gemm_x3_areg_launch(g, st);
         return (g.rows >= 256 && g.K >= 512) ? dma_launch_aimg<256>(g, st) : dma_launch_aimg<128>(g, st);
     }
@@ -433,11 +408,7 @@ int gemm_f32_dma_launch(const GemmArgs& g, hipStream_t st) {
         return -9;
     if (g.precision == 1 && g.w_img) {
         if (g.rows < 128) return dma_launch_t<3, true, 64>(g, st);
-        static int bm256 = -1;
-        if (bm256 < 0) {
-            const char* e = getenv("GECCO_GEMM_BM256");   // 0: keep the 128-row tiles (A/B runs)
-            bm256 = (e && atoi(e) == 0) ? 0 : 1;
-        }
+        static const int bm256 = env_int("GECCO_GEMM_BM256", 1);   // 0: keep the 128-row tiles (A/B runs)
         // measured at C2 (B = 64, N = 2048): 768 -> 384 with residual 0.321 -> 0.288 ms; 384 -> 384 and the prologue
         // form 384 -> 768 are 3-8 % slower with the tall tile (fewer, longer blocks; the prologue form spills): long K only
         if (bm256 && g.rows >= 256 && g.rows % 128 == 0 && !g.pro_a && g.K >= 512) return dma_launch_t<3, true, 256>(g, st);

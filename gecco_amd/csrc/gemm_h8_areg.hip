@@ -24,6 +24,7 @@
 // of group g + D are loaded when group g's registers are free.  The K loop is fully unrolled: every wait is a compile-time
 // count (young_at below).
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 #include "h8_scales.h"
 
 #include <stdlib.h>
@@ -300,30 +301,21 @@ int h8_areg_launch8_t(const GemmArgs& g, hipStream_t st) {   // 256-row blocks o
     constexpr int NS = 6, D = NGK >= 3 ? 3 : NGK;
     const int tilesM = g.rows / 256, tilesN = g.Nout / DBN;
     constexpr size_t lds = (size_t)NS * G_STAGE * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h8_areg_kernel<NGK, NS, D, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (const hipError_t e = lds_opt_in<gemm_h8_areg_kernel<NGK, NS, D, true, 8>>(lds)) return (int)e;
     hipLaunchKernelGGL((gemm_h8_areg_kernel<NGK, NS, D, true, 8>), dim3(g.B * tilesM * tilesN), dim3(512), lds, st, g);
     return (int)hipGetLastError();
 }
 
 template <int NGK>
 int h8_areg_launch_t(const GemmArgs& g, hipStream_t st) {
-    static const int w8_env = [] { const char* e = getenv("GECCO_H8AREG_W8"); return e ? atoi(e) : 0; }();
+    static const int w8_env = env_int("GECCO_H8AREG_W8", 0);
     if (w8_env && g.rows % 256 == 0 && g.Nout % 128 == 0) return h8_areg_launch8_t<NGK>(g, st);
     constexpr int NS = 4, D = NGK >= 3 ? 3 : NGK;
     const int tilesM = g.rows / 128, tilesN = (g.Nout + DBN - 1) / DBN;
     constexpr size_t ring = (size_t)NS * G_STAGE, epi = (size_t)D_EPI;
     const size_t lds = (ring > epi ? ring : epi) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h8_areg_kernel<NGK, NS, D, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h8_areg_kernel<NGK, NS, D, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
-    static const int direct_env = [] { const char* e = getenv("GECCO_H8AREG_DIRECT"); return e ? atoi(e) : 0; }();   // measured: epilogue 17.2 K -> 12.7 K ticks per block, prologue + K loop +6.6 K: 197 -> 193 us at K = 768, 125 -> 128 us at K = 384 (profiles/r04d): off
+    if (const hipError_t e = lds_opt_in<gemm_h8_areg_kernel<NGK, NS, D, true>, gemm_h8_areg_kernel<NGK, NS, D, false>>(lds)) return (int)e;
+    static const int direct_env = env_int("GECCO_H8AREG_DIRECT", 0);   // measured: epilogue 17.2 K -> 12.7 K ticks per block, prologue + K loop +6.6 K: 197 -> 193 us at K = 768, 125 -> 128 us at K = 384 (profiles/r04d): off
     // whole 128-column tiles: the no-transpose epilogue; a ragged last tile keeps the masked LDS-transpose one
     if (direct_env && g.Nout % 128 == 0) hipLaunchKernelGGL((gemm_h8_areg_kernel<NGK, NS, D, true>), dim3(g.B * tilesM * tilesN), dim3(DNT), lds, st, g);
     else hipLaunchKernelGGL((gemm_h8_areg_kernel<NGK, NS, D, false>), dim3(g.B * tilesM * tilesN), dim3(DNT), lds, st, g);

@@ -31,6 +31,7 @@
 // v_permlane32_swap per register pair gives every lane 8 consecutive columns = 16 bytes of the hi plane and 16 of the
 // lo plane of the image, a wave-instruction writes 1 KiB of consecutive bytes.
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 #include "h8_scales.h"
 
 #include <stdlib.h>
@@ -1264,11 +1265,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kvq_astat_kernel(GemmArgs g) {
 template <int NG, int NS, int OUT = 0, bool P48 = false>
 int kvq_launch_t(const GemmArgs& g, hipStream_t st) {
     const size_t lds = ((size_t)NS * H_STAGE + 4 * 1024 + g.Nout + 2 * g.K) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kvq_astat_kernel<NG, NS, OUT, P48>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    if (const hipError_t e = lds_opt_in<gemm_kvq_astat_kernel<NG, NS, OUT, P48>>(lds)) return (int)e;
     hipLaunchKernelGGL((gemm_kvq_astat_kernel<NG, NS, OUT, P48>), dim3(g.B * (g.rows / 128)), dim3(256), lds, st, g);
     return (int)hipGetLastError();
 }
@@ -1279,19 +1276,10 @@ template <int NG, int NW, int ACT, bool IMG2>
 int h8_launch_i(const GemmArgs& g, hipStream_t st) {
     constexpr int NS = h8_ns(NG, NW);
     const size_t lds = ((size_t)NS * H_STAGE + NW * H_STG + g.Nout + 2 * g.K) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h8_astat_kernel<NG, NW, NS, ACT, IMG2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    if (const hipError_t e = lds_opt_in<gemm_h8_astat_kernel<NG, NW, NS, ACT, IMG2>>(lds)) return (int)e;
     if constexpr (IMG2 && NW == 4) {
         if (g.h6) {   // the "h6" arithmetic (w_img is the h6 stream)
-            static size_t attr6 = 0;
-            if (lds > attr6) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h8_astat_kernel<NG, NW, NS, ACT, IMG2, 0, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                attr6 = lds;
-            }
+            if (const hipError_t e = lds_opt_in<gemm_h8_astat_kernel<NG, NW, NS, ACT, IMG2, 0, true>>(lds)) return (int)e;
             hipLaunchKernelGGL((gemm_h8_astat_kernel<NG, NW, NS, ACT, IMG2, 0, true>), dim3(g.B * (g.rows / (32 * NW))), dim3(64 * NW), lds, st, g);
             return (int)hipGetLastError();
         }
@@ -1316,11 +1304,6 @@ int h8_launch_t(const GemmArgs& g, hipStream_t st) {
     }
 }
 
-int h8_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 }  // namespace
 
 size_t h8_image_bytes(int Nout, int K) { return (size_t)((Nout + H_BN - 1) / H_BN) * H_BN * K * 4; }
@@ -1335,7 +1318,7 @@ int h8_image_multi_launch(const SplitJobs& jobs, hipStream_t st) {
 
 // GECCO_H8_K512=0: d = 512 keeps mlp.0 on the split-bf16 LDS-DMA GEMM (A/B runs)
 static bool h8_k512_on() {
-    static const int on = h8_env("GECCO_H8_K512", 1);
+    static const int on = env_int("GECCO_H8_K512", 1);
     return on != 0;
 }
 
@@ -1381,12 +1364,7 @@ int h8_train_launch_t(const GemmArgs& g, hipStream_t st) {
     const dim3 grid(g.B * (g.rows / 128));
 #define H8T(ACT_, OUT_)                                                                                                          \
     do {                                                                                                                         \
-        static size_t attr = 0;                                                                                                  \
-        if (lds > attr) {                                                                                                        \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h8_astat_kernel<NG, 4, NS, ACT_, false, OUT_>),          \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                     \
-            attr = lds;                                                                                                          \
-        }                                                                                                                        \
+        if (const hipError_t e = lds_opt_in<gemm_h8_astat_kernel<NG, 4, NS, ACT_, false, OUT_>>(lds)) return (int)e;              \
         hipLaunchKernelGGL((gemm_h8_astat_kernel<NG, 4, NS, ACT_, false, OUT_>), grid, dim3(256), lds, st, g);                    \
     } while (0)
     if (!g.pre_out) H8T(0, 1);
@@ -1445,7 +1423,7 @@ int gemm_astat_train_launch(const GemmArgs& g0, hipStream_t st) {
 
 int gemm_kvq_astat_launch(const GemmArgs& g0, hipStream_t st) {
     if (!gemm_kvq_astat_supported(g0)) return -9;
-    static const int rev = h8_env("GECCO_H8_REV", 0);
+    static const int rev = env_int("GECCO_H8_REV", 0);
     GemmArgs g = g0;
     g.h8_rev = rev;
     switch (g.K) {
@@ -1471,7 +1449,7 @@ int gemm_kvq_astat_launch(const GemmArgs& g0, hipStream_t st) {
 // (measured: no gain, default 0)
 int gemm_h8_astat_launch(const GemmArgs& g0, hipStream_t st) {
     if (!gemm_h8_astat_supported(g0)) return -9;
-    static const int stagger = h8_env("GECCO_H8_STAGGER", 0), pair = h8_env("GECCO_H8_PAIR", 32), rev = h8_env("GECCO_H8_REV", 0);
+    static const int stagger = env_int("GECCO_H8_STAGGER", 0), pair = env_int("GECCO_H8_PAIR", 32), rev = env_int("GECCO_H8_REV", 0);
     GemmArgs g = g0;
     g.h8_rev = rev;
     g.h8_stagger = stagger;

@@ -17,6 +17,7 @@
 // Slab loads are raw buffer loads (one per-lane offset per operand + scalar offsets), the AdaGN coefficients sit in LDS.
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -459,11 +460,7 @@ int tn_f16_shape(int N, int K) {
     // is 19.2 ms against 19.0 (without the side stream: 19.1 against 19.35).  Round 6: with fp16 tensors between the training kernels the
     // balance tips — 16.46 - 16.53 ms with the wide tiles against 16.63 - 16.68 (three runs each, one box): the DEFAULT since;
     // GECCO_TN_F16_WIDE=0 selects 128 x 128.
-    static int wide = -1;
-    if (wide < 0) {
-        const char* e = getenv("GECCO_TN_F16_WIDE");
-        wide = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    static const int wide = env_int("GECCO_TN_F16_WIDE", 1);
     if (!wide) return 0;
     if (K % 256 == 0 && (N % 256 != 0 || K >= N)) return 2;   // 128 x 256
     if (N % 256 == 0) return 1;                              // 256 x 128
@@ -489,13 +486,8 @@ int gemm_tn_f16_tiles(int N, int K) {
 
 int gemm_tn_f16_launch(const TnArgs& g, hipStream_t st) {
     if (!gemm_tn_f16_supported(g)) return -9;
-    static int xcd = -1;
-    if (xcd < 0) {
-        const char* e = getenv("GECCO_TN_XCD");   // 0: plain dispatch order (A/B runs)
-        xcd = (e && atoi(e) == 0) ? 0 : 1;
-    }
     TnArgs ga = g;
-    ga.xcd = xcd;
+    ga.xcd = tn_xcd();
     if (g.a_f16 && g.b_f16) {   // both operands fp16 tensors: the DMA form, whole 128 x 128 tiles (gemm_tn_f16_supported checked)
         const int G = (g.Z + g.group - 1) / g.group;
         const dim3 grid((g.N / 128) * (g.K / 128), G);

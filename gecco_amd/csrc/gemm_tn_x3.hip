@@ -14,6 +14,7 @@
 // fixed order (reduce_batch_kernel): bit-reproducible gradients, 1/8 of the partial traffic of one per sample.
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -195,21 +196,9 @@ int gemm_tn_x3_launch(const TnArgs& g, hipStream_t st) {
     if (!gemm_tn_x3_supported(g)) return -9;
     const int G = (g.Z + g.group - 1) / g.group;
     const size_t lds = (size_t)2 * 4 * TN_PLANE * 2;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_x3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_x3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        attr = true;
-    }
-    static int xcd = -1;
-    if (xcd < 0) {
-        const char* e = getenv("GECCO_TN_XCD");   // 0: plain dispatch order (A/B runs)
-        xcd = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    if (const hipError_t e = lds_opt_in<gemm_tn_x3_kernel<false>, gemm_tn_x3_kernel<true>>(lds)) return (int)e;
     TnArgs ga = g;
-    ga.xcd = xcd;
+    ga.xcd = tn_xcd();
     const dim3 grid(((g.N + 127) / 128) * ((g.K + 127) / 128), G);
     if (g.pro_a) hipLaunchKernelGGL(gemm_tn_x3_kernel<true>, grid, dim3(256), lds, st, ga);
     else hipLaunchKernelGGL(gemm_tn_x3_kernel<false>, grid, dim3(256), lds, st, ga);

@@ -13,6 +13,7 @@
 // consecutive image bytes per instruction) D K-steps ahead into a register ring, the LDS ring holds W alone (8 KiB per
 // stage), and the fragment reads of A disappear from the LDS pipe.
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 
 #include <cstdlib>
 #include <utility>
@@ -156,11 +157,7 @@ template <int BM, int D, int NK>
 int areg_launch_t(const GemmArgs& g, hipStream_t st) {
     const int tilesM = (g.rows + BM - 1) / BM, tilesN = (g.Nout + DBN - 1) / DBN;
     const size_t lds = (size_t)r_main_floats(D) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3_areg_kernel<BM, D, NK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    if (const hipError_t e = lds_opt_in<gemm_x3_areg_kernel<BM, D, NK>>(lds)) return (int)e;
     hipLaunchKernelGGL((gemm_x3_areg_kernel<BM, D, NK>), dim3(g.B * tilesM * tilesN), dim3(DNT), lds, st, g);
     return (int)hipGetLastError();
 }
@@ -182,7 +179,7 @@ int gemm_x3_areg_launch(const GemmArgs& g, hipStream_t st) {
         case 384: {
             // out_proj at d = 384 (K = 384): 64 x 128 wave tiles measured 0.2 % of the evaluation faster than 32 x 128
             // (6.650 vs 6.665 ms, three pairs on one box); GECCO_AREG_TALL384=0 keeps the 128-row tile (A/B runs)
-            static const int tall384 = [] { const char* e = getenv("GECCO_AREG_TALL384"); return e ? atoi(e) : 1; }();
+            static const int tall384 = env_int("GECCO_AREG_TALL384", 1);
             return (tall && tall384) ? areg_launch_t<256, 4, 24>(g, st) : areg_launch_t<128, 4, 24>(g, st);
         }
         case 512: return tall ? areg_launch_t<256, 4, 32>(g, st) : areg_launch_t<128, 4, 32>(g, st);

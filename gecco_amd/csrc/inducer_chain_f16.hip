@@ -27,6 +27,7 @@
 // Rounding points are those of the stand-alone chain (fp16 operands formed by one fma + one rounding, fp32
 // accumulation in the same k order, fp32 h and kvh); GroupNorm column sums are added in a different order (fp32).
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -812,12 +813,7 @@ template <int NT1, int NH, bool TWO, int CL>
 int chain_launch_w(const ChainArgs& g, hipStream_t st) {
     constexpr int C = 128 * NT1, WD = C * NH;
     constexpr size_t lds = chain_lds_bytes(C, WD);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(inducer_chain_f16_kernel<NT1, NH, TWO, CL>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (const hipError_t e = lds_opt_in<inducer_chain_f16_kernel<NT1, NH, TWO, CL>>(lds)) return (int)e;
     hipLaunchKernelGGL((inducer_chain_f16_kernel<NT1, NH, TWO, CL>), dim3(g.B * CL), dim3(CH_NT), lds, st, g);
     return (int)hipGetLastError();
 }

@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include "kernels.h"
+#include "launch_state.h"
 
 #pragma clang fp contract(off)  // index math must round like the reference's separate fp32 ops
 
@@ -718,11 +719,7 @@ int ray_lookup_bwd_sorted_launch(const float* geom, const float* coef, const flo
     ws.wts = reinterpret_cast<float*>(ws.ent + per * ws.P);
     ws.start = reinterpret_cast<int*>(ws.wts + per * ws.P);
     const size_t lds = (size_t)ws.P * sizeof(unsigned);
-    static size_t attr = 0;
-    if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lookup_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
-    }
+    if (const hipError_t e = lds_opt_in<lookup_sort_kernel>(lds)) return (int)e;
     hipLaunchKernelGGL(lookup_sort_kernel, dim3(B * a.n_levels), dim3(SORT_NT), lds, st, geom, coef, K, a, ws, N);
     int coff = 0;
     for (int l = 0; l < a.n_levels; ++l) {

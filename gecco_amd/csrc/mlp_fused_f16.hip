@@ -19,6 +19,7 @@
 // Every rounding point, the k order of every accumulation, (sum + b) + x and the order of the partial sums are those of
 // the two-launch form: bit-identical x and statistics (tests/test_hip_ops.py::test_mlp_fused_matches_the_two_launch_form).
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -413,12 +414,7 @@ template <int NT1>
 int mlpf_launch_t(const MlpArgs& g, hipStream_t st) {
     constexpr int C = 128 * NT1;
     constexpr size_t lds = mf_lds_bytes(C);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fused_f16_kernel<NT1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (const hipError_t e = lds_opt_in<mlp_fused_f16_kernel<NT1>>(lds)) return (int)e;
     hipLaunchKernelGGL((mlp_fused_f16_kernel<NT1>), dim3(g.B * (g.rows / 128)), dim3(MF_NT), lds, st, g);
     return (int)hipGetLastError();
 }
@@ -431,11 +427,7 @@ bool mlp_fused_f16_supported(int C, int Wd, int rows) {
 
 int mlp_fused_f16_launch(const MlpArgs& g0, int C, int Wd, hipStream_t st) {
     if (!mlp_fused_f16_supported(C, Wd, g0.rows)) return -9;
-    static int stagger = -1;   // GECCO_MLP_STAGGER=<cycles> (0: off); 4000 measured best at C2 (0, 2000 .. 16000 tried)
-    if (stagger < 0) {
-        const char* e = getenv("GECCO_MLP_STAGGER");
-        stagger = e ? atoi(e) : 4000;
-    }
+    static const int stagger = env_int("GECCO_MLP_STAGGER", 4000);   // <cycles> (0: off); 4000 measured best at C2 (0, 2000 .. 16000 tried)
     MlpArgs g = g0;
     g.stagger = g.B * (g.rows / 128) >= 512 ? stagger : 0;   // only when there is more than one round of blocks
     switch (C / 128) {

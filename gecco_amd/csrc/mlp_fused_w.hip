@@ -53,6 +53,7 @@
 #include "common.h"
 #include "h8_scales.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 #ifndef MFW_PART
 #define MFW_PART 0
@@ -932,17 +933,9 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
 
 template <int ACT, int NG>
 int mfw_launch_a(const MlpWArgs& g, hipStream_t st) {
-    static bool attr = false;
-    static int cus = 0, forced = 0;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fused_w_kernel<ACT, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, WCfg<NG>::LDS);
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (cus <= 0) cus = 256;
-        if (const char* e = getenv("GECCO_MLPW_CUS")) { const int v = atoi(e); if (v > 0 && v <= cus) forced = v; }
-        attr = true;
-    }
+    if (const hipError_t e = lds_opt_in<mlp_fused_w_kernel<ACT, NG>>(WCfg<NG>::LDS)) return (int)e;
+    static const int cus_env = env_int("GECCO_MLPW_CUS", 0);
+    const int cus = device_cus(), forced = cus_env > 0 && cus_env <= cus ? cus_env : 0;
     // Blocks of a launch: a block of this kernel fills its CU.  When an evaluation runs as two half batches on two streams (hip_ops.py sets
     // option "mlpwshare" around it -> g.share) three quarters of the CUs per launch let the other stream's kernels find free CUs beside
     // it — C2 4.53 -> 4.42 ms per evaluation (192 of 256; 128: 4.43); alone on the device a launch takes every CU (1024 tiles: 4 rounds

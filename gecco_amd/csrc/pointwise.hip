@@ -2,6 +2,7 @@
 // AdaGN coefficient finalisation, EDM preconditioning, lift (3 -> d) and lower (d -> 3).
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -678,10 +679,8 @@ int adagn_coeffs_launch(const float* stats, int T, int rows, const float* t, int
     while (nsl < 8 && (nsl * 2) * Cp <= 1024 && T / (nsl * 2) >= 8) nsl *= 2;
     const int nt = nsl * Cp >= 1024 ? 1024 : (nsl * Cp <= 256 ? 256 : ((nsl * Cp + 63) / 64) * 64);
     const size_t lds = (size_t)(2 * Cp + 2 * (G / parts) + 2 * nsl * Cp) * sizeof(double);
-    static size_t attr = 0;
-    if (lds > 48 * 1024 && lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adagn_coeffs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = lds;
+    if (lds > 48 * 1024) {
+        if (const hipError_t e = lds_opt_in<adagn_coeffs_kernel>(lds)) return (int)e;
     }
     hipLaunchKernelGGL(adagn_coeffs_kernel, dim3(B, parts), dim3(nt), lds, st, stats, T, rows, t, ctx_dim, scale_w, scale_b,
                        bias_w, bias_b, a, o, C, G, eps, nsl, Cp);
@@ -729,11 +728,7 @@ int lower_edm_launch(const float* feat, const float* x, const float* coef, const
 #define LOWER_V4(CPL)                                                                                              \
     hipLaunchKernelGGL((lower_edm_v4_kernel<CPL>), g16, dim3(256), 0, st, feat, x, coef, W, bias, gn_a, gn_o, out, raw, \
                        B, N, C, eps)
-    static int v5 = -1;
-    if (v5 < 0) {
-        const char* e = getenv("GECCO_LOWER_V5");   // 0: one row per 16-lane group (A/B runs)
-        v5 = (e && atoi(e) == 0) ? 0 : 1;
-    }
+    static const int v5 = env_int("GECCO_LOWER_V5", 1);   // 0: one row per 16-lane group (A/B runs)
     constexpr int RPG = 8;
     if (v5 && C % 4 == 0 && cpl <= 8 && rows >= 16 * RPG * 512) {   // enough 128-row blocks to fill the chip twice
         const dim3 g5((unsigned)((rows + 16 * RPG - 1) / (16 * RPG)));

@@ -37,6 +37,7 @@
 #include "../../include/gecco_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "launch_state.h"
 #include "pair_dist.h"
 
 namespace {
@@ -326,9 +327,7 @@ int sinkhorn_resident_launch(const float* A, const float* Bc, float* f, float* g
     if (pairs <= 0 || N < 1 || M < 1 || (long long)N + M > GECCO_SINKHORN_RESIDENT_MAX_POINTS || (set_mode && T <= 0) || iterations < 1 ||
         !(eps > 0.f))
         return -2;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(sk_resident_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       SK_LDS_BYTES - SK_RES_STATIC);
-    if (attr != hipSuccess) return (int)attr;
+    if (const hipError_t e = lds_opt_in<sk_resident_kernel>(SK_LDS_BYTES - SK_RES_STATIC)) return (int)e;
     const SkScale sc(eps);
     hipLaunchKernelGGL(sk_resident_kernel, dim3(pairs), dim3(SK_RES_THREADS), (size_t)SK_PER_POINT * (N + M) + SK_RES_SCRATCH, st, A, Bc, f, g, out,
                        N, M, T, set_mode, sc.k, sc.inv_k, iterations);

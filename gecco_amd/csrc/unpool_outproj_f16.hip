@@ -15,6 +15,7 @@
 //     residual x, store, per-(sample, row tile, column) GroupNorm partials.
 // Bit-identical to unpool_attn_x3_kernel<hd, fp16, io16> followed by gemm_f16_kernel (fp16 A, residual, stats).
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 
 #include <stdlib.h>
 
@@ -413,12 +414,7 @@ template <int NT1, int HD>
 int uo_launch_t(const UnpoolProjArgs& g, hipStream_t st) {
     constexpr int C = 128 * NT1;
     constexpr size_t lds = uo_lds_bytes(C, HD);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(unpool_outproj_f16_kernel<NT1, HD>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (const hipError_t e = lds_opt_in<unpool_outproj_f16_kernel<NT1, HD>>(lds)) return (int)e;
     hipLaunchKernelGGL((unpool_outproj_f16_kernel<NT1, HD>), dim3(g.B * (g.rows / 128)), dim3(MF_NT), lds, st, g);
     return (int)hipGetLastError();
 }
@@ -434,11 +430,7 @@ bool unpool_outproj_f16_supported(int C, int H, int rows) {
 
 int unpool_outproj_f16_launch(const UnpoolProjArgs& g0, int C, hipStream_t st) {
     if (!unpool_outproj_f16_supported(C, g0.H, g0.rows)) return -9;
-    static int stagger = -1;   // GECCO_UNPOOL_STAGGER=<cycles> (0: off)
-    if (stagger < 0) {
-        const char* e = getenv("GECCO_UNPOOL_STAGGER");
-        stagger = e ? atoi(e) : 4000;
-    }
+    static const int stagger = env_int("GECCO_UNPOOL_STAGGER", 4000);   // <cycles> (0: off)
     UnpoolProjArgs g = g0;
     g.stagger = g.B * (g.rows / 128) >= 512 ? stagger : 0;
     switch (C) {

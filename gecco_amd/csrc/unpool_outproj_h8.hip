@@ -27,6 +27,7 @@
 //
 // HBM per launch at C2: q 100 MB + x in 201 MB + x out 201 MB (the 151 MB image written + read before never leaves the CU).
 #include "gemm_dma_common.h"
+#include "launch_state.h"
 #include "h8_scales.h"
 
 #include <stdlib.h>
@@ -552,11 +553,7 @@ int uo8_launch_t(const UnpoolH8Args& g, hipStream_t st) {
     constexpr int C = 64 * NG;
     constexpr size_t lds = ((size_t)NS * U_STAGE + u_tts_floats(HD) + C + 4 * 2 * 64) * sizeof(float);
     static_assert(lds <= 80 * 1024 || NG > 6, "two blocks per CU");
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(unpool_outproj_h8_kernel<NG, HD, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
+    if (const hipError_t e = lds_opt_in<unpool_outproj_h8_kernel<NG, HD, NS>>(lds)) return (int)e;
     hipLaunchKernelGGL((unpool_outproj_h8_kernel<NG, HD, NS>), dim3(g.B * (g.rows / 128)), dim3(256), lds, st, g);
     return (int)hipGetLastError();
 }
@@ -567,7 +564,7 @@ int uo8_launch_t(const UnpoolH8Args& g, hipStream_t st) {
 bool unpool_outproj_h8_supported(int C, int H, int rows) {
     if (rows < 128 || rows % 128 || H <= 0 || C % H) return false;
     const int hd = C / H;
-    static const int k512 = [] { const char* e = getenv("GECCO_UO8_K512"); return e ? atoi(e) : 1; }();   // 0: d = 512 keeps the two launches
+    static const int k512 = env_int("GECCO_UO8_K512", 1);   // 0: d = 512 keeps the two launches
     return (C == 128 && hd == 16) || (C == 256 && hd == 32) || (C == 384 && hd == 48) || (C == 512 && hd == 64 && k512);
 }
 
@@ -582,22 +579,13 @@ int kvh_image_launch(const float* kvh, void* img, int B, int C, int H, hipStream
 
 int unpool_outproj_h8_launch(const UnpoolH8Args& g0, int C, hipStream_t st) {
     if (!unpool_outproj_h8_supported(C, g0.H, g0.rows)) return -9;
-    static int rev = -1;   // GECCO_UO8_REV=0: blocks walk the row panels first to last
-    if (rev < 0) {
-        const char* e = getenv("GECCO_UO8_REV");
-        rev = e ? (atoi(e) != 0) : 1;
-    }
-    static int stagger = -1, pair = 32;   // GECCO_UO8_STAGGER=<ticks>, GECCO_UO8_PAIR=<blocks per XCD between the two blocks of a CU>
-    if (stagger < 0) {
-        const char* e = getenv("GECCO_UO8_STAGGER");
-        stagger = e ? atoi(e) : 0;
-        const char* e2 = getenv("GECCO_UO8_PAIR");
-        pair = e2 && atoi(e2) > 0 ? atoi(e2) : 32;
-    }
+    static const int rev = env_int("GECCO_UO8_REV", 1);           // 0: blocks walk the row panels first to last
+    static const int stagger = env_int("GECCO_UO8_STAGGER", 0);   // <ticks>
+    static const int pair = env_int("GECCO_UO8_PAIR", 32);        // <blocks per XCD between the two blocks of a CU>
     UnpoolH8Args g = g0;
-    g.rev = rev;
+    g.rev = rev != 0;
     g.stagger = g.B * (g.rows / 128) >= 512 ? stagger : 0;
-    g.pair = pair;
+    g.pair = pair > 0 ? pair : 32;
     switch (C) {
         case 128: return uo8_launch_t<2, 16, 4>(g, st);
         case 256: return uo8_launch_t<4, 32, 5>(g, st);

@@ -2,6 +2,9 @@
 carry no process-wide state (models/set_transformer.py:176-216, diffusion.py:160-178) — two models of different arithmetic in one
 serving process must not see each other.  Plus the hand-overs that used to leave `images_ready = 1` behind images that were never
 (re)built: an EMA swap inside a scope, a first forward that was only captured into a graph."""
+import os
+import subprocess
+import sys
 import threading
 
 import pytest
@@ -82,6 +85,52 @@ def test_two_plans_interleaved_inside_one_frozen_scope(ops):
     [t.start() for t in ts]
     [t.join() for t in ts]
     assert not errs, errs
+
+
+def _cold_start_two_threads():
+    """The child of the test below: the process's FIRST library calls come from two host threads at once."""
+    from gecco_amd import hip_ops
+    p, x, sigma = cases.uncond_inputs("uncond_d384_L6_N128")
+    p = _cuda(p)
+    x, sigma = x.cuda(), sigma.cuda()
+    torch.cuda.synchronize()
+    gate = threading.Barrier(2)
+    plans, got, errs = {}, {}, []
+
+    def worker(mode):
+        try:
+            s = torch.cuda.Stream()
+            gate.wait(timeout=60)
+            with torch.cuda.stream(s):
+                plans[mode] = hip_ops.LinearLiftPlan(p, cases.H, cases.I, precision=mode)
+                got[mode] = [tuple(t.clone() for t in plans[mode].forward(x, sigma, return_raw=True)) for _ in range(2)]
+            s.synchronize()
+        except Exception as e:   # noqa: BLE001
+            errs.append((mode, repr(e)))
+    ts = [threading.Thread(target=worker, args=(mode,)) for mode in ("w2", "mixed")]
+    [t.start() for t in ts]
+    [t.join() for t in ts]
+    assert not errs, errs
+    for mode in ("w2", "mixed"):
+        serial = plans[mode].forward(x, sigma, return_raw=True)
+        torch.cuda.synchronize()
+        for k, run in enumerate(got[mode]):
+            assert torch.equal(run[0], serial[0]) and torch.equal(run[1], serial[1]), (mode, k)
+    assert not torch.equal(got["w2"][0][1], got["mixed"][0][1])   # they are different arithmetics
+    print("cold start ok")
+
+
+def test_cold_start_from_two_threads(ops, tmp_path):
+    """The launchers' first-call state (the dynamic-LDS opt-in, the CU count, the cached knobs, the option table: csrc/launch_state.h)
+    holds when the process's first library calls come from two host threads at the same time, each on its own stream: one in `w2`
+    (the one-launch MLP: 160 KiB of LDS and a grid sized by the CU count), one in `mixed` (the h8 launchers).  A fresh child process,
+    since this one has warmed every launcher.  Each thread's two results equal each other and the same plan run serially afterwards."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    log = tmp_path / "cold_start.log"
+    with open(log, "w") as f:
+        r = subprocess.run([sys.executable, "-c", "from tests.test_hip_plan_state import _cold_start_two_threads as go; go()"], cwd=root,
+                           stdout=f, stderr=subprocess.STDOUT, timeout=300)
+    assert r.returncode == 0, log.read_text()[-4000:]
 
 
 def test_scope_by_plan_freezes_only_that_plan(ops):
