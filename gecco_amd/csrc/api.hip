@@ -2270,6 +2270,25 @@ int gecco_sinkhorn_cloud_bwd_f32(const float* a, const float* b, const float* f,
     return 0;
 }
 
+// farthest-point sampling (fps.hip).  form: 0 auto (resident within GECCO_FPS_RESIDENT_MAX_POINTS), 1 resident, 2 streaming
+int gecco_fps_f32(const float* points, const int* start, int* idx, float* sel2, void* ws, int B, int N, int k, int form, void* stream) {
+    if (!points || !idx) return fail(-1, "fps: null argument");
+    if (B < 1 || N < 1 || k < 1) return fail(-2, "fps: B = %d, N = %d, k = %d must all be >= 1", B, N, k);
+    if (k > N) return fail(-2, "fps: k = %d above N = %d", k, N);
+    if (form < 0 || form > 2) return fail(-2, "fps: form = %d is not 0 (auto), 1 (resident) or 2 (streaming)", form);
+    const bool fits = N <= GECCO_FPS_RESIDENT_MAX_POINTS;
+    if (form == 1 && !fits) return fail(-2, "fps: the resident form takes N <= %d (got %d)", GECCO_FPS_RESIDENT_MAX_POINTS, N);
+    if (form == 1 || (form == 0 && fits)) {
+        TRY(fps_resident_launch(points, start, idx, sel2, B, N, k, (hipStream_t)stream), "fps(resident)");
+        return 0;
+    }
+    if (!ws) return fail(-1, "fps: the streaming form needs ws");
+    if ((long long)B * ((N + GECCO_FPS_STREAM_SLICE - 1) / GECCO_FPS_STREAM_SLICE) > 0x7fffffffLL)
+        return fail(-2, "fps: B * ceil(N / %d) workgroups above 2^31 - 1", GECCO_FPS_STREAM_SLICE);
+    TRY(fps_stream_launch(points, start, idx, sel2, ws, B, N, k, (hipStream_t)stream), "fps(streaming)");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- ConvNeXt conditioner (channels-last)
 int gecco_convnext_stem_f32(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out,
                             int B, int H, int W, int C, float eps, void* stream) {

@@ -481,6 +481,10 @@ int sinkhorn_stream_launch(const float* A, const float* Bc, float* f, float* g, 
                            int iterations, hipStream_t st);
 int sinkhorn_bwd_launch(const float* A, const float* Bc, const float* f, const float* g, const float* gout, float* dA, float* dB, int B, int N,
                         int M, float eps, hipStream_t st);
+// fps.hip — farthest-point sampling (definition: gecco_fps_f32).  resident: one workgroup per cloud, all k steps in one launch
+// (N <= GECCO_FPS_RESIDENT_MAX_POINTS); stream: any N, one launch per selected point, ws of GECCO_FPS_WORKSPACE_BYTES(B, N).  start, sel2 nullable
+int fps_resident_launch(const float* points, const int* start, int* idx, float* sel2, int B, int N, int k, hipStream_t st);
+int fps_stream_launch(const float* points, const int* start, int* idx, float* sel2, void* ws, int B, int N, int k, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

@@ -874,6 +874,33 @@ int gecco_set_sinkhorn_f32(const float* a, const float* b, float* out, int S, in
  * both) may be null.  B, N, M >= 1 (B <= 65535). */
 int gecco_sinkhorn_cloud_bwd_f32(const float* a, const float* b, const float* f, const float* g, const float* gout, float* da, float* db,
                                  int B, int N, int M, float epsilon, void* stream);
+/* Farthest-point sampling of 3-D clouds (csrc/fps.hip): k of the N points of each cloud of points (B, N, 3), each the point farthest from
+ * those chosen before it.  It replaces the random cut the reference's loaders make (gecco-jax data/torch_shapenet.py:20-21 and
+ * data/taskonomy.py:84: `randperm[:n_points]`) where a well-spread subset is wanted.  Definition, per cloud, with s_0 = start[b]:
+ *     d_i = +inf for all i;  for t = 0 .. k-1:
+ *         idx[t] = s_t;  sel2[t] = d_{s_t}    (+inf at t = 0: the squared distance from s_t to the points chosen before it)
+ *         d_i = min(d_i, dist2(p_i, p_{s_t})) for all i
+ *         s_{t+1} = argmax_i d_i, the LOWEST index among equal maxima
+ * dist2(a, b) = (dx*dx + dy*dy) + dz*dz on dx = a.x - b.x, ..., every operation rounded to fp32 and no FMA contraction: the roundings
+ * are the definition (runners-up come within 5e-6 relative of a winner), and a numpy float32 restatement gives the same indices.
+ * Duplicate points: a chosen point has d = 0; once every d is 0 the lowest index wins again and indices repeat (ten identical points,
+ * start 3, k = 4: 3, 0, 0, 0) — documented behaviour, not an error.  NaN coordinates: the selection is unspecified; a candidate enters
+ * with `>`, so a NaN never wins, every index stays in [0, N) and the kernels terminate; other clouds of the batch are untouched.
+ * start (B) int32 or NULL (= 0 for every cloud); a start outside [0, N) cannot be checked on the host: the kernel clamps it into
+ * [0, N).  idx (B, k) int32; sel2 (B, k) fp32 or NULL; every element of both is written.  1 <= k <= N.
+ * form 0: auto (resident when it fits), 1: resident (N <= GECCO_FPS_RESIDENT_MAX_POINTS: one workgroup per cloud, one launch for all
+ * clouds and steps, coordinates and d in registers, a copy of the coordinates in LDS), 2: streaming (any N: workgroups of
+ * GECCO_FPS_STREAM_SLICE points share a cloud, ONE launch per selected point, no workgroup waits on another inside a kernel).
+ * ws: GECCO_FPS_WORKSPACE_BYTES(B, N) bytes, 8-byte aligned, = 4 B N (the running d, rounded up to 8) + 16 B ceil(N /
+ * GECCO_FPS_STREAM_SLICE) (two buffers of per-workgroup winners); NULL is allowed when the resident form runs.  The workspace is never
+ * read before it is written.  The argmax is a maximum of integer keys (d's bits, then ~index): no float atomics, no order to fix, the
+ * same bits run to run, in any batch position and in both forms.  Asynchronous on `stream`, no allocation, no synchronisation.
+ * The limit: 1024 threads * 8 points in registers (their LDS copy, 16 B per point, is 128 KiB of a CU's 160). */
+#define GECCO_FPS_RESIDENT_MAX_POINTS 8192
+#define GECCO_FPS_STREAM_SLICE 1024
+#define GECCO_FPS_WORKSPACE_BYTES(B, N) \
+    ((((size_t)(B) * (size_t)(N) * 4 + 7) & ~(size_t)7) + (size_t)16 * (size_t)(B) * (((size_t)(N) + GECCO_FPS_STREAM_SLICE - 1) / GECCO_FPS_STREAM_SLICE))
+int gecco_fps_f32(const float* points, const int* start, int* idx, float* sel2, void* ws, int B, int N, int k, int form, void* stream);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
