@@ -2289,6 +2289,28 @@ int gecco_fps_f32(const float* points, const int* start, int* idx, float* sel2, 
     return 0;
 }
 
+// k-nearest neighbours (knn.hip).  form: 0 auto (knn_launch's rule; without ws it is the direct form), 1 direct, 2 split
+size_t gecco_knn_workspace_bytes(int B, int M, int N, int k) {
+    if (B < 1 || M < 1 || N < 1 || k < 1) return 0;
+    return GECCO_KNN_WORKSPACE_BYTES(B, M, N, k);
+}
+int gecco_knn_f32(const float* query, const float* ref, int32_t* idx, float* d2, void* ws, int B, int M, int N, int k, int exclude_self,
+                  int form, void* stream) {
+    if (!query || !ref || !idx) return fail(-1, "knn: null argument");
+    if (B < 1 || M < 1 || N < 1) return fail(-2, "knn: B = %d, M = %d, N = %d must all be >= 1", B, M, N);
+    if (k < 1 || k > GECCO_KNN_MAX_K) return fail(-2, "knn: k = %d is not in 1 .. %d", k, GECCO_KNN_MAX_K);
+    if (exclude_self && M != N) return fail(-2, "knn: exclude_self needs the query cloud to be the reference cloud (M = %d, N = %d)", M, N);
+    if (k > N - (exclude_self ? 1 : 0))
+        return fail(-2, "knn: k = %d above the %d candidates of a query (N = %d%s)", k, N - (exclude_self ? 1 : 0), N,
+                    exclude_self ? ", itself excluded" : "");
+    if (form < 0 || form > 2) return fail(-2, "knn: form = %d is not 0 (auto), 1 (direct) or 2 (split)", form);
+    if (form == 2 && !ws) return fail(-1, "knn: the split form needs ws");
+    const int rc = knn_launch(query, ref, idx, d2, ws, B, M, N, k, exclude_self ? 1 : 0, form, (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "knn: the grid for B = %d, M = %d, N = %d passes 2^31 - 1 workgroups", B, M, N);
+    TRY(rc, "knn");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- ConvNeXt conditioner (channels-last)
 int gecco_convnext_stem_f32(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out,
                             int B, int H, int W, int C, float eps, void* stream) {

@@ -485,6 +485,10 @@ int sinkhorn_bwd_launch(const float* A, const float* Bc, const float* f, const f
 // (N <= GECCO_FPS_RESIDENT_MAX_POINTS); stream: any N, one launch per selected point, ws of GECCO_FPS_WORKSPACE_BYTES(B, N).  start, sel2 nullable
 int fps_resident_launch(const float* points, const int* start, int* idx, float* sel2, int B, int N, int k, hipStream_t st);
 int fps_stream_launch(const float* points, const int* start, int* idx, float* sel2, void* ws, int B, int N, int k, hipStream_t st);
+// knn.hip — k nearest neighbours (definition: gecco_knn_f32).  form 0 auto / 1 direct / 2 split; ws of GECCO_KNN_WORKSPACE_BYTES(B, M, N, k)
+// for the split form (auto without ws runs the direct form); d2 nullable.  -3: the grid would pass 2^31 - 1 workgroups
+int knn_launch(const float* query, const float* ref, int* idx, float* d2, void* ws, int B, int M, int N, int k, int exclude_self, int form,
+               hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

@@ -1,4 +1,5 @@
-"""Point-cloud operators on the HIP device: farthest-point sampling (csrc/fps.hip, gecco_fps_f32).
+"""Point-cloud operators on the HIP device: farthest-point sampling (csrc/fps.hip, gecco_fps_f32) and k-nearest-neighbour search
+(csrc/knn.hip, gecco_knn_f32) with the statistical outlier filter built on it.
 
 The reference reduces a dense cloud to a fixed size by random permutation (gecco-jax data/torch_shapenet.py:20-21, data/taskonomy.py:84),
 which keeps density clumps and loses thin structure.  `farthest_point_sample` is the well-spread cut: from a start point, each next point
@@ -16,6 +17,27 @@ Two forms.  "resident": one workgroup per cloud and one launch for the whole bat
 registers; N <= FPS_RESIDENT_MAX_POINTS (8192: every evaluation and training shape).  "streaming": any N, the running distances in a
 workspace, several workgroups per cloud and ONE launch per selected point (no workgroup ever waits on another, so the chain cannot hang);
 the 100 000-point output of `Diffusion.upsample` is its case.  form=None takes the resident form when N fits and the streaming form above.
+
+k nearest neighbours (`knn`, `knn_gather`, `statistical_outlier_mask`).  The reference has no neighbourhood query; the route without
+this module is `metrics.distance_matrix` + `torch.topk`, an M x N matrix (40 GB for a 100 000-point cloud against itself) of
+aa + bb - 2ab distances whose cancellation noise reorders near neighbours.  Definition (include/gecco_hip.h; tests/_knn_ref.py restates
+it in numpy float32).  For queries q_i (i < M) and reference points p_j (j < N) of the same batch element,
+    dist2(q, p) = (dx*dx + dy*dy) + dz*dz
+on the coordinate differences, every operation rounded to fp32 without FMA contraction (the spelling of the sampling above).  A NaN dist2
+is replaced by +inf.  The pairs of query i are ordered by (dist2, j) ascending, equal distances going to the LOWEST index, and the result is
+the first k pairs in that order: idx[i, t], and d2[i, t] non-decreasing in t.  Self mode (the query cloud is the reference cloud and
+exclude_self is set) skips the pair j == i by index, not by distance, so exact duplicates of a point remain candidates at distance 0.
+On the 6 x 6 x 6 integer grid (meshgrid(indexing="ij").reshape(-1, 3)) in self mode with k = 7, query 0 gets [1, 6, 36, 7, 37, 42, 43]
+with d2 = [1, 1, 1, 2, 2, 2, 3] and query 215 gets [179, 209, 214, 173, 178, 208, 172]; without self exclusion, k = 4, query 0 gets
+[0, 1, 6, 36].  Ten identical points, query 3, k = 4: self mode gives [0, 1, 2, 4], all at distance 0; without exclusion [0, 1, 2, 3].
+Indices are always in [0, N).  A NaN coordinate affects only the rows and candidates it touches: a NaN reference point is chosen only
+after every finite one, a NaN query returns [0, 1, ..., k-1] (in self mode the first k indices other than its own) with dist = +inf, other
+batch elements are untouched.  The outputs are the same bits run to run, in any batch position and in both kernel forms: the order is that
+of one monotone integer key per pair (dist2's bits above j), so there are no float atomics and the merge of the split form is exact.
+Two forms.  "direct": one launch, one thread per query, the reference cloud streamed through LDS.  "split": few queries against many
+points (M = 2048 conditioning points against the upsampler's N = 100 000): the reference cloud is cut into slices of KNN_SPLIT_SLICE
+points, one launch finds each slice's k best, a second merges them.  form=None takes the split form when the direct grid would leave
+compute units idle and N spans more than one slice.  1 <= k <= KNN_MAX_K.
 HIP tensors only: there is no CPU fallback."""
 from __future__ import annotations
 
@@ -30,6 +52,9 @@ from .hip_ops import _ptr, _stream
 FPS_RESIDENT_MAX_POINTS = 8192   # GECCO_FPS_RESIDENT_MAX_POINTS: 1024 threads * 8 points in registers
 _FPS_STREAM_SLICE = 1024         # GECCO_FPS_STREAM_SLICE: points per workgroup of the streaming form
 _FPS_FORMS = {None: 0, "resident": 1, "streaming": 2}
+KNN_MAX_K = 64                   # GECCO_KNN_MAX_K
+KNN_SPLIT_SLICE = 4096           # GECCO_KNN_SPLIT_SLICE: reference points per slice of the split form
+_KNN_FORMS = {None: 0, "direct": 1, "split": 2}
 
 
 def _fps_workspace_bytes(B: int, N: int) -> int:
@@ -102,3 +127,97 @@ def farthest_point_subsample(points: Tensor, k: int, start=0, form: str | None =
     idx, _ = _fps(p, k, start, False, form)
     out = p.gather(1, idx.long()[:, :, None].expand(-1, -1, 3))
     return out[0] if single else out
+
+
+def _knn_workspace_bytes(B: int, M: int, N: int, k: int) -> int:
+    """GECCO_KNN_WORKSPACE_BYTES(B, M, N, k)"""
+    return 8 * B * M * k * ((N + KNN_SPLIT_SLICE - 1) // KNN_SPLIT_SLICE)
+
+
+def _knn(q: Tensor, r: Tensor | None, k: int, exclude_self: bool, want_d2: bool, form):
+    """q (B, M, 3), r (B, N, 3) or None (= q) of any float dtype / strides -> idx (B, M, k) int32, d2 (B, M, k) fp32 or None"""
+    if form not in _KNN_FORMS:
+        raise ValueError("form must be None, 'direct' or 'split'")
+    B, M, _ = q.shape
+    k = int(k)
+    if r is not None and r.shape[0] != B:
+        raise ValueError(f"query has {B} clouds, ref has {r.shape[0]}")
+    N = M if r is None else r.shape[1]
+    if B < 1 or M < 1 or N < 1:
+        raise ValueError("empty batch or cloud")
+    if exclude_self and M != N:
+        raise ValueError(f"exclude_self needs the query cloud to be the reference cloud (M = {M}, N = {N})")
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k = {k} is not in 1 .. {KNN_MAX_K}")
+    if k > N - int(exclude_self):
+        raise ValueError(f"k = {k} above the {N - int(exclude_self)} candidates of a query")
+    x = q.detach().float().contiguous()
+    px = _ptr(x)   # HIP tensors only: there is no CPU fallback
+    if r is None or r is q:
+        y, py = x, px
+    else:
+        y = r.detach().float().contiguous()
+        py = _ptr(y)
+    idx = torch.empty(B, M, k, device=x.device, dtype=torch.int32)
+    d2 = torch.empty(B, M, k, device=x.device, dtype=torch.float32) if want_d2 else None
+    # a workspace is offered where knn_launch's auto rule can take the split form; the library decides
+    slices = (N + KNN_SPLIT_SLICE - 1) // KNN_SPLIT_SLICE
+    offer = form == "split" or (form is None and slices > 1
+                                and B * ((M + 63) // 64) < torch.cuda.get_device_properties(x.device).multi_processor_count)
+    ws = torch.empty(_knn_workspace_bytes(B, M, N, k), device=x.device, dtype=torch.uint8) if offer else None
+    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+    _lib.check(_lib.load().gecco_knn_f32(px, py, vp(idx), _ptr(d2), vp(ws), B, M, N, k, int(bool(exclude_self)), _KNN_FORMS[form],
+                                         _stream()), "gecco_knn_f32")
+    return idx, d2
+
+
+def knn(query: Tensor, ref: Tensor | None = None, k: int = 16, exclude_self: bool | None = None, return_distances: bool = True,
+        form: str | None = None):
+    """The k nearest points of `ref` to every point of `query` (module docstring: the definition).  query (B, M, 3) or (M, 3), ref
+    (B, N, 3) or (N, 3) on the HIP device, any float dtype and strides (computed on fp32 contiguous copies).  ref=None: the query cloud
+    itself, and exclude_self then defaults to True (a point is not its own neighbour); with a ref it defaults to False.  Returns idx, int64
+    (B, M, k) — (M, k) for single clouds — and, with return_distances, dist = sqrt(dist2), fp32 of the same shape, non-decreasing along
+    k.  form None / "direct" / "split": same bits either way.  ValueError for bad shapes, k outside 1 .. KNN_MAX_K or above the candidates
+    of a query, mismatched batch sizes, exclude_self with a ref of another size, an unknown form; GeccoHipError for CPU tensors.  No
+    gradient: indices (and the distances are detached)."""
+    q, single = _cloud(query)
+    r = None
+    if ref is not None:
+        r, rsingle = _cloud(ref)
+        if rsingle != single:
+            raise ValueError("query and ref must both be batched (B, ., 3) or both single (., 3)")
+    if exclude_self is None:
+        exclude_self = ref is None
+    idx, d2 = _knn(q, r, k, bool(exclude_self), return_distances, form)
+    idx = idx.long()
+    if single:
+        idx = idx[0]
+    if not return_distances:
+        return idx
+    dist = d2.sqrt()
+    return idx, (dist[0] if single else dist)
+
+
+def knn_gather(values: Tensor, idx: Tensor) -> Tensor:
+    """values (B, N, C) gathered along idx (B, M, k) of `knn` -> (B, M, k, C): out[b, i, t] = values[b, idx[b, i, t]].  A plain torch
+    gather, so gradients flow to the gathered rows (a row's gradient is summed over every (i, t) that picked it)."""
+    if values.dim() != 3 or idx.dim() != 3 or idx.shape[0] != values.shape[0] or idx.is_floating_point() or idx.is_complex():
+        raise ValueError("expected values (B, N, C) and integer idx (B, M, k)")
+    if not values.is_cuda or not idx.is_cuda:
+        raise _lib.GeccoHipError("gecco_amd operators need tensors on the HIP device (no CPU fallback)")
+    B, M, k = idx.shape
+    Cn = values.shape[2]
+    return values.gather(1, idx.long().reshape(B, M * k, 1).expand(-1, -1, Cn)).view(B, M, k, Cn)
+
+
+def statistical_outlier_mask(points: Tensor, k: int = 16, std_ratio: float = 2.0, return_scores: bool = False):
+    """The statistical outlier filter of PCL / Open3D on `knn`: score_i = the mean distance of point i to its k nearest neighbours (itself
+    excluded); per cloud keep_i = score_i <= mean(score) + std_ratio * std(score), the sample standard deviation.  points (B, N, 3) or
+    (N, 3) -> a bool mask (B, N) or (N,), True for the points to keep; with return_scores also the fp32 scores of the same shape."""
+    p, single = _cloud(points)
+    _, d2 = _knn(p, None, k, True, True, None)
+    score = d2.sqrt().mean(-1)
+    keep = score <= score.mean(-1, keepdim=True) + float(std_ratio) * score.std(-1, keepdim=True)
+    if single:
+        keep, score = keep[0], score[0]
+    return (keep, score) if return_scores else keep

@@ -19,6 +19,7 @@
 #ifndef GECCO_HIP_H
 #define GECCO_HIP_H
 #include <stddef.h>
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -901,6 +902,45 @@ int gecco_sinkhorn_cloud_bwd_f32(const float* a, const float* b, const float* f,
 #define GECCO_FPS_WORKSPACE_BYTES(B, N) \
     ((((size_t)(B) * (size_t)(N) * 4 + 7) & ~(size_t)7) + (size_t)16 * (size_t)(B) * (((size_t)(N) + GECCO_FPS_STREAM_SLICE - 1) / GECCO_FPS_STREAM_SLICE))
 int gecco_fps_f32(const float* points, const int* start, int* idx, float* sel2, void* ws, int B, int N, int k, int form, void* stream);
+/* k-nearest-neighbour search between 3-D clouds (csrc/knn.hip): for every query q_i (i < M) of query (B, M, 3) the k points p_j (j < N)
+ * of ref (B, N, 3), same batch element, that are nearest to it.  The reference has no neighbourhood query; without this entry the only
+ * route is an M x N distance matrix and a top-k over it.  Definition:
+ *     dist2(q, p) = (dx*dx + dy*dy) + dz*dz    on dx = q.x - p.x, ..., every operation rounded to fp32 and no FMA contraction (the
+ *                                              spelling of gecco_fps_f32, NOT pair_dist.h's aa + bb - 2ab, whose cancellation noise
+ *                                              reorders near neighbours); a NaN dist2 is replaced by +inf
+ *     the pairs of query i are ordered by (dist2, j) ascending: equal distances go to the LOWEST index
+ *     idx[i, t], d2[i, t] (t < k) = the first k pairs in that order; d2 is non-decreasing in t
+ * exclude_self != 0 (self mode; the query cloud is the reference cloud, M == N required): the pair j == i is skipped by index, not by
+ * distance, so exact duplicates of a point remain candidates at distance 0.  Worked examples (a numpy float32 restatement,
+ * tests/_knn_ref.py, gives the same): on the 6 x 6 x 6 integer grid (meshgrid(indexing="ij").reshape(-1, 3)) in self mode with k = 7,
+ * query 0 gets 1, 6, 36, 7, 37, 42, 43 with d2 = 1, 1, 1, 2, 2, 2, 3 and query 215 gets 179, 209, 214, 173, 178, 208, 172; without self
+ * exclusion, k = 4, query 0 gets 0, 1, 6, 36.  Ten identical points, query 3, k = 4: self mode gives 0, 1, 2, 4, all at distance 0;
+ * without exclusion 0, 1, 2, 3.  Indices are always in [0, N).  A NaN coordinate affects only the rows and candidates it touches: a NaN
+ * reference point is chosen only after every finite one, a NaN query returns 0, 1, ..., k-1 (in self mode the first k indices other than
+ * its own) with d2 = +inf, other batch elements are untouched.
+ * The order is the order of ONE monotone integer key per pair (dist2's bits above j), so it is total and the split form's merge is
+ * exact: the outputs are the same bits run to run, in any batch position and in both forms; no float atomics, and no workgroup ever
+ * waits on another.
+ * idx (B, M, k) int32 and d2 (B, M, k) fp32 or NULL: every element is written.  query == ref is allowed.
+ * 1 <= k <= GECCO_KNN_MAX_K, k <= N (k <= N - 1 in self mode); any M, N >= 1; B clouds with the same M and N.
+ * form 1: "direct", one launch, one thread per query, the reference cloud streamed through LDS tiles, the running k-best list of a
+ * thread in LDS with its worst key in registers (a candidate no better than it costs one compare).  form 2: "split", for few queries
+ * against many points: the reference cloud is cut into slices of GECCO_KNN_SPLIT_SLICE points, a first launch over (query tile x slice)
+ * writes each slice's k best keys to ws, a second launch merges the slices of each query; both are ordinary grids.  form 0: auto =
+ * split when ws is given, N spans more than one slice and the direct grid (64 queries per workgroup) would leave compute units idle;
+ * direct otherwise (a rule fitted to M = 2048, N = 100 000: DESIGN.md).
+ * ws: gecco_knn_workspace_bytes(B, M, N, k) = GECCO_KNN_WORKSPACE_BYTES(B, M, N, k) bytes, 8-byte aligned = 8 B M k ceil(N /
+ * GECCO_KNN_SPLIT_SLICE); NULL is allowed when the direct form runs (form 0 with NULL runs the direct form).  The workspace is never read
+ * before it is written.  Negative return (and gecco_last_error) before anything is enqueued for: null query / ref / idx, non-positive
+ * sizes, k out of range, exclude_self with M != N, an unknown form, form 2 without ws.  Asynchronous on `stream`, no allocation, no
+ * synchronisation.  gecco_knn_workspace_bytes needs no GPU and returns 0 for non-positive arguments. */
+#define GECCO_KNN_MAX_K 64
+#define GECCO_KNN_SPLIT_SLICE 4096
+#define GECCO_KNN_WORKSPACE_BYTES(B, M, N, k) \
+    ((size_t)8 * (size_t)(B) * (size_t)(M) * (size_t)(k) * (((size_t)(N) + GECCO_KNN_SPLIT_SLICE - 1) / GECCO_KNN_SPLIT_SLICE))
+int gecco_knn_f32(const float* query, const float* ref, int32_t* idx, float* d2, void* ws, int B, int M, int N, int k, int exclude_self,
+                  int form, void* stream);
+size_t gecco_knn_workspace_bytes(int B, int M, int N, int k);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
