@@ -2311,6 +2311,19 @@ int gecco_knn_f32(const float* query, const float* ref, int32_t* idx, float* d2,
     return 0;
 }
 
+// normals and curvature from kNN lists (normals.hip).  d2 null: the distances a radius needs are recomputed from the coordinates
+int gecco_normals_f32(const float* ref, const float* query, const int32_t* idx, const float* d2, const float* viewpoint, float radius2,
+                      float* normal, float* eigenvalues, float* curvature, int32_t* count, int B, int M, int N, int k, void* stream) {
+    if (!ref || !query || !idx || !normal) return fail(-1, "normals: null argument");
+    if (B < 1 || M < 1 || N < 1) return fail(-2, "normals: B = %d, M = %d, N = %d must all be >= 1", B, M, N);
+    if (k < 1 || k > GECCO_KNN_MAX_K) return fail(-2, "normals: k = %d is not in 1 .. %d", k, GECCO_KNN_MAX_K);
+    const int rc = normals_launch(ref, query, idx, d2, viewpoint, radius2, normal, eigenvalues, curvature, count, B, M, N, k,
+                                  (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "normals: the grid for B = %d, M = %d passes 2^31 - 1 workgroups", B, M);
+    TRY(rc, "normals");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- ConvNeXt conditioner (channels-last)
 int gecco_convnext_stem_f32(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out,
                             int B, int H, int W, int C, float eps, void* stream) {

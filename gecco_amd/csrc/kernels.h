@@ -489,6 +489,10 @@ int fps_stream_launch(const float* points, const int* start, int* idx, float* se
 // for the split form (auto without ws runs the direct form); d2 nullable.  -3: the grid would pass 2^31 - 1 workgroups
 int knn_launch(const float* query, const float* ref, int* idx, float* d2, void* ws, int B, int M, int N, int k, int exclude_self, int form,
                hipStream_t st);
+// normals.hip — PCA normals and curvature from kNN lists (definition: gecco_normals_f32).  d2, viewpoint, eigenvalues, curvature, count
+// nullable; radius2 <= 0 or +inf: no radius.  -2: sizes out of range, -3: the grid would pass 2^31 - 1 workgroups
+int normals_launch(const float* ref, const float* query, const int* idx, const float* d2, const float* viewpoint, float radius2, float* normal,
+                   float* eigenvalues, float* curvature, int* count, int B, int M, int N, int k, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

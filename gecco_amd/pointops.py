@@ -1,5 +1,6 @@
-"""Point-cloud operators on the HIP device: farthest-point sampling (csrc/fps.hip, gecco_fps_f32) and k-nearest-neighbour search
-(csrc/knn.hip, gecco_knn_f32) with the statistical outlier filter built on it.
+"""Point-cloud operators on the HIP device: farthest-point sampling (csrc/fps.hip, gecco_fps_f32), k-nearest-neighbour search
+(csrc/knn.hip, gecco_knn_f32) with the statistical outlier filter built on it, and surface normals with curvature from the neighbour
+lists (csrc/normals.hip, gecco_normals_f32).
 
 The reference reduces a dense cloud to a fixed size by random permutation (gecco-jax data/torch_shapenet.py:20-21, data/taskonomy.py:84),
 which keeps density clumps and loses thin structure.  `farthest_point_sample` is the well-spread cut: from a start point, each next point
@@ -38,6 +39,27 @@ Two forms.  "direct": one launch, one thread per query, the reference cloud stre
 points (M = 2048 conditioning points against the upsampler's N = 100 000): the reference cloud is cut into slices of KNN_SPLIT_SLICE
 points, one launch finds each slice's k best, a second merges them.  form=None takes the split form when the direct grid would leave
 compute units idle and N spans more than one slice.  1 <= k <= KNN_MAX_K.
+
+Normals and curvature (`estimate_normals`).  What PCL and Open3D compute directly after the neighbour search: the PCA normal of each
+point's k-neighbourhood and its "surface variation".  The route without it is `knn_gather` (a (B, M, k, 3) tensor), a mean, an einsum
+and `torch.linalg.eigh` on B * M little 3 x 3 matrices.  Definition (include/gecco_hip.h; tests/_normals_ref.py restates it in numpy
+float32).  For query i, searched with the point itself among the candidates (a point belongs to its own neighbourhood):
+    neighbourhood  the reference points idx[i, t] with dist2[i, t] <= fp32(radius * radius), or all k of them without a radius; their
+                   number m is `count` (the hybrid search of Open3D)
+    covariance     mu = sum p / m;  C = sum (p - mu)(p - mu)^T / m: two passes, centred, in fp32 (not the raw moments E[pp^T] - mu mu^T,
+                   which lose every digit on a cloud far from the origin)
+    eigenpairs     of C, lambda0 <= lambda1 <= lambda2, by 4 cyclic Jacobi sweeps over (0,1), (0,2), (1,2) on C / trace(C): a fixed
+                   count.  A rotation whose parameter (a_qq - a_pp) / (2 a_pq) is not finite is skipped, one whose square would
+                   overflow takes t = 1 / (2 theta); negative roundings of an eigenvalue are clamped to 0
+    normal         the unit eigenvector of lambda0;  curvature = lambda0 / (lambda0 + lambda1 + lambda2)
+    invalid rows   m < 3, a non-finite coordinate in the query or a counted neighbour, trace(C) not a positive finite number (0: all
+                   counted points identical), an index outside [0, N): normal = (0, 0, 1) as in Open3D, eigenvalues = 0,
+                   curvature = 0, count still m.  A collinear neighbourhood is valid: some unit vector of the null space
+    sign           valid rows only.  With a viewpoint v: n . (v - q_i) >= 0.  Without: the component of largest magnitude is positive,
+                   the lowest axis among equal magnitudes
+One query's result depends on its own neighbour list and the points it names, nothing else: no atomics, the same bits run to run, in
+any batch position and through either form of the search.  Against float64 `eigh` of the float64 covariance of the same fp32
+coordinates, |C n - lambda0 n| and every eigenvalue stay within 32 * 2^-24 * trace(C).
 HIP tensors only: there is no CPU fallback."""
 from __future__ import annotations
 
@@ -221,3 +243,90 @@ def statistical_outlier_mask(points: Tensor, k: int = 16, std_ratio: float = 2.0
     if single:
         keep, score = keep[0], score[0]
     return (keep, score) if return_scores else keep
+
+
+def estimate_normals(points: Tensor, k: int = 16, radius: float | None = None, viewpoint=None, query: Tensor | None = None,
+                     idx: Tensor | None = None, return_curvature: bool = False, return_eigenvalues: bool = False,
+                     return_count: bool = False, form: str | None = None):
+    """Unit normals of the surface that `points` samples, from the PCA of k-neighbourhoods (module docstring: the definition).  points
+    (B, N, 3) or (N, 3) on the HIP device, any float dtype and strides (computed on an fp32 contiguous copy).  query None: the normals at
+    the points themselves; or (B, M, 3) / (M, 3): at other positions (the 2048 farthest-point samples of a 100 000-point cloud).  The
+    search is `knn` of the queries in `points` with the point itself among the candidates, through `form` (None / "direct" / "split":
+    same bits).  idx: the int64 or int32 (B, M, k) — (M, k) for single clouds — indices a caller already holds from
+    `knn(query, points, k, exclude_self=False)`; the search is skipped, k is idx's last dimension and the distances a radius needs are
+    recomputed from the coordinates, with the search's own roundings.  radius: only neighbours within it count (hybrid search); viewpoint
+    (3,) or (B, 3), numbers or a tensor: normals point towards it.  Returns normals, fp32 (B, M, 3) or (M, 3), then the extras asked
+    for, in the order curvature fp32 (B, M), eigenvalues fp32 (B, M, 3) ascending, count int64 (B, M).  ValueError for bad shapes, k
+    outside 1 .. KNN_MAX_K or above N, a radius that is not > 0, an idx whose shape disagrees with the clouds, mixed batched and single
+    inputs, an unknown form; GeccoHipError for CPU tensors.  No gradient: the inputs are detached."""
+    p, single = _cloud(points)
+    q = None
+    if query is not None:
+        q, qsingle = _cloud(query)
+        if qsingle != single:
+            raise ValueError("points and query must both be batched (B, ., 3) or both single (., 3)")
+        if q.shape[0] != p.shape[0]:
+            raise ValueError(f"points has {p.shape[0]} clouds, query has {q.shape[0]}")
+    if form not in _KNN_FORMS:
+        raise ValueError("form must be None, 'direct' or 'split'")
+    B, N, _ = p.shape
+    M = N if q is None else q.shape[1]
+    if B < 1 or M < 1 or N < 1:
+        raise ValueError("empty batch or cloud")
+    if idx is not None:
+        if not isinstance(idx, Tensor) or idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool:
+            raise ValueError("idx must be an integer tensor")
+        if idx.dim() != (2 if single else 3):
+            raise ValueError("idx must be (M, k) for single clouds and (B, M, k) for batched ones")
+        ix = idx[None] if single else idx
+        if ix.shape[0] != B or ix.shape[1] != M:
+            raise ValueError(f"idx of shape {tuple(idx.shape)} does not belong to {B} clouds of {M} queries")
+        k = ix.shape[2]
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k = {k} is not in 1 .. {KNN_MAX_K}")
+    if k > N:
+        raise ValueError(f"k = {k} above the {N} points of a cloud")
+    radius2 = 0.0   # no radius
+    if radius is not None:
+        radius = float(radius)
+        if not radius > 0:
+            raise ValueError(f"radius = {radius} must be > 0")
+        radius2 = radius * radius   # rounded to fp32 on its way into the library
+    vw = None
+    if viewpoint is not None:
+        vw = torch.as_tensor(viewpoint)
+        if vw.is_complex() or tuple(vw.shape) not in ((3,), (B, 3)):
+            raise ValueError(f"viewpoint must be (3,) or ({B}, 3)")
+    x = p.detach().float().contiguous()
+    px = _ptr(x)   # HIP tensors only: there is no CPU fallback
+    if q is None:
+        y, py = x, px
+    else:
+        y = q.detach().float().contiguous()
+        py = _ptr(y)
+    if idx is None:
+        ix, d2 = _knn(y, x, k, False, radius is not None, form)
+    else:
+        if not ix.is_cuda:
+            raise _lib.GeccoHipError("gecco_amd operators need tensors on the HIP device (no CPU fallback)")
+        ix, d2 = ix.detach().to(device=x.device, dtype=torch.int32).contiguous(), None
+    if vw is not None:
+        vw = vw.detach().to(device=x.device, dtype=torch.float32).expand(B, 3).contiguous()
+    normals = torch.empty(B, M, 3, device=x.device, dtype=torch.float32)
+    curv = torch.empty(B, M, device=x.device, dtype=torch.float32) if return_curvature else None
+    eig = torch.empty(B, M, 3, device=x.device, dtype=torch.float32) if return_eigenvalues else None
+    cnt = torch.empty(B, M, device=x.device, dtype=torch.int32) if return_count else None
+    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+    _lib.check(_lib.load().gecco_normals_f32(px, py, vp(ix), _ptr(d2), _ptr(vw), radius2, vp(normals), _ptr(eig), _ptr(curv), vp(cnt),
+                                             B, M, N, k, _stream()), "gecco_normals_f32")
+    out = [normals]
+    if return_curvature:
+        out.append(curv)
+    if return_eigenvalues:
+        out.append(eig)
+    if return_count:
+        out.append(cnt.long())
+    if single:
+        out = [t[0] for t in out]
+    return out[0] if len(out) == 1 else tuple(out)

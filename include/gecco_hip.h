@@ -941,6 +941,39 @@ int gecco_fps_f32(const float* points, const int* start, int* idx, float* sel2, 
 int gecco_knn_f32(const float* query, const float* ref, int32_t* idx, float* d2, void* ws, int B, int M, int N, int k, int exclude_self,
                   int form, void* stream);
 size_t gecco_knn_workspace_bytes(int B, int M, int N, int k);
+/* Surface normals and curvature of 3-D clouds from their k-nearest-neighbour lists (csrc/normals.hip): the PCA normal of every query's
+ * neighbourhood and its "surface variation", what PCL and Open3D compute directly after the neighbour search.  The reference has nothing
+ * of the kind; without this entry the route is a gathered (B, M, k, 3) tensor, a mean, an einsum and a batched 3 x 3 eigen-solver.
+ * ref (B, N, 3) and query (B, M, 3) fp32 (query == ref is allowed); idx (B, M, k) int32 and d2 (B, M, k) fp32 exactly as gecco_knn_f32
+ * writes them (searched WITHOUT exclude_self when the queries are the cloud's own points: a point belongs to its own neighbourhood, as
+ * in PCL and Open3D).  Definition, for query i:
+ *     neighbourhood  the reference points idx[i, t] with d2[i, t] <= radius2, or all k of them when there is no radius (radius2 <= 0,
+ *                    +inf or NaN); their number is m, which is what count holds (the hybrid search of Open3D).  d2 == NULL: the
+ *                    distances are recomputed from the coordinates with the spelling of gecco_knn_f32, dist2(q, p) = (dx*dx + dy*dy)
+ *                    + dz*dz rounded to fp32 with no FMA contraction, NaN -> +inf, so they are the bits the search would have written;
+ *                    d2 is not read at all when there is no radius
+ *     covariance     mu = sum p / m;  C = sum (p - mu)(p - mu)^T / m: two passes, centred, in fp32 (NOT the raw moments
+ *                    E[p p^T] - mu mu^T, which lose every digit on a cloud far from the origin)
+ *     eigenpairs     of C, lambda0 <= lambda1 <= lambda2, by 4 cyclic Jacobi sweeps over the entries (0,1), (0,2), (1,2) of C / trace(C):
+ *                    a fixed count, never a convergence test.  A rotation whose parameter theta = (a_qq - a_pp) / (2 a_pq) is not
+ *                    finite is skipped (a_pq is dropped), one whose square would overflow takes t = 1 / (2 theta).  Negative
+ *                    roundings of an eigenvalue are clamped to 0
+ *     normal         the unit eigenvector of lambda0;  curvature = lambda0 / (lambda0 + lambda1 + lambda2)
+ *     invalid rows   m < 3, or a non-finite coordinate in the query or in a counted neighbour, or trace(C) not a positive finite number
+ *                    (0: all counted points are identical), or an index outside [0, N) (never dereferenced, not counted):
+ *                    normal = (0, 0, 1) as in Open3D, eigenvalues = 0, curvature = 0; count still holds m.  A collinear neighbourhood
+ *                    is valid: its normal is some unit vector of the null space
+ *     sign           valid rows only.  viewpoint (B, 3) given: flipped so that n . (viewpoint_b - q_i) >= 0.  viewpoint == NULL: flipped
+ *                    so that the component of largest magnitude is positive; among equal magnitudes the lowest axis decides
+ * normal (B, M, 3) fp32; eigenvalues (B, M, 3) fp32 ascending, curvature (B, M) fp32 and count (B, M) int32 may each be NULL; every
+ * element of a given output is written.  1 <= k <= GECCO_KNN_MAX_K; any B, M, N >= 1.
+ * One query's result depends on nothing but its own row of idx and d2 and the points those name: one thread per query, no atomics, no
+ * workgroup waits on another; the outputs are the same bits run to run and in any batch position.  Against float64 eigh of the float64
+ * covariance of the same fp32 coordinates: |C n - lambda0 n| and every |lambda_t - lambda_t^64| stay within 32 * 2^-24 * trace(C)
+ * (tests/test_hip_normals.py).  Negative return (and gecco_last_error) before anything is enqueued for: null ref / query / idx / normal,
+ * non-positive sizes, k out of range.  Asynchronous on `stream`, no allocation, no synchronisation. */
+int gecco_normals_f32(const float* ref, const float* query, const int32_t* idx, const float* d2, const float* viewpoint, float radius2,
+                      float* normal, float* eigenvalues, float* curvature, int32_t* count, int B, int M, int N, int k, void* stream);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
