@@ -18,3 +18,4 @@ from .hip_ops import frozen_weights, weights_changed  # noqa: E402,F401
 from .pointops import FPS_RESIDENT_MAX_POINTS, farthest_point_sample, farthest_point_subsample  # noqa: E402,F401
 from .pointops import KNN_MAX_K, knn, knn_gather, statistical_outlier_mask  # noqa: E402,F401
 from .pointops import estimate_normals  # noqa: E402,F401
+from .pointops import voxel_downsample, voxel_pool  # noqa: E402,F401

@@ -232,6 +232,8 @@ SIGNATURES = {
     "gecco_knn_f32": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]),
     "gecco_knn_workspace_bytes": (sz, [i, i, i, i]),
     "gecco_normals_f32": (i, [vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, i, i, i, i, vp]),
+    "gecco_voxel_downsample_f32": (i, [vp, vp, fl, vp, vp, vp, vp, vp, vp, i, i, i, vp]),
+    "gecco_voxel_workspace_bytes": (sz, [i, i]),
     "gecco_convnext_stem_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),
     "gecco_convnext_dwconv_ln_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),
     "gecco_convnext_ln_patch2_f32": (i, [vp] * 4 + [i, i, i, i, fl, vp]),

@@ -2324,6 +2324,26 @@ int gecco_normals_f32(const float* ref, const float* query, const int32_t* idx, 
     return 0;
 }
 
+// voxel-grid downsampling (voxel.hip).  origin null: 0; first, count, inverse nullable
+size_t gecco_voxel_workspace_bytes(int B, int N) {
+    if (B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return 0;
+    return GECCO_VOXEL_WORKSPACE_BYTES(B, N);
+}
+int gecco_voxel_downsample_f32(const float* points, const float* origin, float voxel_size, float* centroids, int32_t* first, int32_t* count,
+                               int32_t* inverse, int32_t* n_voxels, void* workspace, int B, int N, int max_voxels, void* stream) {
+    if (!points || !centroids || !n_voxels || !workspace) return fail(-1, "voxel_downsample: null argument");
+    if (B < 1 || N < 1) return fail(-2, "voxel_downsample: B = %d, N = %d must both be >= 1", B, N);
+    if (N > GECCO_VOXEL_MAX_POINTS) return fail(-2, "voxel_downsample: N = %d above %d", N, GECCO_VOXEL_MAX_POINTS);
+    if (max_voxels < 1 || max_voxels > N) return fail(-2, "voxel_downsample: max_voxels = %d is not in 1 .. N = %d", max_voxels, N);
+    if (!(voxel_size > 0.f) || !(voxel_size <= 3.402823466e38f))
+        return fail(-2, "voxel_downsample: voxel_size = %g must be a finite number > 0", (double)voxel_size);
+    const int rc = voxel_launch(points, origin, voxel_size, centroids, first, count, inverse, n_voxels, workspace, B, N, max_voxels,
+                                (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "voxel_downsample: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
+    TRY(rc, "voxel_downsample");
+    return 0;
+}
+
 // ---------------------------------------------------------------------------- ConvNeXt conditioner (channels-last)
 int gecco_convnext_stem_f32(const float* x, const float* w, const float* bias, const float* ln_w, const float* ln_b, float* out,
                             int B, int H, int W, int C, float eps, void* stream) {

@@ -493,6 +493,10 @@ int knn_launch(const float* query, const float* ref, int* idx, float* d2, void* 
 // nullable; radius2 <= 0 or +inf: no radius.  -2: sizes out of range, -3: the grid would pass 2^31 - 1 workgroups
 int normals_launch(const float* ref, const float* query, const int* idx, const float* d2, const float* viewpoint, float radius2, float* normal,
                    float* eigenvalues, float* curvature, int* count, int B, int M, int N, int k, hipStream_t st);
+// voxel.hip — voxel-grid downsampling (definition: gecco_voxel_downsample_f32).  origin, first, count, inverse nullable; ws of
+// GECCO_VOXEL_WORKSPACE_BYTES(B, N); V = max_voxels rows per cloud.  -2: sizes out of range, -3: a grid would pass 2^31 - 1 workgroups
+int voxel_launch(const float* points, const float* origin, float voxel_size, float* centroids, int* first, int* count, int* inverse,
+                 int* n_voxels, void* ws, int B, int N, int V, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

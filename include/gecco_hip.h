@@ -974,6 +974,52 @@ size_t gecco_knn_workspace_bytes(int B, int M, int N, int k);
  * non-positive sizes, k out of range.  Asynchronous on `stream`, no allocation, no synchronisation. */
 int gecco_normals_f32(const float* ref, const float* query, const int32_t* idx, const float* d2, const float* viewpoint, float radius2,
                       float* normal, float* eigenvalues, float* curvature, int32_t* count, int B, int M, int N, int k, void* stream);
+/* Voxel-grid downsampling of 3-D clouds (csrc/voxel.hip): one output point per occupied cell of a regular grid of edge voxel_size, at
+ * the centroid of the points of points (B, N, 3) that fall in the cell, with the point-to-voxel map.  What PCL and Open3D put before
+ * the neighbour search; O(N) and a fixed number of launches whatever the output size.  The reference has nothing of the kind (its
+ * loaders cut by `randperm[:n_points]`); without this entry the route is floor -> unique(dim=0) (a sort and a synchronisation) ->
+ * index_add (float atomics, not reproducible).  Definition, per cloud, with s = voxel_size (an fp32 value > 0), o = origin[b] (three
+ * fp32 values; NULL: 0, a grid anchored at the world origin) and inv = fp32(1 / s), computed once on the host in fp32:
+ *     cell      per axis t = fp32(p - o), u = fp32(t * inv), c = floor(u): a subtraction, then a multiplication, nothing to contract.
+ *               A point is DROPPED when any u is not finite or any c is outside [-2^20, 2^20): it belongs to no voxel, inverse = -1
+ *     key       (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20): 63 bits, so all-ones means "empty"
+ *     voxels    the distinct keys of the kept points, numbered in order of FIRST OCCURRENCE: voxel v comes before voxel w when the
+ *               lowest point index in v is below the lowest in w.  first[v] = that lowest index, count[v] = the number of points in v,
+ *               inverse[i] = the voxel of point i, n_voxels = the number of voxels
+ *     centroid  no float sums.  Per axis frac = fp32(u - c) (it can round to 1.0 for a tiny negative u: part of the definition),
+ *               q = (uint64) trunc(frac * 2^32), S[v] = the exact integer sum of q over the voxel (64 bits hold any N), and
+ *               centroid = fp32( double(o) + (double(c) + double(S) / (double(count) * 2^32)) * double(s) ), every fp64 operation
+ *               rounded and none contracted
+ *     max_voxels  every output holds max_voxels rows per cloud; rows at or after n_voxels are zero with count = 0 and first = -1;
+ *               points of voxels numbered max_voxels or higher get inverse = -1 (their voxels are not written); n_voxels is reported
+ *               UNCLAMPED, so a caller sees the overflow.  max_voxels = N can never overflow
+ * Worked example (a numpy restatement, tests/_voxel_ref.py, gives the same): s = 1, o = 0, points (.5,.5,.5), (.6,.5,.5), (1.5,.5,.5),
+ * (.4,.4,.4), (-.25,.5,.5), (NaN,0,0): inverse = 0, 0, 1, 0, 2, -1; first = 0, 2, 4; count = 3, 1, 1; centroids (0.5, 0.46666667,
+ * 0.46666667), (1.5, .5, .5), (-.25, .5, .5).
+ * Integer sums do not depend on arrival order and the numbering is a scan over the point index, so the outputs are the same bits run to
+ * run, in any batch position and for any launch geometry.  Five launches: fill (table slots and accumulators), insert (one thread per
+ * point into the cloud's open-addressing table of the power of two >= 2 N slots of 64-bit keys: compare-and-swap with linear probing
+ * from a hash that mixes all three cell fields, a minimum on the slot's first-index word), rank (one workgroup per cloud: an exclusive
+ * scan of "this point is its slot's first" over the point index), accumulate (inverse; integer adds on count and S, lanes of a wave
+ * that follow each other into the same voxel combined first) and finalise (one thread per output row).  A table at load <= 0.5 always
+ * has an empty slot; no thread ever waits on another, no float atomics.
+ * centroids (B, max_voxels, 3) fp32 and n_voxels (B) int32 are required; first (B, max_voxels) int32, count (B, max_voxels) int32 and
+ * inverse (B, N) int32 may each be NULL; every element of a given output is written, padding included.  workspace:
+ * gecco_voxel_workspace_bytes(B, N) = GECCO_VOXEL_WORKSPACE_BYTES(B, N) bytes, 8-byte aligned = 16 B capacity (keys, first-index and
+ * voxel-number words of the slots) + 36 B N (S, count, first, the slot of each point) + 4 B, rounded up to 8; every word of it that
+ * the call reads was written by the call.  Negative return (and gecco_last_error) before anything is enqueued for: null points /
+ * centroids / n_voxels / workspace, B or N < 1, N above GECCO_VOXEL_MAX_POINTS, max_voxels outside 1 .. N, a voxel_size that is not a
+ * finite number > 0.  Asynchronous on `stream`, no allocation, no synchronisation.  gecco_voxel_workspace_bytes needs no GPU and
+ * returns 0 for arguments out of range. */
+#define GECCO_VOXEL_MAX_POINTS (1 << 30)
+#define GECCO_VOXEL_SMEAR_(x, k) ((x) | ((x) >> (k)))
+#define GECCO_VOXEL_CAPACITY(N) /* the power of two >= 2 N, for 1 <= N <= GECCO_VOXEL_MAX_POINTS */ \
+    (GECCO_VOXEL_SMEAR_(GECCO_VOXEL_SMEAR_(GECCO_VOXEL_SMEAR_(GECCO_VOXEL_SMEAR_(GECCO_VOXEL_SMEAR_(2 * (size_t)(N) - 1, 1), 2), 4), 8), 16) + 1)
+#define GECCO_VOXEL_WORKSPACE_BYTES(B, N) \
+    (((size_t)(B) * (16 * GECCO_VOXEL_CAPACITY(N) + 36 * (size_t)(N) + 4) + 7) & ~(size_t)7)
+int gecco_voxel_downsample_f32(const float* points, const float* origin, float voxel_size, float* centroids, int32_t* first, int32_t* count,
+                               int32_t* inverse, int32_t* n_voxels, void* workspace, int B, int N, int max_voxels, void* stream);
+size_t gecco_voxel_workspace_bytes(int B, int N);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
