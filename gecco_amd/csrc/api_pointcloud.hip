@@ -1,0 +1,230 @@
+// C ABI of libgecco_hip.so, part 4 of 4: point-cloud operators and metrics (distance matrix, Chamfer, set metrics, EMD,
+// Sinkhorn, farthest-point sampling, kNN, normals, voxel grid).
+#include "api_common.h"
+
+using namespace gecco_api;
+
+extern "C" {
+
+int gecco_distance_matrix_f32(const float* a, const float* b, float* D, int B, int N, int M, int squared, void* stream) {
+    if (!a || !b || !D) return fail(-1, "distance_matrix: null argument");
+    TRY(dist_matrix_launch(a, b, D, B, N, M, squared, (hipStream_t)stream), "distance_matrix");
+    return 0;
+}
+int gecco_set_chamfer_f32(const float* a, const float* b, float* out, int S, int T, int N, int M, int squared, void* stream) {
+    if (!a || !b || !out) return fail(-1, "set_chamfer: null argument");
+    if (S <= 0 || T <= 0 || N <= 0 || M <= 0) return fail(-2, "set_chamfer: empty set or cloud");
+    hipStream_t s = (hipStream_t)stream;
+    TRY(set_nearest_mean_launch(a, b, out, S, T, N, M, squared, T, 1, 0.5f, 0, s), "set_chamfer(a -> b)");
+    TRY(set_nearest_mean_launch(b, a, out, T, S, M, N, squared, 1, T, 0.5f, 1, s), "set_chamfer(b -> a)");
+    return 0;
+}
+
+int gecco_set_metrics_f32(const float* ss, const float* sd, const float* dd, int n, float* out3, int* flags, void* stream) {
+    if (!ss || !sd || !dd || !out3 || !flags) return fail(-1, "set_metrics: null argument");
+    if (n <= 0) return fail(-2, "set_metrics: empty set");
+    TRY(set_metrics_launch(ss, sd, dd, n, out3, flags, (hipStream_t)stream), "set_metrics");
+    return 0;
+}
+
+int gecco_chamfer_f32(const float* a, const float* b, float* out, float* ws, int B, int N, int M, int squared, void* stream) {
+    if (!a || !b || !out || !ws) return fail(-1, "chamfer: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    float* min_ab = ws;                       // (B, N): nearest b of every a
+    float* min_ba = ws + (size_t)B * N;       // (B, M): nearest a of every b
+    TRY(nearest_dist_launch(a, b, min_ab, B, N, M, squared, s), "chamfer(a -> b)");
+    TRY(nearest_dist_launch(b, a, min_ba, B, M, N, squared, s), "chamfer(b -> a)");
+    TRY(row_mean_launch(min_ab, out, B, N, 0.5f, 0, s), "chamfer(mean a)");
+    TRY(row_mean_launch(min_ba, out, B, M, 0.5f, 1, s), "chamfer(mean b)");
+    return 0;
+}
+int gecco_chamfer_idx_f32(const float* a, const float* b, float* out, float* ws, int* ia, int* ib, int B, int N, int M, int squared,
+                          void* stream) {
+    if (!a || !b || !out || !ws || !ia || !ib) return fail(-1, "chamfer_idx: null argument");
+    if (B < 1 || N < 1 || M < 1) return fail(-2, "chamfer_idx: B = %d, N = %d, M = %d must all be >= 1", B, N, M);
+    if (B > 65535) return fail(-2, "chamfer_idx: B = %d above 65535 (one grid row per sample)", B);
+    if (squared != 0 && squared != 1) return fail(-2, "chamfer_idx: squared = %d is not 0 / 1", squared);
+    hipStream_t s = (hipStream_t)stream;
+    float* min_ab = ws;                       // the layout and the launch order of gecco_chamfer_f32
+    float* min_ba = ws + (size_t)B * N;
+    TRY(nearest_idx_launch(a, b, min_ab, ia, B, N, M, squared, s), "chamfer_idx(a -> b)");
+    TRY(nearest_idx_launch(b, a, min_ba, ib, B, M, N, squared, s), "chamfer_idx(b -> a)");
+    TRY(row_mean_launch(min_ab, out, B, N, 0.5f, 0, s), "chamfer_idx(mean a)");
+    TRY(row_mean_launch(min_ba, out, B, M, 0.5f, 1, s), "chamfer_idx(mean b)");
+    return 0;
+}
+int gecco_chamfer_bwd_f32(const float* a, const float* b, const int* ia, const int* ib, const float* gout, float* da, float* db, int B,
+                          int N, int M, int squared, void* stream) {
+    if (!a || !b || !ia || !ib || !gout || (!da && !db)) return fail(-1, "chamfer_bwd: null argument");
+    if (B < 1 || N < 1 || M < 1) return fail(-2, "chamfer_bwd: B = %d, N = %d, M = %d must all be >= 1", B, N, M);
+    if (B > 65535) return fail(-2, "chamfer_bwd: B = %d above 65535 (one grid row per sample)", B);
+    if (squared != 0 && squared != 1) return fail(-2, "chamfer_bwd: squared = %d is not 0 / 1", squared);
+    hipStream_t s = (hipStream_t)stream;
+    if (da) TRY(chamfer_bwd_launch(a, b, ia, ib, gout, da, B, N, M, squared, s), "chamfer_bwd(da)");
+    if (db) TRY(chamfer_bwd_launch(b, a, ib, ia, gout, db, B, M, N, squared, s), "chamfer_bwd(db)");
+    return 0;
+}
+int gecco_emd_bwd_f32(const float* a, const float* b, const int* cols, const float* gout, float* da, float* db, int B, int N,
+                      int average_squared, void* stream) {
+    if (!a || !b || !cols || !gout || (!da && !db)) return fail(-1, "emd_bwd: null argument");
+    if (B < 1 || N < 1) return fail(-2, "emd_bwd: B = %d, N = %d must both be >= 1", B, N);
+    if (B > 65535) return fail(-2, "emd_bwd: B = %d above 65535 (one grid row per sample)", B);
+    if (average_squared != 0 && average_squared != 1) return fail(-2, "emd_bwd: average_squared = %d is not 0 / 1", average_squared);
+    TRY(emd_bwd_launch(a, b, cols, gout, da, db, B, N, average_squared, (hipStream_t)stream), "emd_bwd");
+    return 0;
+}
+int gecco_sinkhorn_f32(const float* C, float* f, float* g, float* rowcost, float* out, int B, int N, int M, float epsilon,
+                       int iterations, void* stream) {
+    if (!C || !f || !g || !rowcost || !out) return fail(-1, "sinkhorn: null argument");
+    if (epsilon <= 0.f || iterations < 1) return fail(-2, "sinkhorn: epsilon > 0 and iterations >= 1");
+    hipStream_t s = (hipStream_t)stream;
+    TRY((int)hipMemsetAsync(g, 0, (size_t)B * M * sizeof(float), s), "sinkhorn(g = 0)");
+    for (int it = 0; it < iterations; ++it) TRY(sinkhorn_step_launch(C, f, g, B, N, M, epsilon, s), "sinkhorn(step)");
+    TRY(sinkhorn_cost_launch(C, f, g, rowcost, out, B, N, M, epsilon, s), "sinkhorn(cost)");
+    return 0;
+}
+
+int gecco_emd_f32(const float* a, const float* b, int B, int N, int match_squared, int average_squared, float* out, int* assign,
+                  int* status, int max_rounds, void* stream) {
+    if (!a || !b || !out || !status) return fail(-1, "emd: null argument");
+    if (B <= 0) return fail(-2, "emd: empty batch");
+    if (N < 1 || N > GECCO_EMD_MAX_POINTS) return fail(-2, "emd: N = %d outside 1 .. %d (the LDS-resident limit)", N, GECCO_EMD_MAX_POINTS);
+    if (max_rounds < 0) return fail(-2, "emd: max_rounds %d < 0", max_rounds);
+    TRY(emd_auction_launch(a, b, out, assign, status, B, 1, 0, N, match_squared != 0, average_squared != 0,
+                           max_rounds ? max_rounds : GECCO_EMD_DEFAULT_ROUNDS, (hipStream_t)stream), "emd");
+    return 0;
+}
+int gecco_set_emd_f32(const float* a, const float* b, int S, int T, int N, int match_squared, int average_squared, float* out,
+                      int* status, int max_rounds, void* stream) {
+    if (!a || !b || !out || !status) return fail(-1, "set_emd: null argument");
+    if (S <= 0 || T <= 0) return fail(-2, "set_emd: empty set");
+    if ((long long)S * T > 0x7fffffffLL) return fail(-2, "set_emd: S * T = %lld pairs above 2^31 - 1", (long long)S * T);
+    if (N < 1 || N > GECCO_EMD_MAX_POINTS) return fail(-2, "set_emd: N = %d outside 1 .. %d (the LDS-resident limit)", N, GECCO_EMD_MAX_POINTS);
+    if (max_rounds < 0) return fail(-2, "set_emd: max_rounds %d < 0", max_rounds);
+    TRY(emd_auction_launch(a, b, out, nullptr, status, S * T, T, 1, N, match_squared != 0, average_squared != 0,
+                           max_rounds ? max_rounds : GECCO_EMD_DEFAULT_ROUNDS, (hipStream_t)stream), "set_emd");
+    return 0;
+}
+
+// matrix-free Sinkhorn (sinkhorn.hip).  form: 0 auto (resident within GECCO_SINKHORN_RESIDENT_MAX_POINTS), 1 resident, 2 streaming
+static int sinkhorn_common_checks(const char* who, int N, int M, float epsilon) {
+    if (N < 1 || M < 1) return fail(-2, "%s: N = %d, M = %d must both be >= 1", who, N, M);
+    if (!(epsilon > 0.f)) return fail(-2, "%s: epsilon = %g must be > 0", who, (double)epsilon);
+    return 0;
+}
+int gecco_sinkhorn_cloud_f32(const float* a, const float* b, float* f, float* g, float* ws, float* out, int B, int N, int M, float epsilon,
+                             int iterations, int form, void* stream) {
+    if (!a || !b || !out) return fail(-1, "sinkhorn_cloud: null argument");
+    if (B < 1) return fail(-2, "sinkhorn_cloud: empty batch");
+    if (int rc = sinkhorn_common_checks("sinkhorn_cloud", N, M, epsilon)) return rc;
+    if (iterations < 1) return fail(-2, "sinkhorn_cloud: iterations = %d must be >= 1", iterations);
+    if (form < 0 || form > 2) return fail(-2, "sinkhorn_cloud: form = %d is not 0 (auto), 1 (resident) or 2 (streaming)", form);
+    const bool fits = (long long)N + M <= GECCO_SINKHORN_RESIDENT_MAX_POINTS;
+    if (form == 1 && !fits)
+        return fail(-2, "sinkhorn_cloud: the resident form takes N + M <= %d (got %d + %d)", GECCO_SINKHORN_RESIDENT_MAX_POINTS, N, M);
+    if (form == 1 || (form == 0 && fits)) {
+        TRY(sinkhorn_resident_launch(a, b, f, g, out, B, 1, 0, N, M, epsilon, iterations, (hipStream_t)stream), "sinkhorn_cloud(resident)");
+        return 0;
+    }
+    if (!f || !g || !ws) return fail(-1, "sinkhorn_cloud: the streaming form needs f, g and ws");
+    if (B > 65535) return fail(-2, "sinkhorn_cloud: B = %d above 65535 (one grid row per sample)", B);
+    TRY(sinkhorn_stream_launch(a, b, f, g, ws, out, B, N, M, epsilon, iterations, (hipStream_t)stream), "sinkhorn_cloud(streaming)");
+    return 0;
+}
+int gecco_set_sinkhorn_f32(const float* a, const float* b, float* out, int S, int T, int N, int M, float epsilon, int iterations,
+                           void* stream) {
+    if (!a || !b || !out) return fail(-1, "set_sinkhorn: null argument");
+    if (S <= 0 || T <= 0) return fail(-2, "set_sinkhorn: empty set");
+    if ((long long)S * T > 0x7fffffffLL) return fail(-2, "set_sinkhorn: S * T = %lld pairs above 2^31 - 1", (long long)S * T);
+    if (int rc = sinkhorn_common_checks("set_sinkhorn", N, M, epsilon)) return rc;
+    if (iterations < 1) return fail(-2, "set_sinkhorn: iterations = %d must be >= 1", iterations);
+    if ((long long)N + M > GECCO_SINKHORN_RESIDENT_MAX_POINTS)
+        return fail(-2, "set_sinkhorn: the resident form takes N + M <= %d (got %d + %d)", GECCO_SINKHORN_RESIDENT_MAX_POINTS, N, M);
+    TRY(sinkhorn_resident_launch(a, b, nullptr, nullptr, out, S * T, T, 1, N, M, epsilon, iterations, (hipStream_t)stream), "set_sinkhorn");
+    return 0;
+}
+int gecco_sinkhorn_cloud_bwd_f32(const float* a, const float* b, const float* f, const float* g, const float* gout, float* da, float* db,
+                                 int B, int N, int M, float epsilon, void* stream) {
+    if (!a || !b || !f || !g || !gout || (!da && !db)) return fail(-1, "sinkhorn_cloud_bwd: null argument");
+    if (B < 1) return fail(-2, "sinkhorn_cloud_bwd: empty batch");
+    if (B > 65535) return fail(-2, "sinkhorn_cloud_bwd: B = %d above 65535 (one grid row per sample)", B);
+    if (int rc = sinkhorn_common_checks("sinkhorn_cloud_bwd", N, M, epsilon)) return rc;
+    TRY(sinkhorn_bwd_launch(a, b, f, g, gout, da, db, B, N, M, epsilon, (hipStream_t)stream), "sinkhorn_cloud_bwd");
+    return 0;
+}
+
+// farthest-point sampling (fps.hip).  form: 0 auto (resident within GECCO_FPS_RESIDENT_MAX_POINTS), 1 resident, 2 streaming
+int gecco_fps_f32(const float* points, const int* start, int* idx, float* sel2, void* ws, int B, int N, int k, int form, void* stream) {
+    if (!points || !idx) return fail(-1, "fps: null argument");
+    if (B < 1 || N < 1 || k < 1) return fail(-2, "fps: B = %d, N = %d, k = %d must all be >= 1", B, N, k);
+    if (k > N) return fail(-2, "fps: k = %d above N = %d", k, N);
+    if (form < 0 || form > 2) return fail(-2, "fps: form = %d is not 0 (auto), 1 (resident) or 2 (streaming)", form);
+    const bool fits = N <= GECCO_FPS_RESIDENT_MAX_POINTS;
+    if (form == 1 && !fits) return fail(-2, "fps: the resident form takes N <= %d (got %d)", GECCO_FPS_RESIDENT_MAX_POINTS, N);
+    if (form == 1 || (form == 0 && fits)) {
+        TRY(fps_resident_launch(points, start, idx, sel2, B, N, k, (hipStream_t)stream), "fps(resident)");
+        return 0;
+    }
+    if (!ws) return fail(-1, "fps: the streaming form needs ws");
+    if ((long long)B * ((N + GECCO_FPS_STREAM_SLICE - 1) / GECCO_FPS_STREAM_SLICE) > 0x7fffffffLL)
+        return fail(-2, "fps: B * ceil(N / %d) workgroups above 2^31 - 1", GECCO_FPS_STREAM_SLICE);
+    TRY(fps_stream_launch(points, start, idx, sel2, ws, B, N, k, (hipStream_t)stream), "fps(streaming)");
+    return 0;
+}
+
+// k-nearest neighbours (knn.hip).  form: 0 auto (knn_launch's rule; without ws it is the direct form), 1 direct, 2 split
+size_t gecco_knn_workspace_bytes(int B, int M, int N, int k) {
+    if (B < 1 || M < 1 || N < 1 || k < 1) return 0;
+    return GECCO_KNN_WORKSPACE_BYTES(B, M, N, k);
+}
+int gecco_knn_f32(const float* query, const float* ref, int32_t* idx, float* d2, void* ws, int B, int M, int N, int k, int exclude_self,
+                  int form, void* stream) {
+    if (!query || !ref || !idx) return fail(-1, "knn: null argument");
+    if (B < 1 || M < 1 || N < 1) return fail(-2, "knn: B = %d, M = %d, N = %d must all be >= 1", B, M, N);
+    if (k < 1 || k > GECCO_KNN_MAX_K) return fail(-2, "knn: k = %d is not in 1 .. %d", k, GECCO_KNN_MAX_K);
+    if (exclude_self && M != N) return fail(-2, "knn: exclude_self needs the query cloud to be the reference cloud (M = %d, N = %d)", M, N);
+    if (k > N - (exclude_self ? 1 : 0))
+        return fail(-2, "knn: k = %d above the %d candidates of a query (N = %d%s)", k, N - (exclude_self ? 1 : 0), N,
+                    exclude_self ? ", itself excluded" : "");
+    if (form < 0 || form > 2) return fail(-2, "knn: form = %d is not 0 (auto), 1 (direct) or 2 (split)", form);
+    if (form == 2 && !ws) return fail(-1, "knn: the split form needs ws");
+    const int rc = knn_launch(query, ref, idx, d2, ws, B, M, N, k, exclude_self ? 1 : 0, form, (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "knn: the grid for B = %d, M = %d, N = %d passes 2^31 - 1 workgroups", B, M, N);
+    TRY(rc, "knn");
+    return 0;
+}
+
+// normals and curvature from kNN lists (normals.hip).  d2 null: the distances a radius needs are recomputed from the coordinates
+int gecco_normals_f32(const float* ref, const float* query, const int32_t* idx, const float* d2, const float* viewpoint, float radius2,
+                      float* normal, float* eigenvalues, float* curvature, int32_t* count, int B, int M, int N, int k, void* stream) {
+    if (!ref || !query || !idx || !normal) return fail(-1, "normals: null argument");
+    if (B < 1 || M < 1 || N < 1) return fail(-2, "normals: B = %d, M = %d, N = %d must all be >= 1", B, M, N);
+    if (k < 1 || k > GECCO_KNN_MAX_K) return fail(-2, "normals: k = %d is not in 1 .. %d", k, GECCO_KNN_MAX_K);
+    const int rc = normals_launch(ref, query, idx, d2, viewpoint, radius2, normal, eigenvalues, curvature, count, B, M, N, k,
+                                  (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "normals: the grid for B = %d, M = %d passes 2^31 - 1 workgroups", B, M);
+    TRY(rc, "normals");
+    return 0;
+}
+
+// voxel-grid downsampling (voxel.hip).  origin null: 0; first, count, inverse nullable
+size_t gecco_voxel_workspace_bytes(int B, int N) {
+    if (B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return 0;
+    return GECCO_VOXEL_WORKSPACE_BYTES(B, N);
+}
+int gecco_voxel_downsample_f32(const float* points, const float* origin, float voxel_size, float* centroids, int32_t* first, int32_t* count,
+                               int32_t* inverse, int32_t* n_voxels, void* workspace, int B, int N, int max_voxels, void* stream) {
+    if (!points || !centroids || !n_voxels || !workspace) return fail(-1, "voxel_downsample: null argument");
+    if (B < 1 || N < 1) return fail(-2, "voxel_downsample: B = %d, N = %d must both be >= 1", B, N);
+    if (N > GECCO_VOXEL_MAX_POINTS) return fail(-2, "voxel_downsample: N = %d above %d", N, GECCO_VOXEL_MAX_POINTS);
+    if (max_voxels < 1 || max_voxels > N) return fail(-2, "voxel_downsample: max_voxels = %d is not in 1 .. N = %d", max_voxels, N);
+    if (!(voxel_size > 0.f) || !(voxel_size <= 3.402823466e38f))
+        return fail(-2, "voxel_downsample: voxel_size = %g must be a finite number > 0", (double)voxel_size);
+    const int rc = voxel_launch(points, origin, voxel_size, centroids, first, count, inverse, n_voxels, workspace, B, N, max_voxels,
+                                (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "voxel_downsample: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
+    TRY(rc, "voxel_downsample");
+    return 0;
+}
+
+}  // extern "C"

@@ -70,12 +70,12 @@ def _csrc():
 
 def test_launch_state_is_the_only_home_of_the_host_queries():
     """The dynamic-LDS opt-in, the CU count and the environment are reached through csrc/launch_state.h alone (per device, safe under
-    concurrent first calls); the one exception is the indexed option table, api.hip's option()."""
+    concurrent first calls); the one exception is the indexed option table, api_network.hip's option()."""
     src = _csrc()
     for api in ("hipFuncSetAttribute", "hipDeviceGetAttribute", "getenv"):
         users = {f for f, text in src.items() if api in text}
-        assert users == ({"launch_state.h", "api.hip"} if api == "getenv" else {"launch_state.h"}), (api, sorted(users))
-    api_hip = src["api.hip"]
+        assert users == ({"launch_state.h", "api_network.hip"} if api == "getenv" else {"launch_state.h"}), (api, sorted(users))
+    api_hip = src["api_network.hip"]
     option = api_hip[api_hip.index("int option(int which) {"):]
     option = option[:option.index("\n}\n")]
     assert api_hip.count("getenv") == 1 and "getenv" in option
@@ -87,7 +87,7 @@ def test_every_environment_knob_is_documented():
     names = set()
     for text in src.values():
         names.update(re.findall(r'env_int\(\s*"(GECCO_[A-Z0-9_]+)"', text))
-    table = re.search(r"g_option_env\[OPT_COUNT\]\s*=\s*\{(.*?)\};", src["api.hip"], flags=re.S).group(1)
+    table = re.search(r"g_option_env\[OPT_COUNT\]\s*=\s*\{(.*?)\};", src["api_network.hip"], flags=re.S).group(1)
     names.update(re.findall(r'"(GECCO_[A-Z0-9_]+)"', table))
     assert len(names) >= 40, sorted(names)
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()

@@ -209,7 +209,7 @@ def test_c5_cached_upsampling_shape_vs_oracle(ops, c5_case, precision):
 @pytest.mark.parametrize("d,L", [(384, 8), (256, 10), (128, 14)])
 def test_fp16_deep_network_weight_staging(ops, d, L):
     """Networks deeper than the shipped L=6: the per-forward weight-image staging table (96 split jobs per launch,
-    csrc/api.hip st_forward) is flushed and refilled mid-network; output must still match the oracle."""
+    csrc/api_network.hip st_forward) is flushed and refilled mid-network; output must still match the oracle."""
     N, B = 256, 2
     p = W.linear_lift_state_dict(100 + L, d, L, cases.I, cases.H)
     x, sigma = _noisy(7, B, N, (0.2, 4.0))

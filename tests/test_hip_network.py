@@ -621,7 +621,7 @@ def test_inducer_chain_cluster_matches_one_block_chain_bitwise(ops, precision, d
         ops.set_option("chaincl", -1)
     assert torch.equal(one[0], out[1][0][0])
     if precision == "mixed" and d == 512:
-        # d = 512 runs the one-launch chain ONLY as a cluster (one block per sample loses to the five split-bf16 launches there, api.hip):
+        # d = 512 runs the one-launch chain ONLY as a cluster (one block per sample loses to the five split-bf16 launches there, api_network.hip):
         # "chaincl" = 0 is that split-bf16 chain — the two agree like "chain2" on / off do (test_mixed_two_term_chain_...)
         e = cpu_ref.rel_err(out[1][0].cpu(), out[0][0].cpu())
         assert 0 < e[0] <= 3e-4, e
