@@ -19,3 +19,4 @@ from .pointops import FPS_RESIDENT_MAX_POINTS, farthest_point_sample, farthest_p
 from .pointops import KNN_MAX_K, knn, knn_gather, statistical_outlier_mask  # noqa: E402,F401
 from .pointops import estimate_normals  # noqa: E402,F401
 from .pointops import voxel_downsample, voxel_pool  # noqa: E402,F401
+from .pointops import ICP_MAX_ITERATIONS, ICPResult, icp, transform_points  # noqa: E402,F401

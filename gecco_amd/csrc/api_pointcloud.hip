@@ -1,5 +1,5 @@
 // C ABI of libgecco_hip.so, part 4 of 4: point-cloud operators and metrics (distance matrix, Chamfer, set metrics, EMD,
-// Sinkhorn, farthest-point sampling, kNN, normals, voxel grid).
+// Sinkhorn, farthest-point sampling, kNN, normals, ICP, voxel grid).
 #include "api_common.h"
 
 using namespace gecco_api;
@@ -204,6 +204,34 @@ int gecco_normals_f32(const float* ref, const float* query, const int32_t* idx, 
                                   (hipStream_t)stream);
     if (rc == -3) return fail(-2, "normals: the grid for B = %d, M = %d passes 2^31 - 1 workgroups", B, M);
     TRY(rc, "normals");
+    return 0;
+}
+
+// ICP registration (icp.hip).  method 0 point-to-point / 1 point-to-plane; form as gecco_knn_f32; normals, init, correspondence nullable
+size_t gecco_icp_workspace_bytes(int B, int M, int N) {
+    if (B < 1 || M < 1 || N < 1) return 0;
+    return GECCO_ICP_WORKSPACE_BYTES(B, M, N);
+}
+int gecco_icp_f32(const float* source, const float* target, const float* normals, const double* init, float r, int method,
+                  int max_iterations, double relative_fitness, double relative_rmse, double* transformation, float* fitness,
+                  float* inlier_rmse, int32_t* iterations, int32_t* status, int32_t* correspondence, void* ws, int B, int M, int N, int form,
+                  void* stream) {
+    if (!source || !target || !transformation || !fitness || !inlier_rmse || !iterations || !status || !ws)
+        return fail(-1, "icp: null argument");
+    if (B < 1 || M < 1 || N < 1) return fail(-2, "icp: B = %d, M = %d, N = %d must all be >= 1", B, M, N);
+    if (method != 0 && method != 1) return fail(-2, "icp: method = %d is not 0 (point-to-point) or 1 (point-to-plane)", method);
+    if (method == 1 && !normals) return fail(-1, "icp: the point-to-plane method needs normals");
+    if (form < 0 || form > 2) return fail(-2, "icp: form = %d is not 0 (auto), 1 (direct) or 2 (split)", form);
+    if (max_iterations < 0 || max_iterations > GECCO_ICP_MAX_ITERATIONS)
+        return fail(-2, "icp: max_iterations = %d is not in 0 .. %d", max_iterations, GECCO_ICP_MAX_ITERATIONS);
+    if (!(r > 0.f) || !(r <= 3.402823466e38f)) return fail(-2, "icp: r = %g must be a finite number > 0", (double)r);
+    if (!(relative_fitness >= 0.0) || !(relative_rmse >= 0.0))
+        return fail(-2, "icp: relative_fitness = %g and relative_rmse = %g must both be >= 0", relative_fitness, relative_rmse);
+    const float r2 = (float)((double)r * (double)r);
+    const int rc = icp_launch(source, target, normals, init, r2, method, max_iterations, relative_fitness, relative_rmse, transformation,
+                              fitness, inlier_rmse, iterations, status, correspondence, ws, B, M, N, form, (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "icp: the grid for B = %d, M = %d, N = %d passes 2^31 - 1 workgroups", B, M, N);
+    TRY(rc, "icp");
     return 0;
 }
 

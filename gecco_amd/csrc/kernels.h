@@ -493,6 +493,12 @@ int knn_launch(const float* query, const float* ref, int* idx, float* d2, void* 
 // nullable; radius2 <= 0 or +inf: no radius.  -2: sizes out of range, -3: the grid would pass 2^31 - 1 workgroups
 int normals_launch(const float* ref, const float* query, const int* idx, const float* d2, const float* viewpoint, float radius2, float* normal,
                    float* eigenvalues, float* curvature, int* count, int B, int M, int N, int k, hipStream_t st);
+// icp.hip — ICP registration (definition: gecco_icp_f32).  r2 = fp32(r * r); method 0 point-to-point / 1 point-to-plane (normals required);
+// init, correspondence nullable; ws of GECCO_ICP_WORKSPACE_BYTES(B, M, N); form as knn_launch; 2 * (max_iterations + 1) launches.
+// -2: arguments out of range, -3: the grid would pass 2^31 - 1 workgroups
+int icp_launch(const float* source, const float* target, const float* normals, const double* init, float r2, int method, int max_iterations,
+               double rel_fitness, double rel_rmse, double* transformation, float* fitness, float* inlier_rmse, int* iterations, int* status,
+               int* correspondence, void* ws, int B, int M, int N, int form, hipStream_t st);
 // voxel.hip — voxel-grid downsampling (definition: gecco_voxel_downsample_f32).  origin, first, count, inverse nullable; ws of
 // GECCO_VOXEL_WORKSPACE_BYTES(B, N); V = max_voxels rows per cloud.  -2: sizes out of range, -3: a grid would pass 2^31 - 1 workgroups
 int voxel_launch(const float* points, const float* origin, float voxel_size, float* centroids, int* first, int* count, int* inverse,

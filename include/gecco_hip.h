@@ -974,6 +974,63 @@ size_t gecco_knn_workspace_bytes(int B, int M, int N, int k);
  * non-positive sizes, k out of range.  Asynchronous on `stream`, no allocation, no synchronisation. */
 int gecco_normals_f32(const float* ref, const float* query, const int32_t* idx, const float* d2, const float* viewpoint, float radius2,
                       float* normal, float* eigenvalues, float* curvature, int32_t* count, int B, int M, int N, int k, void* stream);
+/* Rigid registration of 3-D clouds by ICP (csrc/icp.hip), point-to-point (method 0) and point-to-plane (method 1): the transformation
+ * that maps source (B, M, 3) onto target (B, N, 3), the consumer PCL and Open3D put behind the neighbour search and the normals.  The
+ * reference has nothing of the kind; without this entry the route is gecco_knn_f32 at k = 1, a gather and a batched SVD in a host loop
+ * with one synchronisation per iteration.  The definition follows Open3D's registration_icp (tests/_icp_ref.py restates it in numpy).
+ * Each cloud of the batch is independent.  Its state T is a 4 x 4 fp64 matrix (row-major), starting at init[b] (NULL: the identity);
+ * r2 = fp32(r * r) with the product taken in double; the anchor is c = double(target[0]).  Pass i = 0, 1, ...:
+ *     1 transform  Tf = fp32(T);  p'_m = ((Tf[a][0] x + Tf[a][1] y) + Tf[a][2] z) + Tf[a][3] per axis a, every operation rounded to fp32
+ *                  and none contracted into an FMA
+ *     2 match      (d2_m, j_m) = the first pair of gecco_knn_f32(p', target, k = 1): its dist2 spelling, NaN -> +inf, equal distances to
+ *                  the LOWEST index.  Pair m is an inlier when d2_m <= r2 (and d2_m < +inf: a NaN source point is never an inlier); in
+ *                  the plane method the three components of normals[j_m] must be finite as well
+ *     3 measure    n = the number of inliers;  fitness_i = n / M;  rmse_i = sqrt(sum d2 / n), the sum in fp64, 0 when n = 0
+ *     4 stop       at the first of these that holds, with status
+ *                    3  init has a non-finite entry (tested at pass 0 only)
+ *                    0  i >= 1 and |fitness_i - fitness_{i-1}| < relative_fitness and |rmse_i - rmse_{i-1}| < relative_rmse (absolute
+ *                       differences, as in Open3D despite the names)
+ *                    1  i == max_iterations
+ *                    2  n < 3 (point) or n < 6 (plane), or a singular system (step 5)
+ *                  T is left as it is; the outputs are this pass's fitness, rmse and correspondences (j_m for inliers, -1 otherwise)
+ *                  and iterations = i
+ *     5 update     T <- dT * double(Tf).
+ *                  point-to-point: for the inlier pairs P = double(p'), Q = double(q) the centroids and the cross-covariance S from
+ *                  moments about c in fp64; Horn's 4 x 4 symmetric matrix of S (scaled by its largest magnitude); its largest
+ *                  eigenvector by 8 cyclic Jacobi sweeps over (0,1), (0,2), (0,3), (1,2), (1,3), (2,3) in fp64, a fixed count (a
+ *                  rotation whose parameter theta is not finite is skipped, one whose square would overflow takes t = 1 / (2 theta),
+ *                  as in gecco_normals_f32); the quaternion normalised with w >= 0; R from it, t = mu_q - R mu_p.  A collinear
+ *                  inlier set is valid: it yields some rotation.  A non-finite dT counts as singular
+ *                  point-to-plane: res_m = (p'_m - q_m) . n_m,  J_m = [ (p'_m - c) x n_m , n_m ],  A = sum J^T J,  g = sum J res in
+ *                  fp64;  A x = -g by LDL^T without pivoting, singular when a pivot is non-finite or <= 2^-36 max diag(A);
+ *                  dT = Trans(c) [ Rz(x2) Ry(x1) Rx(x0) | x3..5 ] Trans(-c).  Normals are used as given (not normalised)
+ * max_iterations = 0 is Open3D's evaluate_registration: one matching pass under init, status 1, T = init.  A NaN target point is never
+ * matched while a finite one exists.  Neither a NaN point nor a NaN init disturbs another cloud.
+ * Outputs, every element written: transformation (B, 16) fp64; fitness (B) and inlier_rmse (B) fp32; iterations (B) and status (B)
+ * int32; correspondence (B, M) int32 or NULL.  init (B, 16) fp64 or NULL; normals (B, N, 3) fp32, required for method 1 and not read
+ * for method 0.  0 <= max_iterations <= GECCO_ICP_MAX_ITERATIONS; r a finite number > 0; the tolerances >= 0.
+ * Launches: 2 * (max_iterations + 1), a number that depends on max_iterations alone: per pass a match launch over (cloud x tile of
+ * source points x slice of the target) that keeps ONE 64-bit key (dist2's bits above j) per thread and applies Tf on load, and an
+ * update launch of one workgroup per cloud that reduces the fp64 sums in a fixed order, solves, tests and writes the state.  A stopped
+ * cloud's workgroups return at once.  No atomics, no workgroup waits on another, no synchronisation: the call can be captured in a
+ * graph.  form 1: "direct", a thread scans the whole target; form 2: "split", slices of GECCO_KNN_SPLIT_SLICE points, the update takes
+ * the minimum of a point's slice keys (exact); form 0: the auto rule of gecco_knn_f32.  The outputs are the same bits run to run, in any
+ * batch position and in both forms.
+ * ws: gecco_icp_workspace_bytes(B, M, N) = GECCO_ICP_WORKSPACE_BYTES(B, M, N) bytes, 8-byte aligned = GECCO_ICP_STATE_BYTES per cloud
+ * (T, the previous pass's fitness and rmse, the stopped flag) + 8 B M ceil(N / GECCO_KNN_SPLIT_SLICE) of keys; required; never read
+ * before it is written.  Negative return (and gecco_last_error) before anything is enqueued for: a null source / target / output / ws,
+ * method 1 without normals, non-positive sizes, an unknown method or form, max_iterations out of range, r not a finite number > 0, a
+ * negative or NaN tolerance.  gecco_icp_workspace_bytes needs no GPU and returns 0 for non-positive arguments. */
+#define GECCO_ICP_MAX_ITERATIONS 1000
+#define GECCO_ICP_STATE_BYTES 160
+#define GECCO_ICP_WORKSPACE_BYTES(B, M, N)           \
+    ((size_t)(B) * GECCO_ICP_STATE_BYTES +           \
+     (size_t)8 * (size_t)(B) * (size_t)(M) * (((size_t)(N) + GECCO_KNN_SPLIT_SLICE - 1) / GECCO_KNN_SPLIT_SLICE))
+int gecco_icp_f32(const float* source, const float* target, const float* normals, const double* init, float r, int method,
+                  int max_iterations, double relative_fitness, double relative_rmse, double* transformation, float* fitness,
+                  float* inlier_rmse, int32_t* iterations, int32_t* status, int32_t* correspondence, void* ws, int B, int M, int N, int form,
+                  void* stream);
+size_t gecco_icp_workspace_bytes(int B, int M, int N);
 /* Voxel-grid downsampling of 3-D clouds (csrc/voxel.hip): one output point per occupied cell of a regular grid of edge voxel_size, at
  * the centroid of the points of points (B, N, 3) that fall in the cell, with the point-to-voxel map.  What PCL and Open3D put before
  * the neighbour search; O(N) and a fixed number of launches whatever the output size.  The reference has nothing of the kind (its
