@@ -5,8 +5,8 @@
 // Definition (gecco_fps_f32, include/gecco_hip.h; tests/_fps_ref.py restates it in numpy float32).  d_i = +inf; for t = 0 .. k-1:
 //     idx[t] = s_t;  sel2[t] = d_{s_t};  d_i = min(d_i, dist2(p_i, p_{s_t}));  s_{t+1} = argmax_i d_i, the LOWEST index of equal maxima
 // dist2(a, b) = (dx dx + dy dy) + dz dz on the coordinate differences, every operation rounded to fp32 and none contracted into an
-// FMA (fps_dist2 spells the roundings out, as pair_dist.h does for its form and for the same reason): near-ties between candidates
-// are closer than an FMA's rounding, so the roundings are part of the definition.
+// FMA (cloud_dist2 of cloud_nn.h spells the roundings out, as pair_dist.h does for its form and for the same reason): near-ties
+// between candidates are closer than an FMA's rounding, so the roundings are part of the definition.
 //
 // The argmax is the maximum of ONE 64-bit key per candidate: d's bits in the high word (d >= 0, so they order as unsigned integers)
 // and ~index in the low word, so the largest key is the largest d and, among equals, the lowest index.  A maximum of integers has
@@ -29,8 +29,7 @@
 // slice against p_{s_t} and writes its key into the other of two key buffers.  Launch 0 takes s_0 from `start` and d = +inf from
 // nowhere, so the workspace is never read before it is written.  No workgroup waits on another inside a kernel: the order between
 // steps is the stream's order between launches, so the chain cannot hang however few workgroups are co-resident.
-#include "../../include/gecco_hip.h"
-#include "common.h"
+#include "cloud_nn.h"
 #include "kernels.h"
 #include "launch_state.h"
 
@@ -49,11 +48,6 @@ constexpr int FPS_STR_WAVES = FPS_STR_THREADS / 64;
 constexpr int FPS_STR_P = GECCO_FPS_STREAM_SLICE / FPS_STR_THREADS;
 static_assert(FPS_STR_P * FPS_STR_THREADS == GECCO_FPS_STREAM_SLICE, "a slice is a whole number of points per thread");
 
-static __device__ __forceinline__ float fps_dist2(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
 // min that keeps a NaN (np.minimum): a point with a NaN distance stays out of every later comparison
 static __device__ __forceinline__ float fps_min(float d, float v) { return (v < d || v != v) ? v : d; }
 static __device__ __forceinline__ fps_key fps_make_key(float d, int i) {
@@ -113,7 +107,7 @@ __global__ __launch_bounds__(FPS_RES_THREADS) void fps_resident_kernel(const flo
         int bj = 0;
 #pragma unroll
         for (int j = 0; j < P; ++j) {                   // ascending j is ascending index: `>` keeps the lowest of equals
-            d[j] = fps_min(d[j], fps_dist2(x[j], y[j], z[j], c[0], c[1], c[2]));
+            d[j] = fps_min(d[j], cloud_dist2(x[j], y[j], z[j], c[0], c[1], c[2]));
             if (d[j] > bd) {
                 bd = d[j];
                 bj = j;
@@ -171,7 +165,7 @@ __global__ __launch_bounds__(FPS_STR_THREADS) void fps_stream_kernel(const float
         const int i = g * GECCO_FPS_STREAM_SLICE + j * FPS_STR_THREADS + tid;
         if (i < N) {
             const float old = t == 0 ? __builtin_inff() : db[i];
-            const float dn = fps_min(old, fps_dist2(pb[3 * (size_t)i], pb[3 * (size_t)i + 1], pb[3 * (size_t)i + 2], cx, cy, cz));
+            const float dn = fps_min(old, cloud_dist2(pb[3 * (size_t)i], pb[3 * (size_t)i + 1], pb[3 * (size_t)i + 2], cx, cy, cz));
             db[i] = dn;
             if (dn > bd) {
                 bd = dn;

@@ -6,8 +6,8 @@
 // cloud the state T is a 4 x 4 fp64 matrix starting at init, r2 = fp32(r * r) and the anchor c = double(target[0]).  Pass i = 0, 1, ...:
 //   1 transform  Tf = fp32(T); p' = ((Tf[a][0] x + Tf[a][1] y) + Tf[a][2] z) + Tf[a][3] per axis a, every operation rounded to fp32,
 //                none contracted (icp_transform)
-//   2 match      (d2, j) = the first pair of the k = 1 search of p' in the target: knn.hip's dist2 spelling, NaN -> +inf, equal distances
-//                to the lowest index.  Inlier: d2 <= r2 and d2 < +inf (plane method: the three components of n_j finite as well)
+//   2 match      (d2, j) = the first pair of the k = 1 search of p' in the target: cloud_nn.h's dist2 spelling, NaN -> +inf, equal
+//                distances to the lowest index.  Inlier: d2 <= r2 and d2 < +inf (plane method: the three components of n_j finite as well)
 //   3 measure    n inliers; fitness = n / M; rmse = sqrt(sum d2 / n) with the sum in fp64, 0 when n = 0
 //   4 stop       at the first that holds: status 3, init has a non-finite entry (pass 0 only); status 0, i >= 1 and |fitness_i -
 //                fitness_{i-1}| < relative_fitness and |rmse_i - rmse_{i-1}| < relative_rmse; status 1, i == max_iterations; status 2,
@@ -21,28 +21,26 @@
 //
 // icp_match_kernel<T>: grid (cloud, tile of T source points, slice of the target), one thread per source point.  It reads its cloud's T
 // (pass 0: from init, later: from the state in the workspace), transforms its point on load, and walks the slice through LDS tiles the
-// way knn_scan_kernel does: (x, y, z, 0) entries, broadcast reads, four candidates per step, the next tile fetched while this one is
-// scanned.  ONE 64-bit key (dist2's bits above j) lives in a register; there is no LDS list.  keys[(b * S + s) * M + m] gets it.  The
-// minimum over a point's S slice keys is exact, so the direct (S = 1) and split forms give the same bits.
+// way knn_scan_kernel does (the same loop; cloud_nn.h says why it is written out in both): (x, y, z, 0) entries, broadcast reads, four
+// candidates per step, the next tile fetched while this one is scanned.  ONE 64-bit key (dist2's bits above j) lives in a register;
+// there is no LDS list.  keys[(b * S + s) * M + m] gets it.  The minimum over a point's S slice keys is exact, so the direct (S = 1)
+// and split forms give the same bits.
 //
 // icp_update_kernel<PLANE>: one workgroup of ICP_UPDATE_THREADS per cloud.  Thread t takes points t, t + T, ...: the minimum of the S
 // keys, the gather of q (and n), the correspondence, and its fp64 sums (17 numbers for the point method, 29 for the plane method).  The
 // sums are reduced inside the wave by a fixed shuffle tree and across the waves through LDS by thread 0 in wave order; thread 0 then
 // runs steps 3 - 5 and writes the state and, on a stop, the outputs.  The geometry of this kernel never depends on the batch or the
 // form, so a cloud's bits are the same run to run, in any batch position and in both forms.
-#include "../../include/gecco_hip.h"
-#include "common.h"
+#include "cloud_nn.h"
 #include "kernels.h"
 #include "launch_state.h"
 
 namespace {
 
 typedef unsigned long long icp_key;
-constexpr int ICP_TILE = 512;
 constexpr int ICP_UPDATE_THREADS = 512;
 constexpr int ICP_JACOBI_SWEEPS = 8;   // cyclic sweeps over the six pairs of Horn's 4 x 4 matrix: quadratic convergence, fp64 by the fifth
 constexpr int ICP_STATE_DOUBLES = GECCO_ICP_STATE_BYTES / 8;   // T (16), fitness and rmse of the previous pass, the stopped flag
-static_assert(GECCO_KNN_SPLIT_SLICE % ICP_TILE == 0, "a slice is a whole number of tiles");
 static_assert(ICP_STATE_DOUBLES >= 19, "the state of a cloud");
 
 __device__ const double icp_identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -61,21 +59,12 @@ static __device__ __forceinline__ void icp_transform(const float* tf, float x, f
     pz = ((tf[8] * x + tf[9] * y) + tf[10] * z) + tf[11];
 }
 
-// knn_dist2_bits of knn.hip
-static __device__ __forceinline__ unsigned icp_dist2_bits(float qx, float qy, float qz, const f32x4 p) {
-#pragma clang fp contract(off)
-    const float dx = qx - p[0], dy = qy - p[1], dz = qz - p[2];
-    const float d = (dx * dx + dy * dy) + dz * dz;
-    return __float_as_uint(__builtin_fminf(d, __builtin_inff()));   // minNum: a NaN becomes +inf
-}
-
 // grid: B * tiles * S blocks, block (b, tile, s) scans target points [s * slice, min(N, (s + 1) * slice)) for source points tile * T ..
 template <int T>
 __global__ __launch_bounds__(T) void icp_match_kernel(const float* __restrict__ source, const float* __restrict__ target,
                                                       const double* __restrict__ init, const double* __restrict__ state,
                                                       icp_key* __restrict__ keys, int pass, int M, int N, int tiles, int S, unsigned slice) {
-    constexpr int PPT = ICP_TILE / T;
-    __shared__ __attribute__((aligned(16))) f32x4 tile[ICP_TILE];
+    __shared__ __attribute__((aligned(16))) f32x4 tile[CLOUD_TILE];
 
     const int tid = threadIdx.x;
     const unsigned bid = blockIdx.x;
@@ -98,6 +87,7 @@ __global__ __launch_bounds__(T) void icp_match_kernel(const float* __restrict__ 
 
     unsigned best_bits = 0xffffffffu, best_j = 0xffffffffu;   // above every key: dist2's bits are at most +inf's
 
+    constexpr int PPT = CLOUD_TILE / T;
     float rx[PPT], ry[PPT], rz[PPT];
     auto fetch = [&](unsigned base) {
 #pragma unroll
@@ -118,18 +108,18 @@ __global__ __launch_bounds__(T) void icp_match_kernel(const float* __restrict__ 
     };
 
     fetch(lo);
-    for (unsigned base = lo; base < hi; base += ICP_TILE) {
+    for (unsigned base = lo; base < hi; base += CLOUD_TILE) {
         __syncthreads();   // the scan of the previous tile is over
 #pragma unroll
         for (int p = 0; p < PPT; ++p) tile[tid + p * T] = f32x4{rx[p], ry[p], rz[p], 0.f};
         __syncthreads();
-        if (base + ICP_TILE < hi) fetch(base + ICP_TILE);
+        if (base + CLOUD_TILE < hi) fetch(base + CLOUD_TILE);
         if (!valid) continue;
-        const int cnt = (int)min((unsigned)ICP_TILE, hi - base);   // entries past cnt are never candidates
+        const int cnt = (int)min((unsigned)CLOUD_TILE, hi - base);   // entries past cnt are never candidates
         int g = 0;
         for (; g + 4 <= cnt; g += 4) {
-            const unsigned u0 = icp_dist2_bits(qx, qy, qz, tile[g]), u1 = icp_dist2_bits(qx, qy, qz, tile[g + 1]);
-            const unsigned u2 = icp_dist2_bits(qx, qy, qz, tile[g + 2]), u3 = icp_dist2_bits(qx, qy, qz, tile[g + 3]);
+            const unsigned u0 = cloud_dist2_bits(qx, qy, qz, tile[g]), u1 = cloud_dist2_bits(qx, qy, qz, tile[g + 1]);
+            const unsigned u2 = cloud_dist2_bits(qx, qy, qz, tile[g + 2]), u3 = cloud_dist2_bits(qx, qy, qz, tile[g + 3]);
             if (min(min(u0, u1), min(u2, u3)) < best_bits) {   // ascending j inside the step
                 single(u0, base + g);
                 single(u1, base + g + 1);
@@ -137,16 +127,13 @@ __global__ __launch_bounds__(T) void icp_match_kernel(const float* __restrict__ 
                 single(u3, base + g + 3);
             }
         }
-        for (; g < cnt; ++g) single(icp_dist2_bits(qx, qy, qz, tile[g]), base + g);
+        for (; g < cnt; ++g) single(cloud_dist2_bits(qx, qy, qz, tile[g]), base + g);
     }
     if (!valid) return;
     keys[((size_t)b * S + s) * (size_t)M + i] = ((icp_key)best_bits << 32) | (icp_key)best_j;   // a slice holds a point: best_j < N
 }
 
 static __device__ __forceinline__ bool icp_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and inf
-static __device__ __forceinline__ bool icp_finite3f(float x, float y, float z) {
-    return fabsf(x) <= 3.402823466e38f && fabsf(y) <= 3.402823466e38f && fabsf(z) <= 3.402823466e38f;
-}
 
 // One Jacobi rotation of the symmetric 4 x 4 matrix a that annihilates a[p][q], accumulated into the eigenvector columns v.  The
 // guard of normals_rotate: a non-finite theta gives t = 0 (the entry is already nothing beside the diagonal and is dropped), a theta
@@ -336,7 +323,7 @@ __global__ __launch_bounds__(ICP_UPDATE_THREADS) void icp_update_kernel(
         float nx = 0.f, ny = 0.f, nz = 0.f;
         if (PLANE && in) {
             nx = nb[3 * (size_t)j], ny = nb[3 * (size_t)j + 1], nz = nb[3 * (size_t)j + 2];
-            in = icp_finite3f(nx, ny, nz);
+            in = cloud_finite3(nx, ny, nz);
         }
         if (correspondence) correspondence[(size_t)b * M + m] = in ? (int)j : -1;
         if (!in) continue;
@@ -431,52 +418,30 @@ __global__ __launch_bounds__(ICP_UPDATE_THREADS) void icp_update_kernel(
     st[18] = 0.0;
 }
 
-int icp_threads(long long rows_of_blocks, int M, int cus) {
-    int T = 256;
-    while (T > 64 && rows_of_blocks * ((M + T - 1) / T) < 2LL * cus) T >>= 1;
-    return T;
-}
-
-template <int T>
-void icp_match_go(const float* source, const float* target, const double* init, const double* state, icp_key* keys, int pass, int B, int M,
-                  int N, int S, hipStream_t st) {
-    const int tiles = (M + T - 1) / T;
-    hipLaunchKernelGGL(icp_match_kernel<T>, dim3((unsigned)((long long)B * tiles * S)), dim3(T), 0, st, source, target, init, state, keys, pass,
-                       M, N, tiles, S, S == 1 ? (unsigned)N : (unsigned)GECCO_KNN_SPLIT_SLICE);
-}
-
 }  // namespace
 
-// form 0: split when N spans more than one slice and the direct grid at its smallest workgroup (64 points) leaves CUs idle (knn_launch's
-// rule); 1: direct; 2: split.  ws of GECCO_ICP_WORKSPACE_BYTES(B, M, N).  -2: arguments out of range, -3: a grid would pass 2^31 - 1
+// form 0 / 1 / 2: cloud_plan's forms; the workspace is mandatory, so the auto form can always split.  ws of
+// GECCO_ICP_WORKSPACE_BYTES(B, M, N).  -2: arguments out of range, -3: a grid would pass 2^31 - 1
 int icp_launch(const float* source, const float* target, const float* normals, const double* init, float r2, int method, int max_iterations,
                double rel_fitness, double rel_rmse, double* transformation, float* fitness, float* inlier_rmse, int* iterations, int* status,
                int* correspondence, void* ws, int B, int M, int N, int form, hipStream_t st) {
     if (B < 1 || M < 1 || N < 1 || form < 0 || form > 2 || method < 0 || method > 1 || max_iterations < 0 || !ws || (method == 1 && !normals))
         return -2;
-    const int cus = device_cus();
-    const int slices = (int)(((long long)N + GECCO_KNN_SPLIT_SLICE - 1) / GECCO_KNN_SPLIT_SLICE);
-    const bool split = form == 2 || (form == 0 && slices > 1 && (long long)B * ((M + 63) / 64) < cus);
-    const int S = split ? slices : 1;
-    const int T = icp_threads((long long)B * S, M, cus);
-    if ((long long)B * ((M + T - 1) / T) * S > 0x7fffffffLL) return -3;
+    const CloudPlan p = cloud_plan(B, M, N, form, true, 256, device_cus());
+    if (!p.fits()) return -3;
     double* state = static_cast<double*>(ws);
     icp_key* keys = reinterpret_cast<icp_key*>(state + (size_t)B * ICP_STATE_DOUBLES);
+    const unsigned slice = p.S == 1 ? (unsigned)N : (unsigned)GECCO_KNN_SPLIT_SLICE;
+    const auto update = method == 1 ? icp_update_kernel<true> : icp_update_kernel<false>;
     for (int pass = 0; pass <= max_iterations; ++pass) {
-        if (T == 256)
-            icp_match_go<256>(source, target, init, state, keys, pass, B, M, N, S, st);
-        else if (T == 128)
-            icp_match_go<128>(source, target, init, state, keys, pass, B, M, N, S, st);
-        else
-            icp_match_go<64>(source, target, init, state, keys, pass, B, M, N, S, st);
-        if (method == 1)
-            hipLaunchKernelGGL(icp_update_kernel<true>, dim3((unsigned)B), dim3(ICP_UPDATE_THREADS), 0, st, source, target, normals, init, state,
-                               keys, r2, pass, max_iterations, rel_fitness, rel_rmse, transformation, fitness, inlier_rmse, iterations, status,
-                               correspondence, M, N, S);
-        else
-            hipLaunchKernelGGL(icp_update_kernel<false>, dim3((unsigned)B), dim3(ICP_UPDATE_THREADS), 0, st, source, target, normals, init, state,
-                               keys, r2, pass, max_iterations, rel_fitness, rel_rmse, transformation, fitness, inlier_rmse, iterations, status,
-                               correspondence, M, N, S);
+        dispatch_T(p.T, [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            hipLaunchKernelGGL(icp_match_kernel<T>, dim3((unsigned)p.blocks), dim3(T), 0, st, source, target, init, state, keys, pass, M, N,
+                               p.tiles, p.S, slice);
+        });
+        hipLaunchKernelGGL(update, dim3((unsigned)B), dim3(ICP_UPDATE_THREADS), 0, st, source, target, normals, init, state, keys, r2, pass,
+                           max_iterations, rel_fitness, rel_rmse, transformation, fitness, inlier_rmse, iterations, status, correspondence, M,
+                           N, p.S);
         const int rc = (int)hipGetLastError();
         if (rc) return rc;
     }

@@ -3,8 +3,8 @@
 // without this file is a materialised M x N distance matrix and a top-k over it.
 //
 // Definition (gecco_knn_f32, include/gecco_hip.h; tests/_knn_ref.py restates it in numpy float32).  dist2(q, p) = (dx dx + dy dy) + dz dz
-// on the coordinate differences, every operation rounded to fp32 and none contracted into an FMA (knn_dist2 spells the roundings out,
-// as fps_dist2 does); a NaN dist2 is replaced by +inf; the pairs of query i are ordered by (dist2, j) ascending — equal distances go to
+// on the coordinate differences, every operation rounded to fp32 and none contracted into an FMA (cloud_dist2 of cloud_nn.h spells the
+// roundings out); a NaN dist2 is replaced by +inf; the pairs of query i are ordered by (dist2, j) ascending — equal distances go to
 // the LOWEST index — and the first k of them are the result.  Self mode skips the pair j == i by index.
 //
 // One 64-bit key per pair: dist2's bits in the high word (dist2 >= 0 or +inf, so they order as unsigned integers) and j in the low
@@ -19,7 +19,7 @@
 // At the end slot t goes to output position rank(t) = the number of keys below it (keys are distinct: k * k compares, no sort).
 //
 // Scan kernel.  A workgroup of T = 64, 128 or 256 threads (T queries) walks the points [lo, hi) of the reference cloud in tiles of
-// KNN_TILE = 512 points staged in LDS as (x, y, z, 0); the next tile is fetched into registers while this one is scanned.  Every lane
+// CLOUD_TILE = 512 points staged in LDS as (x, y, z, 0); the next tile is fetched into registers while this one is scanned.  Every lane
 // reads the same tile entry (a broadcast read), four candidates per step: eight subtractions / products / sums and one min (NaN ->
 // +inf) each, one min over the four and ONE branch; only a step that holds a winner for some lane looks at its four candidates singly.
 // "direct" form: one launch, [lo, hi) = the whole cloud, results written from the list.
@@ -27,8 +27,7 @@
 // as it is (k keys, empty slots included) to the workspace ws[((b * S + s) * k + t) * M + i]; a second launch (knn_merge_kernel) pushes
 // the S * k keys of a query through the same list (full 64-bit compare: slices arrive unsorted) and writes the results.  Both launches
 // are ordinary grids; every workspace word the merge reads was written by the first launch.
-#include "../../include/gecco_hip.h"
-#include "common.h"
+#include "cloud_nn.h"
 #include "kernels.h"
 #include "launch_state.h"
 
@@ -36,17 +35,8 @@ namespace {
 
 typedef unsigned long long knn_key;
 constexpr knn_key KNN_EMPTY = ~0ull;
-constexpr int KNN_TILE = 512;
-static_assert(GECCO_KNN_SPLIT_SLICE % KNN_TILE == 0, "a slice is a whole number of tiles");
 static_assert(8 * 256 * 16 <= 32 * 1024 && 8 * 128 * 32 <= 32 * 1024 && 8 * 64 * GECCO_KNN_MAX_K <= 32 * 1024,
-              "the lists of a workgroup take at most 32 KiB of LDS (knn_threads)");
-
-static __device__ __forceinline__ unsigned knn_dist2_bits(float qx, float qy, float qz, const f32x4 p) {
-#pragma clang fp contract(off)
-    const float dx = qx - p[0], dy = qy - p[1], dz = qz - p[2];
-    const float d = (dx * dx + dy * dy) + dz * dz;
-    return __float_as_uint(__builtin_fminf(d, __builtin_inff()));   // minNum: a NaN becomes +inf
-}
+              "the lists of a workgroup take at most 32 KiB of LDS (cloud_max_threads)");
 
 // the running k-best list of one thread: `list` points at slot 0 of this thread, slots are T words apart
 template <int T>
@@ -97,9 +87,8 @@ template <int T>
 __global__ __launch_bounds__(T) void knn_scan_kernel(const float* __restrict__ query, const float* __restrict__ ref, int* __restrict__ idx,
                                                      float* __restrict__ d2, knn_key* __restrict__ ws, int M, int N, int k, int exclude_self,
                                                      int tiles, int S, unsigned slice) {
-    constexpr int PPT = KNN_TILE / T;
     extern __shared__ __attribute__((aligned(16))) unsigned char knn_lds[];
-    __shared__ __attribute__((aligned(16))) f32x4 tile[KNN_TILE];
+    __shared__ __attribute__((aligned(16))) f32x4 tile[CLOUD_TILE];
 
     const int tid = threadIdx.x;
     const unsigned bid = blockIdx.x;
@@ -115,6 +104,8 @@ __global__ __launch_bounds__(T) void knn_scan_kernel(const float* __restrict__ q
     KnnList<T> best;
     best.init(reinterpret_cast<knn_key*>(knn_lds) + tid, k);
 
+    // (icp_match_kernel has the same loop; cloud_nn.h says why it is written out in both)
+    constexpr int PPT = CLOUD_TILE / T;
     float rx[PPT], ry[PPT], rz[PPT];
     auto fetch = [&](unsigned base) {
 #pragma unroll
@@ -131,18 +122,18 @@ __global__ __launch_bounds__(T) void knn_scan_kernel(const float* __restrict__ q
     };
 
     fetch(lo);
-    for (unsigned base = lo; base < hi; base += KNN_TILE) {
+    for (unsigned base = lo; base < hi; base += CLOUD_TILE) {
         __syncthreads();   // the scan of the previous tile is over
 #pragma unroll
         for (int p = 0; p < PPT; ++p) tile[tid + p * T] = f32x4{rx[p], ry[p], rz[p], 0.f};
         __syncthreads();
-        if (base + KNN_TILE < hi) fetch(base + KNN_TILE);
+        if (base + CLOUD_TILE < hi) fetch(base + CLOUD_TILE);
         if (!valid) continue;
-        const int cnt = (int)min((unsigned)KNN_TILE, hi - base);   // entries past cnt are never candidates
+        const int cnt = (int)min((unsigned)CLOUD_TILE, hi - base);   // entries past cnt are never candidates
         int g = 0;
         for (; g + 4 <= cnt; g += 4) {
-            const unsigned u0 = knn_dist2_bits(qx, qy, qz, tile[g]), u1 = knn_dist2_bits(qx, qy, qz, tile[g + 1]);
-            const unsigned u2 = knn_dist2_bits(qx, qy, qz, tile[g + 2]), u3 = knn_dist2_bits(qx, qy, qz, tile[g + 3]);
+            const unsigned u0 = cloud_dist2_bits(qx, qy, qz, tile[g]), u1 = cloud_dist2_bits(qx, qy, qz, tile[g + 1]);
+            const unsigned u2 = cloud_dist2_bits(qx, qy, qz, tile[g + 2]), u3 = cloud_dist2_bits(qx, qy, qz, tile[g + 3]);
             if (min(min(u0, u1), min(u2, u3)) < best.worst_bits()) {   // ascending j inside the step
                 single(u0, base + g);
                 single(u1, base + g + 1);
@@ -150,7 +141,7 @@ __global__ __launch_bounds__(T) void knn_scan_kernel(const float* __restrict__ q
                 single(u3, base + g + 3);
             }
         }
-        for (; g < cnt; ++g) single(knn_dist2_bits(qx, qy, qz, tile[g]), base + g);
+        for (; g < cnt; ++g) single(cloud_dist2_bits(qx, qy, qz, tile[g]), base + g);
     }
     if (!valid) return;
     if (ws) {
@@ -183,40 +174,22 @@ __global__ __launch_bounds__(T) void knn_merge_kernel(const knn_key* __restrict_
     best.emit(idx + o, d2 ? d2 + o : nullptr);
 }
 
-// threads per workgroup: the most whose lists fit 32 KiB, halved while the grid would leave the device short of two workgroups per CU
-int knn_threads(int k, long long rows_of_blocks, int M, int cus) {
-    int T = k <= 16 ? 256 : k <= 32 ? 128 : 64;
-    while (T > 64 && rows_of_blocks * ((M + T - 1) / T) < 2LL * cus) T >>= 1;
-    return T;
-}
-
-template <int T>
-int knn_go(const float* query, const float* ref, int* idx, float* d2, knn_key* ws, int B, int M, int N, int k, int exclude_self, int S,
-           hipStream_t st) {
-    const int tiles = (M + T - 1) / T;
-    const long long blocks = (long long)B * tiles * S;
-    if (blocks > 0x7fffffffLL) return -3;
-    const size_t lds = (size_t)8 * T * k;
-    hipLaunchKernelGGL(knn_scan_kernel<T>, dim3((unsigned)blocks), dim3(T), lds, st, query, ref, idx, d2, ws, M, N, k, exclude_self, tiles,
-                       S, S == 1 ? (unsigned)N : (unsigned)GECCO_KNN_SPLIT_SLICE);
-    if (ws) hipLaunchKernelGGL(knn_merge_kernel<T>, dim3((unsigned)(B * tiles)), dim3(T), lds, st, ws, idx, d2, M, k, tiles, S);
-    return (int)hipGetLastError();
-}
-
 }  // namespace
 
-// form 0: split when a workspace is there, N spans more than one slice and the direct grid at its smallest workgroup (64 queries)
-// leaves CUs idle; 1: direct; 2: split (ws required).  Returns -3 when the grid would pass 2^31 - 1 workgroups.
+// form 0: split when a workspace is there and cloud_plan's rule takes it; 1: direct; 2: split (ws required).  T: the most threads whose
+// lists fit 32 KiB, halved by the plan.  Returns -3 when the grid would pass 2^31 - 1 workgroups.
 int knn_launch(const float* query, const float* ref, int* idx, float* d2, void* ws, int B, int M, int N, int k, int exclude_self, int form,
                hipStream_t st) {
     if (B < 1 || M < 1 || N < 1 || k < 1 || k > GECCO_KNN_MAX_K || form < 0 || form > 2 || (form == 2 && !ws)) return -2;
-    const int cus = device_cus();
-    const int slices = (int)(((long long)N + GECCO_KNN_SPLIT_SLICE - 1) / GECCO_KNN_SPLIT_SLICE);
-    const bool split = form == 2 || (form == 0 && ws && slices > 1 && (long long)B * ((M + 63) / 64) < cus);
-    const int S = split ? slices : 1;
-    knn_key* w = split ? static_cast<knn_key*>(ws) : nullptr;
-    const int T = knn_threads(k, (long long)B * S, M, cus);
-    if (T == 256) return knn_go<256>(query, ref, idx, d2, w, B, M, N, k, exclude_self, S, st);
-    if (T == 128) return knn_go<128>(query, ref, idx, d2, w, B, M, N, k, exclude_self, S, st);
-    return knn_go<64>(query, ref, idx, d2, w, B, M, N, k, exclude_self, S, st);
+    const CloudPlan p = cloud_plan(B, M, N, form, ws != nullptr, cloud_max_threads(k), device_cus());
+    if (!p.fits()) return -3;
+    knn_key* w = p.split ? static_cast<knn_key*>(ws) : nullptr;
+    const size_t lds = (size_t)8 * p.T * k;
+    dispatch_T(p.T, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(knn_scan_kernel<T>, dim3((unsigned)p.blocks), dim3(T), lds, st, query, ref, idx, d2, w, M, N, k, exclude_self, p.tiles,
+                           p.S, p.S == 1 ? (unsigned)N : (unsigned)GECCO_KNN_SPLIT_SLICE);
+        if (w) hipLaunchKernelGGL(knn_merge_kernel<T>, dim3((unsigned)(B * p.tiles)), dim3(T), lds, st, w, idx, d2, M, k, p.tiles, p.S);
+    });
+    return (int)hipGetLastError();
 }

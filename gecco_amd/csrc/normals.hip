@@ -17,8 +17,7 @@
 // cloud that sits in L2: 100 000 points are 1.2 MB); the second pass finds them in cache.  Which of the k entries count is a 64-bit
 // mask in registers (k <= 64).  Every loop has a trip count that depends on k alone; nothing is shared between queries after the
 // staging, there are no atomics and no workgroup waits on another, so a row's bits depend on that row's inputs and nothing else.
-#include "../../include/gecco_hip.h"
-#include "common.h"
+#include "cloud_nn.h"
 #include "kernels.h"
 #include "launch_state.h"
 
@@ -27,19 +26,7 @@ namespace {
 constexpr int NORMALS_SWEEPS = 4;
 static_assert(GECCO_KNN_MAX_K <= 64, "the neighbourhood mask of a query is one 64-bit word");
 static_assert(2 * 4 * 256 * 17 <= 64 * 1024 && 2 * 4 * 128 * 33 <= 64 * 1024 && 2 * 4 * 64 * (GECCO_KNN_MAX_K | 1) <= 64 * 1024,
-              "the idx and d2 tiles of a workgroup fit the LDS a kernel has without an opt-in (normals_threads)");
-
-static __device__ __forceinline__ bool normals_finite3(float x, float y, float z) {
-    return fabsf(x) <= 3.402823466e38f && fabsf(y) <= 3.402823466e38f && fabsf(z) <= 3.402823466e38f;   // false for NaN and inf
-}
-
-// the kNN spelling of the squared distance (knn_dist2_bits): every operation rounded to fp32, none contracted, NaN -> +inf
-static __device__ __forceinline__ float normals_dist2(float qx, float qy, float qz, float px, float py, float pz) {
-#pragma clang fp contract(off)
-    const float dx = qx - px, dy = qy - py, dz = qz - pz;
-    const float d = (dx * dx + dy * dy) + dz * dz;
-    return __builtin_fminf(d, __builtin_inff());
-}
+              "the idx and d2 tiles of a workgroup fit the LDS a kernel has without an opt-in (cloud_max_threads)");
 
 // One Jacobi rotation that annihilates a_pq: app, aqq, apq the 2 x 2 block, (arp, arq) the third row's two entries, (v?p, v?q) the two
 // eigenvector columns.  theta = (aqq - app) / (2 apq) overflows when apq is tiny: a non-finite theta gives t = 0 (the entry is already
@@ -83,7 +70,8 @@ static __device__ __forceinline__ void normals_order(float& la, float& lb, float
 }
 
 // grid: B * tiles blocks, block (b, tile) owns queries tile * T .. + T - 1 of cloud b.  d2 == null with a radius: the distances are
-// recomputed from the coordinates.  LDS: T * (k | 1) words of idx, then as many of d2 when use_d2.
+// recomputed from the coordinates (cloud_dist2_inf: the search's own roundings).  LDS: T * (k | 1) words of idx, then as many of d2
+// when use_d2.
 template <int T>
 __global__ __launch_bounds__(T) void normals_kernel(const float* __restrict__ ref, const float* __restrict__ query, const int* __restrict__ idx,
                                                     const float* __restrict__ d2, const float* __restrict__ viewpoint, float radius2,
@@ -125,7 +113,7 @@ __global__ __launch_bounds__(T) void normals_kernel(const float* __restrict__ re
 
     // pass 1: which entries count, their number and their sum.  An index outside [0, N) is never dereferenced: the row is invalid
     unsigned long long mask = 0;
-    bool ok = normals_finite3(qx, qy, qz);
+    bool ok = cloud_finite3(qx, qy, qz);
     int m = 0;
     float sx = 0.f, sy = 0.f, sz = 0.f;
 #pragma unroll 4
@@ -137,12 +125,12 @@ __global__ __launch_bounds__(T) void normals_kernel(const float* __restrict__ re
         }
         const float px = rb[3 * (size_t)j], py = rb[3 * (size_t)j + 1], pz = rb[3 * (size_t)j + 2];
         if (use_radius) {
-            const float d = use_d2 ? myd[t] : normals_dist2(qx, qy, qz, px, py, pz);
+            const float d = use_d2 ? myd[t] : cloud_dist2_inf(qx, qy, qz, px, py, pz);
             if (!(d <= radius2)) continue;
         }
         mask |= 1ull << t;
         ++m;
-        ok = ok && normals_finite3(px, py, pz);
+        ok = ok && cloud_finite3(px, py, pz);
         sx += px;
         sy += py;
         sz += pz;
@@ -209,25 +197,6 @@ __global__ __launch_bounds__(T) void normals_kernel(const float* __restrict__ re
     if (count) count[row] = m;
 }
 
-// threads per workgroup: the most whose tiles stay near 32 KiB, halved while the grid would leave the device short of two workgroups per CU
-int normals_threads(int k, int B, int M, int cus) {
-    int T = k <= 16 ? 256 : k <= 32 ? 128 : 64;
-    while (T > 64 && (long long)B * ((M + T - 1) / T) < 2LL * cus) T >>= 1;
-    return T;
-}
-
-template <int T>
-int normals_go(const float* ref, const float* query, const int* idx, const float* d2, const float* viewpoint, float radius2, int use_radius,
-               float* normal, float* eigenvalues, float* curvature, int* count, int B, int M, int N, int k, hipStream_t st) {
-    const int tiles = (M + T - 1) / T;
-    const long long blocks = (long long)B * tiles;
-    if (blocks > 0x7fffffffLL) return -3;
-    const size_t lds = (size_t)4 * T * (k | 1) * ((use_radius && d2) ? 2 : 1);
-    hipLaunchKernelGGL(normals_kernel<T>, dim3((unsigned)blocks), dim3(T), lds, st, ref, query, idx, d2, viewpoint, radius2, use_radius, normal,
-                       eigenvalues, curvature, count, M, N, k, tiles);
-    return (int)hipGetLastError();
-}
-
 }  // namespace
 
 // One launch.  radius2 <= 0, +inf or NaN: no radius.  Returns -2 for sizes out of range, -3 when the grid would pass 2^31 - 1 workgroups.
@@ -235,10 +204,13 @@ int normals_launch(const float* ref, const float* query, const int* idx, const f
                    float* eigenvalues, float* curvature, int* count, int B, int M, int N, int k, hipStream_t st) {
     if (B < 1 || M < 1 || N < 1 || k < 1 || k > GECCO_KNN_MAX_K) return -2;
     const int use_radius = radius2 > 0.f && radius2 <= 3.402823466e38f ? 1 : 0;
-    const int T = normals_threads(k, B, M, device_cus());
-    if (T == 256)
-        return normals_go<256>(ref, query, idx, d2, viewpoint, radius2, use_radius, normal, eigenvalues, curvature, count, B, M, N, k, st);
-    if (T == 128)
-        return normals_go<128>(ref, query, idx, d2, viewpoint, radius2, use_radius, normal, eigenvalues, curvature, count, B, M, N, k, st);
-    return normals_go<64>(ref, query, idx, d2, viewpoint, radius2, use_radius, normal, eigenvalues, curvature, count, B, M, N, k, st);
+    // T: the most threads whose tiles stay near 32 KiB, halved by the plan (the direct form: one slice)
+    const CloudPlan p = cloud_plan(B, M, N, 1, false, cloud_max_threads(k), device_cus());
+    if (!p.fits()) return -3;
+    const size_t lds = (size_t)4 * p.T * (k | 1) * ((use_radius && d2) ? 2 : 1);
+    dispatch_T(p.T, [&](auto t) {
+        hipLaunchKernelGGL(normals_kernel<decltype(t)::value>, dim3((unsigned)p.blocks), dim3(p.T), lds, st, ref, query, idx, d2, viewpoint,
+                           radius2, use_radius, normal, eigenvalues, curvature, count, M, N, k, p.tiles);
+    });
+    return (int)hipGetLastError();
 }

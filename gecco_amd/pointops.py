@@ -154,6 +154,52 @@ def _cloud(points: Tensor):
     return p, single
 
 
+def _vp(t):
+    return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _f32(t: Tensor):
+    """the fp32 contiguous copy the library reads, detached, and its device pointer"""
+    x = t.detach().float().contiguous()
+    return x, _ptr(x)   # HIP tensors only: there is no CPU fallback
+
+
+def _same_batching(a: Tensor, a_single: bool, b: Tensor, b_single: bool, a_name: str, b_name: str):
+    if b_single != a_single:
+        raise ValueError(f"{a_name} and {b_name} must both be batched (B, ., 3) or both single (., 3)")
+    if b.shape[0] != a.shape[0]:
+        raise ValueError(f"{a_name} has {a.shape[0]} clouds, {b_name} has {b.shape[0]}")
+
+
+def _check_form(form):
+    if form not in _KNN_FORMS:
+        raise ValueError("form must be None, 'direct' or 'split'")
+
+
+def _positive_f32(value, name: str, catch):
+    """`value` rounded to fp32, as it reaches the library; `catch`: what float() may raise for something that is not a number"""
+    try:
+        v = C.c_float(float(value)).value
+    except catch as e:
+        raise ValueError(f"{name} = {value!r} is not a number") from e
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError(f"{name} = {value!r} must be a finite fp32 number > 0")
+    return v
+
+
+def _per_cloud_vector(value, name: str, B: int, refuse_bool: bool):
+    """numbers or a tensor of shape (3,) or (B, 3), as a tensor (the caller moves it to the device and expands it)"""
+    v = torch.as_tensor(value)
+    if v.is_complex() or (refuse_bool and v.dtype == torch.bool) or tuple(v.shape) not in ((3,), (B, 3)):
+        raise ValueError(f"{name} must be (3,) or ({B}, 3)")
+    return v
+
+
+def _unbatch(out, single: bool):
+    """drop the batch dimension of every tensor of `out` for single clouds (None stays None)"""
+    return [None if t is None else t[0] for t in out] if single else out
+
+
 def _fps(p: Tensor, k: int, start, want_sel2: bool, form):
     """p (B, N, 3) of any float dtype / strides -> idx (B, k) int32, sel2 (B, k) fp32 or None"""
     B, N, _ = p.shape
@@ -172,8 +218,7 @@ def _fps(p: Tensor, k: int, start, want_sel2: bool, form):
     code = 1 if (form == "resident" or (form is None and fits)) else 2
     if isinstance(start, Tensor) and (start.dim() != 1 or start.shape[0] != B or start.is_floating_point() or start.is_complex()):
         raise ValueError(f"start must be an int or an integer tensor of shape ({B},)")
-    x = p.detach().float().contiguous()
-    px = _ptr(x)   # HIP tensors only: there is no CPU fallback
+    x, px = _f32(p)
     if isinstance(start, Tensor):
         st = start.to(device=x.device, dtype=torch.int32).contiguous()
     else:
@@ -181,8 +226,7 @@ def _fps(p: Tensor, k: int, start, want_sel2: bool, form):
     idx = torch.empty(B, k, device=x.device, dtype=torch.int32)
     sel2 = torch.empty(B, k, device=x.device, dtype=torch.float32) if want_sel2 else None
     ws = torch.empty(_fps_workspace_bytes(B, N), device=x.device, dtype=torch.uint8) if code == 2 else None
-    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-    _lib.check(_lib.load().gecco_fps_f32(px, vp(st), vp(idx), _ptr(sel2), vp(ws), B, N, k, code, _stream()), "gecco_fps_f32")
+    _lib.check(_lib.load().gecco_fps_f32(px, _vp(st), _vp(idx), _ptr(sel2), _vp(ws), B, N, k, code, _stream()), "gecco_fps_f32")
     return idx, sel2
 
 
@@ -195,13 +239,11 @@ def farthest_point_sample(points: Tensor, k: int, start=0, return_distances: boo
     force one — same indices either way.  ValueError for k < 1 or k > N; GeccoHipError for CPU tensors.  No gradient: indices."""
     p, single = _cloud(points)
     idx, sel2 = _fps(p, k, start, return_distances, form)
-    idx = idx.long()
-    if single:
-        idx = idx[0]
-    if not return_distances:
-        return idx
-    dist = sel2.sqrt()
-    return idx, (dist[0] if single else dist)
+    out = [idx.long()]
+    if return_distances:
+        out.append(sel2.sqrt())
+    out = _unbatch(out, single)
+    return tuple(out) if return_distances else out[0]
 
 
 def farthest_point_subsample(points: Tensor, k: int, start=0, form: str | None = None) -> Tensor:
@@ -220,8 +262,7 @@ def _knn_workspace_bytes(B: int, M: int, N: int, k: int) -> int:
 
 def _knn(q: Tensor, r: Tensor | None, k: int, exclude_self: bool, want_d2: bool, form):
     """q (B, M, 3), r (B, N, 3) or None (= q) of any float dtype / strides -> idx (B, M, k) int32, d2 (B, M, k) fp32 or None"""
-    if form not in _KNN_FORMS:
-        raise ValueError("form must be None, 'direct' or 'split'")
+    _check_form(form)
     B, M, _ = q.shape
     k = int(k)
     if r is not None and r.shape[0] != B:
@@ -235,13 +276,8 @@ def _knn(q: Tensor, r: Tensor | None, k: int, exclude_self: bool, want_d2: bool,
         raise ValueError(f"k = {k} is not in 1 .. {KNN_MAX_K}")
     if k > N - int(exclude_self):
         raise ValueError(f"k = {k} above the {N - int(exclude_self)} candidates of a query")
-    x = q.detach().float().contiguous()
-    px = _ptr(x)   # HIP tensors only: there is no CPU fallback
-    if r is None or r is q:
-        y, py = x, px
-    else:
-        y = r.detach().float().contiguous()
-        py = _ptr(y)
+    x, px = _f32(q)
+    y, py = (x, px) if r is None or r is q else _f32(r)
     idx = torch.empty(B, M, k, device=x.device, dtype=torch.int32)
     d2 = torch.empty(B, M, k, device=x.device, dtype=torch.float32) if want_d2 else None
     # a workspace is offered where knn_launch's auto rule can take the split form; the library decides
@@ -249,8 +285,7 @@ def _knn(q: Tensor, r: Tensor | None, k: int, exclude_self: bool, want_d2: bool,
     offer = form == "split" or (form is None and slices > 1
                                 and B * ((M + 63) // 64) < torch.cuda.get_device_properties(x.device).multi_processor_count)
     ws = torch.empty(_knn_workspace_bytes(B, M, N, k), device=x.device, dtype=torch.uint8) if offer else None
-    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-    _lib.check(_lib.load().gecco_knn_f32(px, py, vp(idx), _ptr(d2), vp(ws), B, M, N, k, int(bool(exclude_self)), _KNN_FORMS[form],
+    _lib.check(_lib.load().gecco_knn_f32(px, py, _vp(idx), _ptr(d2), _vp(ws), B, M, N, k, int(bool(exclude_self)), _KNN_FORMS[form],
                                          _stream()), "gecco_knn_f32")
     return idx, d2
 
@@ -268,18 +303,16 @@ def knn(query: Tensor, ref: Tensor | None = None, k: int = 16, exclude_self: boo
     r = None
     if ref is not None:
         r, rsingle = _cloud(ref)
-        if rsingle != single:
+        if rsingle != single:   # (_knn compares the cloud counts, after the form: not _same_batching)
             raise ValueError("query and ref must both be batched (B, ., 3) or both single (., 3)")
     if exclude_self is None:
         exclude_self = ref is None
     idx, d2 = _knn(q, r, k, bool(exclude_self), return_distances, form)
-    idx = idx.long()
-    if single:
-        idx = idx[0]
-    if not return_distances:
-        return idx
-    dist = d2.sqrt()
-    return idx, (dist[0] if single else dist)
+    out = [idx.long()]
+    if return_distances:
+        out.append(d2.sqrt())
+    out = _unbatch(out, single)
+    return tuple(out) if return_distances else out[0]
 
 
 def knn_gather(values: Tensor, idx: Tensor) -> Tensor:
@@ -302,8 +335,7 @@ def statistical_outlier_mask(points: Tensor, k: int = 16, std_ratio: float = 2.0
     _, d2 = _knn(p, None, k, True, True, None)
     score = d2.sqrt().mean(-1)
     keep = score <= score.mean(-1, keepdim=True) + float(std_ratio) * score.std(-1, keepdim=True)
-    if single:
-        keep, score = keep[0], score[0]
+    keep, score = _unbatch([keep, score], single)
     return (keep, score) if return_scores else keep
 
 
@@ -325,12 +357,8 @@ def estimate_normals(points: Tensor, k: int = 16, radius: float | None = None, v
     q = None
     if query is not None:
         q, qsingle = _cloud(query)
-        if qsingle != single:
-            raise ValueError("points and query must both be batched (B, ., 3) or both single (., 3)")
-        if q.shape[0] != p.shape[0]:
-            raise ValueError(f"points has {p.shape[0]} clouds, query has {q.shape[0]}")
-    if form not in _KNN_FORMS:
-        raise ValueError("form must be None, 'direct' or 'split'")
+        _same_batching(p, single, q, qsingle, "points", "query")
+    _check_form(form)
     B, N, _ = p.shape
     M = N if q is None else q.shape[1]
     if B < 1 or M < 1 or N < 1:
@@ -355,18 +383,9 @@ def estimate_normals(points: Tensor, k: int = 16, radius: float | None = None, v
         if not radius > 0:
             raise ValueError(f"radius = {radius} must be > 0")
         radius2 = radius * radius   # rounded to fp32 on its way into the library
-    vw = None
-    if viewpoint is not None:
-        vw = torch.as_tensor(viewpoint)
-        if vw.is_complex() or tuple(vw.shape) not in ((3,), (B, 3)):
-            raise ValueError(f"viewpoint must be (3,) or ({B}, 3)")
-    x = p.detach().float().contiguous()
-    px = _ptr(x)   # HIP tensors only: there is no CPU fallback
-    if q is None:
-        y, py = x, px
-    else:
-        y = q.detach().float().contiguous()
-        py = _ptr(y)
+    vw = None if viewpoint is None else _per_cloud_vector(viewpoint, "viewpoint", B, refuse_bool=False)
+    x, px = _f32(p)
+    y, py = (x, px) if q is None else _f32(q)
     if idx is None:
         ix, d2 = _knn(y, x, k, False, radius is not None, form)
     else:
@@ -379,8 +398,7 @@ def estimate_normals(points: Tensor, k: int = 16, radius: float | None = None, v
     curv = torch.empty(B, M, device=x.device, dtype=torch.float32) if return_curvature else None
     eig = torch.empty(B, M, 3, device=x.device, dtype=torch.float32) if return_eigenvalues else None
     cnt = torch.empty(B, M, device=x.device, dtype=torch.int32) if return_count else None
-    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-    _lib.check(_lib.load().gecco_normals_f32(px, py, vp(ix), _ptr(d2), _ptr(vw), radius2, vp(normals), _ptr(eig), _ptr(curv), vp(cnt),
+    _lib.check(_lib.load().gecco_normals_f32(px, py, _vp(ix), _ptr(d2), _ptr(vw), radius2, _vp(normals), _ptr(eig), _ptr(curv), _vp(cnt),
                                              B, M, N, k, _stream()), "gecco_normals_f32")
     out = [normals]
     if return_curvature:
@@ -389,8 +407,7 @@ def estimate_normals(points: Tensor, k: int = 16, radius: float | None = None, v
         out.append(eig)
     if return_count:
         out.append(cnt.long())
-    if single:
-        out = [t[0] for t in out]
+    out = _unbatch(out, single)
     return out[0] if len(out) == 1 else tuple(out)
 
 
@@ -419,23 +436,13 @@ def voxel_downsample(points: Tensor, voxel_size: float, origin=None, max_voxels:
         raise ValueError("empty batch or cloud")
     if N > VOXEL_MAX_POINTS:
         raise ValueError(f"N = {N} above {VOXEL_MAX_POINTS}")
-    try:
-        size = C.c_float(float(voxel_size)).value   # rounded to fp32, as it reaches the library
-    except (TypeError, OverflowError) as e:
-        raise ValueError(f"voxel_size = {voxel_size!r} is not a number") from e
-    if not (math.isfinite(size) and size > 0):
-        raise ValueError(f"voxel_size = {voxel_size!r} must be a finite fp32 number > 0")
+    size = _positive_f32(voxel_size, "voxel_size", (TypeError, OverflowError))
     if max_voxels is not None:
         max_voxels = int(max_voxels)
         if not 1 <= max_voxels <= N:
             raise ValueError(f"max_voxels = {max_voxels} is not in 1 .. {N}")
-    org = None
-    if origin is not None:
-        org = torch.as_tensor(origin)
-        if org.is_complex() or org.dtype == torch.bool or tuple(org.shape) not in ((3,), (B, 3)):
-            raise ValueError(f"origin must be (3,) or ({B}, 3)")
-    x = p.detach().float().contiguous()
-    px = _ptr(x)   # HIP tensors only: there is no CPU fallback
+    org = None if origin is None else _per_cloud_vector(origin, "origin", B, refuse_bool=True)
+    x, px = _f32(p)
     if org is not None:
         org = org.detach().to(device=x.device, dtype=torch.float32).expand(B, 3).contiguous()
     V = N if max_voxels is None else max_voxels
@@ -445,8 +452,7 @@ def voxel_downsample(points: Tensor, voxel_size: float, origin=None, max_voxels:
     cnt = torch.empty(B, V, device=x.device, dtype=torch.int32) if return_counts else None
     inv = torch.empty(B, N, device=x.device, dtype=torch.int32) if return_inverse else None
     ws = torch.empty(_voxel_workspace_bytes(B, N), device=x.device, dtype=torch.uint8)   # filled by the library, inside the call
-    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-    _lib.check(_lib.load().gecco_voxel_downsample_f32(px, _ptr(org), size, vp(cen), vp(first), vp(cnt), vp(inv), vp(nv), vp(ws), B, N, V,
+    _lib.check(_lib.load().gecco_voxel_downsample_f32(px, _ptr(org), size, _vp(cen), _vp(first), _vp(cnt), _vp(inv), _vp(nv), _vp(ws), B, N, V,
                                                       _stream()), "gecco_voxel_downsample_f32")
     if max_voxels is None:
         V = max(int(nv.max()), 1)   # the one synchronisation
@@ -460,9 +466,7 @@ def voxel_downsample(points: Tensor, voxel_size: float, origin=None, max_voxels:
         out.append(cnt.long())
     if return_inverse:
         out.append(inv.long())
-    if single:
-        out = [t[0] for t in out]
-    return tuple(out)
+    return tuple(_unbatch(out, single))
 
 
 def voxel_pool(values: Tensor, inverse: Tensor, n_voxels, reduce: str = "mean") -> Tensor:
@@ -533,18 +537,14 @@ def icp(source: Tensor, target: Tensor, max_correspondence_distance: float, init
     (`transform_points` is the differentiable way to apply the result)."""
     s, single = _cloud(source)
     t, tsingle = _cloud(target)
-    if tsingle != single:
-        raise ValueError("source and target must both be batched (B, ., 3) or both single (., 3)")
+    _same_batching(s, single, t, tsingle, "source", "target")
     B, M, _ = s.shape
     N = t.shape[1]
-    if t.shape[0] != B:
-        raise ValueError(f"source has {B} clouds, target has {t.shape[0]}")
     if B < 1 or M < 1 or N < 1:
         raise ValueError("empty batch or cloud")
     if method not in _ICP_METHODS:
         raise ValueError("method must be 'point_to_point' or 'point_to_plane'")
-    if form not in _KNN_FORMS:
-        raise ValueError("form must be None, 'direct' or 'split'")
+    _check_form(form)
     nrm = None
     if method == "point_to_plane":
         if target_normals is None:
@@ -556,12 +556,7 @@ def icp(source: Tensor, target: Tensor, max_correspondence_distance: float, init
             raise ValueError(f"target_normals of shape {tuple(target_normals.shape)} do not belong to a target of shape {tuple(target.shape)}")
     elif target_normals is not None:
         raise ValueError("target_normals are only used by method 'point_to_plane'")
-    try:
-        r = C.c_float(float(max_correspondence_distance)).value   # rounded to fp32, as it reaches the library
-    except (TypeError, ValueError, OverflowError) as e:
-        raise ValueError(f"max_correspondence_distance = {max_correspondence_distance!r} is not a number") from e
-    if not (math.isfinite(r) and r > 0):
-        raise ValueError(f"max_correspondence_distance = {max_correspondence_distance!r} must be a finite fp32 number > 0")
+    r = _positive_f32(max_correspondence_distance, "max_correspondence_distance", (TypeError, ValueError, OverflowError))
     max_iterations = int(max_iterations)
     if not 0 <= max_iterations <= ICP_MAX_ITERATIONS:
         raise ValueError(f"max_iterations = {max_iterations} is not in 0 .. {ICP_MAX_ITERATIONS}")
@@ -576,14 +571,9 @@ def icp(source: Tensor, target: Tensor, max_correspondence_distance: float, init
             raise ValueError(f"init must be (4, 4) or ({B}, 4, 4)") from e
         if T0.is_complex() or T0.dtype == torch.bool or tuple(T0.shape) not in ((4, 4), (B, 4, 4)):
             raise ValueError(f"init must be (4, 4) or ({B}, 4, 4)")
-    x = s.detach().float().contiguous()
-    px = _ptr(x)   # HIP tensors only: there is no CPU fallback
-    y = t.detach().float().contiguous()
-    py = _ptr(y)
-    pn = None
-    if nrm is not None:
-        nrm = nrm.detach().float().contiguous()
-        pn = _ptr(nrm)
+    x, px = _f32(s)
+    y, py = _f32(t)
+    nrm, pn = (None, None) if nrm is None else _f32(nrm)
     if T0 is not None:
         T0 = T0.detach().to(device=x.device, dtype=torch.float64).expand(B, 4, 4).contiguous()
     dev = x.device
@@ -594,14 +584,10 @@ def icp(source: Tensor, target: Tensor, max_correspondence_distance: float, init
     status = torch.empty(B, device=dev, dtype=torch.int32)
     corr = torch.empty(B, M, device=dev, dtype=torch.int32) if return_correspondence else None
     ws = torch.empty(_icp_workspace_bytes(B, M, N), device=dev, dtype=torch.uint8)   # written by the library before it is read
-    vp = lambda a: C.c_void_p(0 if a is None else a.data_ptr())
-    _lib.check(_lib.load().gecco_icp_f32(px, py, pn, vp(T0), r, _ICP_METHODS[method], max_iterations, relative_fitness, relative_rmse,
-                                         vp(T), vp(fit), vp(rmse), vp(its), vp(status), vp(corr), vp(ws), B, M, N, _KNN_FORMS[form],
+    _lib.check(_lib.load().gecco_icp_f32(px, py, pn, _vp(T0), r, _ICP_METHODS[method], max_iterations, relative_fitness, relative_rmse,
+                                         _vp(T), _vp(fit), _vp(rmse), _vp(its), _vp(status), _vp(corr), _vp(ws), B, M, N, _KNN_FORMS[form],
                                          _stream()), "gecco_icp_f32")
-    out = [T, fit, rmse, its.long(), status.long(), None if corr is None else corr.long()]
-    if single:
-        out = [None if o is None else o[0] for o in out]
-    return ICPResult(*out)
+    return ICPResult(*_unbatch([T, fit, rmse, its.long(), status.long(), None if corr is None else corr.long()], single))
 
 
 def transform_points(points: Tensor, transform) -> Tensor:

@@ -8,14 +8,10 @@ only alternative on this device:
 The torch loop is a gather, a subtract (and the squared norm), a min and an argmax per selected point.  Every callable is warmed up once and
 timed by HIP events over `reps` runs (the median is reported).  Prints one JSON line."""
 import argparse
-import json
-import os
-import statistics
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _pointbench import emit, setup, timed
 
 
 def torch_loop(p, k):
@@ -31,30 +27,12 @@ def torch_loop(p, k):
     return idx
 
 
-def timed(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_fps.py needs a GPU: a CPU run says nothing about these kernels")
-    import __graft_entry__ as ge
-    ge.build()
-    from gecco_amd import pointops
+    pointops = setup(__file__)
 
     res = {}
     for name, B, N, k, form in (("a_resident", 64, 2048, 512, "resident"), ("b_streaming", 8, 100_000, 2048, "streaming")):
@@ -65,11 +43,7 @@ def main():
         agree = float((pointops.farthest_point_sample(p, k, form=form) == torch_loop(p, k)).float().mean())
         res[name] = {"B": B, "N": N, "k": k, "form": form, "hip_ms": round(hip, 3), "torch_loop_ms": round(loop, 3),
                      "ratio": round(loop / hip, 2), "hip_us_per_step": round(1e3 * hip / k, 3), "index_agreement": round(agree, 4)}
-    line = json.dumps({"bench": "fps", "device": torch.cuda.get_device_name(0), **res})
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    emit("fps", res, args.out)
 
 
 if __name__ == "__main__":

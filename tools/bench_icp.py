@@ -13,34 +13,13 @@ the call's time over passes + 1.  `evaluate_ms` is a call with max_iterations = 
 the two are also timed in five alternating rounds.
 Every callable is warmed up once and timed by HIP events over `reps` runs (the median is reported); each shape runs in a child process
 of its own under a time limit, and the first failure ends the run.  Prints one JSON line."""
-import argparse
 import json
-import os
-import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _pointbench import main, setup, stream, timed, vp
 
 SHAPES = {"a_16x2048_vs_2048": (16, 2048, 2048), "b_2048_vs_100000": (1, 2048, 100_000), "c_100000_vs_100000": (1, 100_000, 100_000)}
 STEP_SECONDS = 240
 RADIUS = 0.3
-
-
-def timed(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
 
 
 def torch_route(pointops, src, tgt, r, passes):
@@ -73,7 +52,6 @@ def torch_route(pointops, src, tgt, r, passes):
 
 def library_call(pointops, src, tgt, nrm, method, passes, form):
     """gecco_icp_f32 alone on ready fp32 buffers (no copies, no index widening); returns a callable and its output tensors"""
-    import ctypes as C
     import torch
     from gecco_amd import _lib
     lib = _lib.load()
@@ -84,8 +62,7 @@ def library_call(pointops, src, tgt, nrm, method, passes, form):
     fit, rmse = torch.empty(B, device=dev), torch.empty(B, device=dev)
     its, status = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
     ws = torch.empty(pointops._icp_workspace_bytes(B, M, N), dtype=torch.uint8, device=dev)
-    vp = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = stream()
 
     def go():
         _lib.check(lib.gecco_icp_f32(vp(src), vp(tgt), vp(nrm if method else None), None, RADIUS, method, passes, 0.0, 0.0, vp(T), vp(fit),
@@ -94,7 +71,6 @@ def library_call(pointops, src, tgt, nrm, method, passes, form):
 
 
 def knn_k1_ms(pointops, q, p, form, reps):
-    import ctypes as C
     import torch
     from gecco_amd import _lib
     lib = _lib.load()
@@ -103,18 +79,13 @@ def knn_k1_ms(pointops, q, p, form, reps):
     idx = torch.empty(B, M, 1, dtype=torch.int32, device=q.device)
     d2 = torch.empty(B, M, 1, device=q.device)
     ws = torch.empty(pointops._knn_workspace_bytes(B, M, N, 1), dtype=torch.uint8, device=q.device)
-    vp = lambda t: C.c_void_p(t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = stream()
     return timed(lambda: _lib.check(lib.gecco_knn_f32(vp(q), vp(p), vp(idx), vp(d2), vp(ws), B, M, N, 1, 0, form, st), "gecco_knn_f32"), reps)
 
 
 def run_shape(name, reps, passes):
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_icp.py needs a GPU: a CPU run says nothing about these kernels")
-    import __graft_entry__ as ge
-    ge.build()
-    from gecco_amd import pointops
+    pointops = setup(__file__)
     B, M, N = SHAPES[name]
     gen = torch.Generator("cuda").manual_seed(N + M)
     tgt = torch.randn(B, N, 3, device="cuda", generator=gen)
@@ -155,29 +126,5 @@ def run_shape(name, reps, passes):
     print(json.dumps({name: {k: (round(v, 4) if isinstance(v, float) and k.endswith("_ms") else v) for k, v in res.items()}}))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--passes", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--shape", default=None, help="(internal) run one shape in this process")
-    args = ap.parse_args()
-    if args.shape:
-        return run_shape(args.shape, args.reps, args.passes)
-    res = {}
-    for name in SHAPES:   # a fresh process per shape, each under its own time limit; nothing more is started after a failure
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--shape", name, "--reps", str(args.reps), "--passes", str(args.passes)],
-                           stdout=subprocess.PIPE, text=True, timeout=STEP_SECONDS)
-        if r.returncode != 0:
-            raise SystemExit(f"bench_icp.py: shape {name} ended with status {r.returncode}; stopping")
-        res.update(json.loads(r.stdout.strip().splitlines()[-1]))
-    import torch
-    line = json.dumps({"bench": "icp", "device": torch.cuda.get_device_name(0), **res})
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, "icp", SHAPES, STEP_SECONDS, run_shape, options=(("--passes", 10),))

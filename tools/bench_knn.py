@@ -8,15 +8,9 @@ user has without it on the same device: torch.cdist -> topk(largest=False), chun
 (c) self-kNN at B = 1, N = 100 000, k = 16 (the upsampler's output against itself).
 Every callable is warmed up once and timed by HIP events over `reps` runs (the median is reported); each shape runs in a child process of
 its own under a time limit, and the first failure ends the run.  Prints one JSON line."""
-import argparse
 import json
-import os
-import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _pointbench import main, setup, stream, timed, vp
 
 SHAPES = {"a_self_16x2048": (16, 2048, 2048, 16, True), "b_2048_vs_100000": (1, 2048, 100_000, 16, False),
           "c_self_100000": (1, 100_000, 100_000, 16, True)}
@@ -41,24 +35,8 @@ def torch_route(q, p, k, exclude_self):
     return idx, dist
 
 
-def timed(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
-
-
 def kernel_ms(pointops, q, p, k, exclude_self, form, reps):
     """the library call alone on ready fp32 buffers (no copies, no sqrt, no index widening)"""
-    import ctypes as C
     import torch
     from gecco_amd import _lib
     lib = _lib.load()
@@ -67,8 +45,7 @@ def kernel_ms(pointops, q, p, k, exclude_self, form, reps):
     idx = torch.empty(B, M, k, dtype=torch.int32, device=q.device)
     d2 = torch.empty(B, M, k, device=q.device)
     ws = torch.empty(pointops._knn_workspace_bytes(B, M, N, k), dtype=torch.uint8, device=q.device)
-    vp = lambda t: C.c_void_p(t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = stream()
 
     def go():
         _lib.check(lib.gecco_knn_f32(vp(q), vp(p), vp(idx), vp(d2), vp(ws), B, M, N, k, int(exclude_self), form, st), "gecco_knn_f32")
@@ -77,11 +54,7 @@ def kernel_ms(pointops, q, p, k, exclude_self, form, reps):
 
 def run_shape(name, reps):
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_knn.py needs a GPU: a CPU run says nothing about these kernels")
-    import __graft_entry__ as ge
-    ge.build()
-    from gecco_amd import pointops
+    pointops = setup(__file__)
     B, M, N, k, self_mode = SHAPES[name]
     gen = torch.Generator("cuda").manual_seed(N + M)
     p = torch.randn(B, N, 3, device="cuda", generator=gen)
@@ -102,28 +75,5 @@ def run_shape(name, reps):
     print(json.dumps({name: res}))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--shape", default=None, help="(internal) run one shape in this process")
-    args = ap.parse_args()
-    if args.shape:
-        return run_shape(args.shape, args.reps)
-    res = {}
-    for name in SHAPES:   # a fresh process per shape, each under its own time limit; nothing more is started after a failure
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--shape", name, "--reps", str(args.reps)], stdout=subprocess.PIPE,
-                           text=True, timeout=STEP_SECONDS)
-        if r.returncode != 0:
-            raise SystemExit(f"bench_knn.py: shape {name} ended with status {r.returncode}; stopping")
-        res.update(json.loads(r.stdout.strip().splitlines()[-1]))
-    import torch
-    line = json.dumps({"bench": "knn", "device": torch.cuda.get_device_name(0), **res})
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, "knn", SHAPES, STEP_SECONDS, run_shape)

@@ -13,15 +13,9 @@ so a window is 200 launches enqueued back to back and the time is per launch), `
 included, so it is to be held against `kernel_ms`).  Every callable is warmed up once and timed by HIP events over `reps` runs (the
 median is reported); each shape runs in a child process of its own under a time limit, and the first failure ends the run.  Prints one
 JSON line."""
-import argparse
 import json
-import os
-import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _pointbench import main, setup, stream, timed, vp
 
 SHAPES = {"a_self_16x2048": (16, 2048, 2048, 16, True), "b_2048_vs_100000": (1, 2048, 100_000, 16, False),
           "c_self_100000": (1, 100_000, 100_000, 16, True)}
@@ -39,31 +33,10 @@ def torch_route(pointops, p, idx):
     return vec[..., 0], lam[..., 0] / lam.sum(-1)
 
 
-def timed(fn, reps, inner=1):
-    """median over `reps` windows of HIP-event time per call; a window holds `inner` calls enqueued back to back"""
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(inner):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / inner)
-    return statistics.median(ms)
-
-
 def run_shape(name, reps):
-    import ctypes as C
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_normals.py needs a GPU: a CPU run says nothing about these kernels")
-    import __graft_entry__ as ge
-    ge.build()
-    from gecco_amd import _lib, pointops
+    pointops = setup(__file__)
+    from gecco_amd import _lib
     lib = _lib.load()
     B, M, N, k, self_mode = SHAPES[name]
     gen = torch.Generator("cuda").manual_seed(N + M)
@@ -75,8 +48,7 @@ def run_shape(name, reps):
     eig = torch.empty(B, M, 3, device="cuda")
     curv = torch.empty(B, M, device="cuda")
     cnt = torch.empty(B, M, dtype=torch.int32, device="cuda")
-    vp = lambda t: C.c_void_p(t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = stream()
 
     def kernel():
         _lib.check(lib.gecco_normals_f32(vp(p), vp(q), vp(idx32), None, None, 0.0, vp(normal), vp(eig), vp(curv), vp(cnt), B, M, N, k, st),
@@ -98,28 +70,5 @@ def run_shape(name, reps):
     print(json.dumps({name: res}))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--shape", default=None, help="(internal) run one shape in this process")
-    args = ap.parse_args()
-    if args.shape:
-        return run_shape(args.shape, args.reps)
-    res = {}
-    for name in SHAPES:   # a fresh process per shape, each under its own time limit; nothing more is started after a failure
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--shape", name, "--reps", str(args.reps)], stdout=subprocess.PIPE,
-                           text=True, timeout=STEP_SECONDS)
-        if r.returncode != 0:
-            raise SystemExit(f"bench_normals.py: shape {name} ended with status {r.returncode}; stopping")
-        res.update(json.loads(r.stdout.strip().splitlines()[-1]))
-    import torch
-    line = json.dumps({"bench": "normals", "device": torch.cuda.get_device_name(0), **res})
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, "normals", SHAPES, STEP_SECONDS, run_shape)

@@ -10,15 +10,9 @@ batch with the cloud's index as a fourth key column, and synchronises inside uni
 events over `reps` windows (the median is reported; a window of the library call is INNER back-to-back calls, divided by INNER, one of
 a Python-level call or of the composition is a single call); each shape runs in a child process of its own under a time limit, and the first
 failure ends the run.  Prints one JSON line."""
-import argparse
 import json
-import os
-import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _pointbench import main, setup, stream, timed, vp
 
 SHAPES = {"a_16x2048": (16, 2048, 0.8), "b_64x2048": (64, 2048, 0.8), "c_1x100000": (1, 100_000, 0.49)}
 STEP_SECONDS = 240
@@ -39,26 +33,8 @@ def torch_route(p, s):
     return total / count[:, None], count, inverse
 
 
-def timed(fn, reps, inner=1):
-    """median over `reps` windows of `inner` back-to-back calls, per call"""
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(inner):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / inner)
-    return statistics.median(ms)
-
-
 def kernel_ms(pointops, p, s, V, reps):
     """the library call alone on ready fp32 buffers (no copies, no index widening, no trim)"""
-    import ctypes as C
     import torch
     from gecco_amd import _lib
     lib = _lib.load()
@@ -66,8 +42,7 @@ def kernel_ms(pointops, p, s, V, reps):
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=p.device)
     cen, first, count, inverse, nv = torch.empty(B, V, 3, device=p.device), i32(B, V), i32(B, V), i32(B, N), i32(B)
     ws = torch.empty(pointops._voxel_workspace_bytes(B, N), dtype=torch.uint8, device=p.device)
-    vp = lambda t: C.c_void_p(t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = stream()
 
     def go():
         _lib.check(lib.gecco_voxel_downsample_f32(vp(p), None, s, vp(cen), vp(first), vp(count), vp(inverse), vp(nv), vp(ws), B, N, V, st),
@@ -77,11 +52,7 @@ def kernel_ms(pointops, p, s, V, reps):
 
 def run_shape(name, reps):
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_voxel.py needs a GPU: a CPU run says nothing about these kernels")
-    import __graft_entry__ as ge
-    ge.build()
-    from gecco_amd import pointops
+    pointops = setup(__file__)
     B, N, s = SHAPES[name]
     p = torch.randn(B, N, 3, device="cuda", generator=torch.Generator("cuda").manual_seed(N + B))
     V = min(N, 4096)
@@ -100,28 +71,5 @@ def run_shape(name, reps):
     print(json.dumps({name: res}))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--shape", default=None, help="(internal) run one shape in this process")
-    args = ap.parse_args()
-    if args.shape:
-        return run_shape(args.shape, args.reps)
-    res = {}
-    for name in SHAPES:   # a fresh process per shape, each under its own time limit; nothing more is started after a failure
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--shape", name, "--reps", str(args.reps)], stdout=subprocess.PIPE,
-                           text=True, timeout=STEP_SECONDS)
-        if r.returncode != 0:
-            raise SystemExit(f"bench_voxel.py: shape {name} ended with status {r.returncode}; stopping")
-        res.update(json.loads(r.stdout.strip().splitlines()[-1]))
-    import torch
-    line = json.dumps({"bench": "voxel", "device": torch.cuda.get_device_name(0), **res})
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, "voxel", SHAPES, STEP_SECONDS, run_shape)
