@@ -18,15 +18,13 @@
 // queries) read the probability / dS tile back from a wave-private LDS tile as the A operand.
 // Deterministic: per-block partials of the reductions over N (dQ of the pool, dk | dv of the unpool) are summed in a
 // fixed order by reduce_batch_kernel — no float atomics.
-#include "common.h"
+#include "kernel_prims.h"
 #include "kernels.h"
 #include "launch_state.h"
 
 namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // lse2[b, h, i] = log2 sum_n exp2(s2[i, n]) from the forward's per-split (max, sum) partials (log2 domain, scaled scores)
 __global__ void pool_lse_kernel(const float* __restrict__ part_ml, float* __restrict__ lse, int total, int nsplit) {

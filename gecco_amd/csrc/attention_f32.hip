@@ -11,7 +11,7 @@
 //   * the probability tile is already the B operand of O^T = V^T P^T (accumulator-as-operand:
 //     register e of lane half h is key mfma_row(e, h); the V fragment is read in that order).
 // Softmax runs in the log2 domain (queries pre-scaled by log2(e)/sqrt(hd)).
-#include "common.h"
+#include "kernel_prims.h"
 #include "kernels.h"
 #include "launch_state.h"
 
@@ -23,7 +23,6 @@ constexpr float LOG2E = 1.4426950408889634f;
 
 // K/V/Q staging tiles are wave-private: a wave's own LDS writes are ordered before its later reads once they have
 // completed, so a counter wait replaces the workgroup barrier and the four waves run decoupled.
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // ------------------------------------------------------------------------------------- pool
 template <int HD>

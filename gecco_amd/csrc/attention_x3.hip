@@ -14,87 +14,14 @@
 // Head dims: multiples of 16 up to 64; anything else stays on the fp32 kernels.
 // The same kernels serve the fp16 mode (precision 2, template flag F16): one fp16 plane instead of hi | lo, one
 // v_mfma_f32_32x32x16_f16 per product, operands rounded to nearest even.
-#include "common.h"
+#include "kernel_prims.h"
 #include "h8_scales.h"
 #include "kernels.h"
 #include "launch_state.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-
 constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// 4 fp32 -> 4 bf16 hi (top 16 bits) and 4 bf16 lo = rne(x - hi), each packed in two dwords
-// (F16: hi = the 4 values rounded to fp16, lo unused)
-template <bool F16>
-__device__ __forceinline__ void split4(const f32x4& x, u32x2& hi, u32x2& lo) {
-    if (F16) {
-        f16x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (_Float16)x[e];
-        hi = __builtin_bit_cast(u32x2, v);
-        lo = hi;
-        return;
-    }
-    bf16x4 l;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const unsigned ua = __float_as_uint(x[2 * p]), uc = __float_as_uint(x[2 * p + 1]);
-        hi[p] = __builtin_amdgcn_perm(uc, ua, 0x07060302u);  // {hi16(x[2p+1]), hi16(x[2p])}
-        l[2 * p] = (__bf16)(x[2 * p] - __uint_as_float(ua & 0xFFFF0000u));
-        l[2 * p + 1] = (__bf16)(x[2 * p + 1] - __uint_as_float(uc & 0xFFFF0000u));
-    }
-    lo = __builtin_bit_cast(u32x2, l);
-}
-
-// accumulator registers e0 .. e0+7 -> the hi / lo fragments of one 16-key chunk (F16: one fp16 fragment)
-template <bool F16>
-__device__ __forceinline__ void split_acc8(const f32x16& s, int e0, u32x4& hi, u32x4& lo) {
-    if (F16) {
-        f16x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (_Float16)s[e0 + e];
-        hi = __builtin_bit_cast(u32x4, v);
-        lo = hi;
-        return;
-    }
-    u32x4 hb;
-    bf16x8 l;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const float a = s[e0 + 2 * p], c = s[e0 + 2 * p + 1];
-        const unsigned ua = __float_as_uint(a), uc = __float_as_uint(c);
-        hb[p] = __builtin_amdgcn_perm(uc, ua, 0x07060302u);
-        l[2 * p] = (__bf16)(a - __uint_as_float(ua & 0xFFFF0000u));
-        l[2 * p + 1] = (__bf16)(c - __uint_as_float(uc & 0xFFFF0000u));
-    }
-    hi = hb;
-    lo = __builtin_bit_cast(u32x4, l);
-}
-
-__device__ __forceinline__ u32x4 frag(const u16* p) { return *reinterpret_cast<const u32x4*>(p); }
-
-template <bool F16>
-__device__ __forceinline__ f32x16 mfma3(const u32x4& ahi, const u32x4& alo, const u32x4& bhi, const u32x4& blo,
-                                        f32x16 acc) {
-    if (F16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ahi), __builtin_bit_cast(f16x8, bhi), acc, 0, 0, 0);
-    const bf16x8 ah = __builtin_bit_cast(bf16x8, ahi), al = __builtin_bit_cast(bf16x8, alo);
-    const bf16x8 bh = __builtin_bit_cast(bf16x8, bhi), bl = __builtin_bit_cast(bf16x8, blo);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------- pool
 // element offset of value (key, d) in a wave's value tile: 4-key x 32-column blocks of 128 elements (256 B).

@@ -2,22 +2,11 @@
 // forward/backward for the materialised training attention, GaussianActivation / AdaGN / LayerNorm-lower / lift
 // backward.  All reductions that cross workgroups go through per-block partials summed in a fixed order
 // (reduce_batch_kernel): gradients are bitwise reproducible.
-#include "common.h"
+#include "kernel_prims.h"
 #include "kernels.h"
 #include "launch_state.h"
 
 namespace {
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // P[row, :] = softmax(scale * S[row, :]); one wave per row.
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* __restrict__ S, float* __restrict__ P,
@@ -29,14 +18,14 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* __restric
     float* p = P + row * n;
     float m = -INFINITY;
     for (int i = lane; i < n; i += 64) m = fmaxf(m, s[i] * scale);
-    m = wmax(m);
+    m = wave_max(m);
     float l = 0.f;
     for (int i = lane; i < n; i += 64) {
         const float e = __expf(s[i] * scale - m);
         p[i] = e;
         l += e;
     }
-    l = wsum(l);
+    l = wave_sum(l);
     const float inv = 1.0f / l;
     for (int i = lane; i < n; i += 64) p[i] *= inv;
 }
@@ -51,7 +40,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restric
     const float* dp = dP + row * n;
     float d = 0.f;
     for (int i = lane; i < n; i += 64) d += p[i] * dp[i];
-    d = wsum(d);
+    d = wave_sum(d);
     for (int i = lane; i < n; i += 64) dS[row * n + i] = scale * p[i] * (dp[i] - d);
 }
 
@@ -69,7 +58,7 @@ __global__ __launch_bounds__(256) void gauss_act_bwd_kernel(const float* __restr
         du[i] = g * E * (-x / (a * a));
         acc += g * E * (x * x / (a * a * a));
     }
-    acc = wsum(acc);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
@@ -297,10 +286,10 @@ __global__ __launch_bounds__(256) void lower_bwd_kernel(const float* __restrict_
         const float* f = feat + row * C;
         float s1 = 0.f;
         for (int c = lane; c < C; c += 64) s1 += f[c];
-        const float mean = wsum(s1) / C;
+        const float mean = wave_sum(s1) / C;
         float s2 = 0.f;
         for (int c = lane; c < C; c += 64) { const float d = f[c] - mean; s2 += d * d; }
-        const float rstd = rsqrtf(wsum(s2) / C + eps);
+        const float rstd = rsqrtf(wave_sum(s2) / C + eps);
         const float g0 = dF[row * 3 + 0], g1 = dF[row * 3 + 1], g2 = dF[row * 3 + 2];
         // dyhat = dF * W ; LN backward needs mean(dyhat) and mean(dyhat * yhat)
         float m1 = 0.f, m2 = 0.f;
@@ -313,8 +302,8 @@ __global__ __launch_bounds__(256) void lower_bwd_kernel(const float* __restrict_
             wacc[C + c] += g1 * yh;
             wacc[2 * C + c] += g2 * yh;
         }
-        m1 = wsum(m1) / C;
-        m2 = wsum(m2) / C;
+        m1 = wave_sum(m1) / C;
+        m2 = wave_sum(m2) / C;
         for (int c = lane; c < C; c += 64) {
             const float yh = (f[c] - mean) * rstd;
             const float dyh = g0 * W[c] + g1 * W[C + c] + g2 * W[2 * C + c];

@@ -10,16 +10,11 @@
 // of gemm_f32*.hip on rows = B H W (bias + GELU, or bias + residual with layer_scale folded into the weights), and
 // this file holds the HBM-bound rest: patchify stem, depthwise 7x7 + LayerNorm, LayerNorm + 2x2 patch gather, the
 // layer_scale fold.  LayerNorm statistics are per texel over its channels (fp32 sums over <= 768 values).
-#include "common.h"
+#include "kernel_prims.h"
 #include "kernels.h"
 #include "launch_state.h"
 
 namespace {
-
-__device__ __forceinline__ float group_sum(float v, int width) {   // sum over `width` consecutive lanes (power of two <= 64)
-    for (int o = 1; o < width; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- stem: out[b, h, w, :] = LN(W x_patch + bias), x NCHW (B, 3, H, W), patch 4 x 4 stride 4, weight (C, 3, 4, 4).
 // Ho = H / 4, Wo = W / 4 floor like Conv2d: the last H % 4 rows and W % 4 columns of the image are never read.
@@ -61,11 +56,11 @@ __global__ __launch_bounds__(256) void stem_conv_ln_kernel(const float* __restri
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) s1 += acc[j];
-    s1 = group_sum(s1, 8);
+    s1 = lanes_sum(s1, 8);
     const float mean = s1 / C;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) s2 += (acc[j] - mean) * (acc[j] - mean);
-    s2 = group_sum(s2, 8);
+    s2 = lanes_sum(s2, 8);
     const float rstd = rsqrtf(s2 / C + eps);
     if (p < npix) {
 #pragma unroll

@@ -10,15 +10,10 @@
 // taps, convnext.hip `ln_w == null`), GELU forward / backward, and the stem's 4 x 4 patch gather (its weight gradient is a
 // GEMM over the patch matrix).  Column reductions (LayerNorm weight / bias, conv bias, tap gradients) are per-block partials
 // summed in a fixed order by reduce_batch: the gradients are bit-reproducible run to run.
-#include "common.h"
+#include "kernel_prims.h"
 #include "kernels.h"
 
 namespace {
-
-__device__ __forceinline__ float lanes_sum(float v, int width) {   // over `width` consecutive lanes (power of two <= 64)
-    for (int o = 1; o < width; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- LayerNorm backward over the channels of a texel.  y = (z - mean) rstd g + b:
 //   xh = (z - mean) rstd,  gy = dy g,  dz = rstd (gy - mean_c(gy) - xh mean_c(gy xh)),  dg += dy xh,  db += dy,  dzsum += dz

@@ -2,7 +2,7 @@
 // tile mapping with the optional second output segment, and the epilogue (bias, GaussianActivation, residual,
 // GroupNorm partials) through a wave-private LDS transpose with 16-byte nontemporal stores.
 #pragma once
-#include "common.h"
+#include "kernel_prims.h"
 #include "h8_scales.h"
 #include "kernels.h"
 
@@ -17,16 +17,9 @@ __device__ __forceinline__ void dma16(const void* gsrc, float* lds_wave_base) {
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// Counted waits as the s_waitcnt BUILTIN, not inline asm: the compiler's own wait-count scoreboard understands the
-// builtin, so after wait_vm_lgkm0 it knows every earlier LDS read has returned and does not put a second
-// s_waitcnt lgkmcnt(0) in front of the first MFMA that uses last step's fragments — which would also wait for the
-// fragment reads just issued for the NEXT step and expose their whole latency every K-step (it did, with asm).
-// gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14.
-constexpr int waitcnt_imm(int vm, int lgkm) { return (vm & 0xF) | (0x7 << 4) | ((lgkm & 0xF) << 8) | ((vm >> 4) << 14); }
-template <int N>
-__device__ __forceinline__ void wait_vm() { __builtin_amdgcn_s_waitcnt(waitcnt_imm(N, 0xF)); }
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm0() { __builtin_amdgcn_s_waitcnt(waitcnt_imm(N, 0)); }
+// the counted waits (kernel_prims.h) under the names this family calls them by
+using ::wait_vm;
+using ::wait_vm_lgkm0;
 
 // Which tile this block computes.  Optional second output segment (two linears over the same A in one launch): whole
 // column tiles belong to one segment (n_split % 128 == 0); columns below are relative to the segment.
@@ -150,16 +143,12 @@ __device__ __forceinline__ void epilogue_t(const GemmArgs& g, const Tile& t, f32
             if (!C16 && g.c_img) {
                 // tiled split image (GemmArgs::c_img): 8 lanes per 64-column row of the sub-tile, 8 rows per instruction; a lane's 8
                 // consecutive k are 16 bytes of the hi plane and 16 of the lo plane of one 8 KiB block
-                typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-                typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
                 const int lr8 = lane >> 3, c8 = lane & 7;
                 const int n8 = ncol0 + c8 * 8;
                 if (g.c_img == 2) {
                     // h8 activation image (gemm_h8_areg.hip): per (sample, 128-row tile, 64-column group) 6144 floats — fp16 hi
                     // fragments [32-row tile][sub][c][lane], then fp8(2^11 lo) halves [32-row tile][t][lane]; a lane's 8
                     // consecutive columns are one 16-byte hi chunk and 8 lo bytes (Nout % 64 == 0)
-                    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-                    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
                     for (int it = 0; it < 4; ++it) {
                         const int m = mrow0 + it * 8 + lr8;
@@ -245,8 +234,6 @@ __device__ __forceinline__ void epilogue_t(const GemmArgs& g, const Tile& t, f32
                     }
                 }
                 if (C16) {
-                    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-                    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
                     f16x4 hv;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) hv[e] = (_Float16)v4[e];

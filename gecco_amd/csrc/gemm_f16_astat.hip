@@ -34,28 +34,11 @@ namespace {
 
 using dma::dma16;
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int SBK = 32;            // k per stage
 constexpr int S_TILE = 2048;       // floats of one [128][32] fp16 W tile (8 KiB)
 constexpr int S_NT = 256;          // threads
 constexpr int S_PW = 2;            // 1 KiB pieces of a W stage per wave
 constexpr int S_STORES = 32;       // store instructions a wave's epilogue issues (32 x 128 wave tile)
-
-// value of the neighbouring lane (lane ^ 1): one DPP move (quad_perm [1, 0, 3, 2])
-__device__ __forceinline__ unsigned swap_pair(unsigned v) {
-    return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
-}
-
-// W stage pieces by buffer_load ... lds: the per-lane offset is a register computed once, the stage offset a scalar
-__device__ __forceinline__ void dma16_buf(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float* lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
 
 #ifdef ASTAT_STAMPS   // diagnostic build (tools/probe): per-block s_memtime stamps
 __device__ unsigned long long g_astat_stamps[4096 * 8];
@@ -66,16 +49,6 @@ __device__ unsigned long long g_astat_stamps[4096 * 8];
 #else
 #define ASTAMP(i)
 #endif
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-// the same with a second compile-time tag handed through (no wrapper lambda around f: the accumulators stay in registers)
-template <int TAG, int... I, class F>
-__device__ __forceinline__ void static_for_tag(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}, std::integral_constant<int, TAG>{}), ...);
-}
 
 // NK = K / 32 K-steps (compile-time: the A fragments are registers, indexed statically); NS ring slots with
 // NK % NS == 0, so the ring slot of K-step kt of ANY column tile is kt % NS — every LDS address in the loop is static.

@@ -30,9 +30,6 @@ using dma::DNT;
 using dma::D_EPI;
 using dma::dma16;
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int FBK = 32;                    // k per ring stage
 constexpr int FB_TILE = DBN * FBK / 2;     // floats of the fp16 W tile per stage (8 KiB)
 constexpr int fa_tile(int bm, bool a16) { return a16 ? bm * FBK / 2 : bm * FBK; }   // floats of the A tile per stage

@@ -30,9 +30,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 using dma::DBN;
 using dma::DNT;
 using dma::D_EPI;

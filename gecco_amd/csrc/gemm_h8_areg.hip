@@ -33,13 +33,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
 using dma::DBN;
 using dma::DNT;
 using dma::D_EPI;
@@ -49,11 +42,6 @@ constexpr int G_STAGE = 4096;   // floats per 16 KiB W stage: two [128][16 float
 constexpr int A_BLK = 6144;     // floats per (128-row tile, 64-k group) block of the activation image
 constexpr int PW4 = 4;          // 1 KiB W pieces per wave and stage (4 waves; 8 waves: 2)
 constexpr int AL = 6;           // A loads per lane and group: 4 hi + 2 lo
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
 
 // Diagnostic builds (tools/probe/h8areg_probe.hip): -DH8_STAMPS per-block s_memtime stamps; -DH8_DIAG_NOMFMA / _NOEPI
 #ifdef H8_STAMPS
@@ -66,14 +54,6 @@ __device__ unsigned long long g_h8a_stamps[4096 * 4];
 #define ASTAMP(i)
 #endif
 #ifdef H8_DIAG_NOMFMA
-__device__ __forceinline__ f32x16 keep16(f16x8 a, f16x8 b, f32x16 c) {
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-}
-__device__ __forceinline__ f32x16 keep8(i32x8 a, i32x8 b, f32x16 c) {
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-}
 #define A_MFMA16(a, b, c) keep16(a, b, c)
 #define A_MFMA8(a, b, c, sa, sb) keep8(a, b, c)
 #else

@@ -40,16 +40,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int H_BN = 64;           // columns per W tile
 inline bool act_gauss_host(int act) { return act == 1 || act == 2; }
 // the training forms' activations: GaussianActivation (1 normalized / 2 raw) and ReLU (3) — common.h's expressions without the GELU
@@ -69,15 +59,6 @@ constexpr int H_STG = 1536;        // floats of a wave's staging tile: [32][64] 
 constexpr int H_STORES = 8;        // store instructions of a wave's epilogue per column tile
 constexpr float YL_SCALE = H8_AL_SCALE, W8_SCALE = H8_W8_SCALE, WL_SCALE = H8_WL_SCALE;   // h8_scales.h
 
-__device__ __forceinline__ void dma16_buf(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float* lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-
 // Diagnostic builds (tools/probe/h8_probe.hip): -DH8_STAMPS per-block s_memtime stamps; -DH8_DIAG_NOMFMA / _NODMA / _NOACT /
 // _NOSTORE / _NOEPI remove one ingredient each (results are then garbage; only the time is of interest)
 #ifdef H8_DIAG_NOACT
@@ -96,16 +77,8 @@ __device__ unsigned long long g_h8_stamps[1024 * 4];
 #endif
 
 #ifdef H8_DIAG_NOMFMA
-__device__ __forceinline__ f32x16 h8_keep16(f16x8 a, f16x8 b, f32x16 c) {
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-}
-__device__ __forceinline__ f32x16 h8_keep8(i32x8 a, i32x8 b, f32x16 c) {
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-}
-#define H8_MFMA16(a, b, c) h8_keep16(a, b, c)
-#define H8_MFMA8(a, b, c, sa, sb) h8_keep8(a, b, c)
+#define H8_MFMA16(a, b, c) keep16(a, b, c)
+#define H8_MFMA8(a, b, c, sa, sb) keep8(a, b, c)
 #else
 #define H8_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 #ifdef H8_DIAG_CROSSFMT   // timing only: the cross terms' instruction with both operands read as fp6 (2) / fp4 (4) — garbage values
@@ -115,8 +88,6 @@ __device__ __forceinline__ f32x16 h8_keep8(i32x8 a, i32x8 b, f32x16 c) {
 #endif
 #endif
 
-__device__ __forceinline__ float clamp448(float v) { return __builtin_fminf(__builtin_fmaxf(v, -448.f), 448.f); }
-
 // ---- "h6": the two cross terms in fp6 (e2m3) with one E8M0 scale per lane and 64-k group (OCP-MX block scaling: the lane's 32 values
 // ARE a scale block of v_mfma_scale_f32_32x32x64_f8f6f4) instead of fp8 with fixed power-of-two scales.  Both operands 6 bits wide:
 // the instruction takes half the matrix-pipe cycles of the fp8 form (tools/probe/fp6_rate.hip: 1.65x the rate on random operands), and
@@ -124,27 +95,6 @@ __device__ __forceinline__ float clamp448(float v) { return __builtin_fminf(__bu
 // e2m3: 3 mantissa bits like e4m3, normal range [1, 7.5], subnormal step 0.125.  Semantics pinned by tools/probe/fp6_mfma_probe.hip:
 // v_cvt_scalef32_pk32_fp6_f16 divides by its scale operand and packs element i at bit 6 i — the layout the MFMA reads; scale operand =
 // E8M0 byte (2^(byte - 127)) of the selected byte of a VGPR, per lane.
-typedef _Float16 f16x32 __attribute__((ext_vector_type(32)));
-typedef unsigned int u32x6 __attribute__((ext_vector_type(6)));
-// E8M0 byte of the block scale for a block whose largest magnitude is m: m / 2^(byte - 127) in (3.75, 7.5]
-__device__ __forceinline__ int h6_scale_byte(float m) {
-    const int e = (int)(__float_as_uint(m * (16.0f / 15.0f)) >> 23) - 2;
-    return m > 0.f ? (e < 1 ? 1 : e) : 127;
-}
-__device__ __forceinline__ float h6_scale_of(int byte) { return __uint_as_float((unsigned)byte << 23); }
-// largest magnitude of four fp16 fragments (32 values)
-__device__ __forceinline__ float h6_absmax32(f16x8 a, f16x8 b, f16x8 c, f16x8 d) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    auto ab = [](f16x8 v) {
-        u32x4 u = __builtin_bit_cast(u32x4, v);
-        u &= 0x7fff7fffu;
-        return __builtin_bit_cast(f16x8, u);
-    };
-    f16x8 m = __builtin_elementwise_max(__builtin_elementwise_max(ab(a), ab(b)), __builtin_elementwise_max(ab(c), ab(d)));
-    const h2 m2 = __builtin_elementwise_max(__builtin_elementwise_max(h2{m[0], m[1]}, h2{m[2], m[3]}),
-                                            __builtin_elementwise_max(h2{m[4], m[5]}, h2{m[6], m[7]}));
-    return fmaxf((float)m2[0], (float)m2[1]);
-}
 __device__ __forceinline__ u32x6 h6_pack32(f16x8 a, f16x8 b, f16x8 c, f16x8 d, float scale) {
     const f16x32 v = __builtin_shufflevector(__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15),
                                              __builtin_shufflevector(c, d, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15), 0, 1, 2, 3, 4, 5,
@@ -152,14 +102,6 @@ __device__ __forceinline__ u32x6 h6_pack32(f16x8 a, f16x8 b, f16x8 c, f16x8 d, f
     return __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(v, scale);
 }
 #define H6_MFMA(a, b, c, sa, sb) __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 2, 2, 0, sa, 0, sb)
-
-// four floats -> four fp8 (e4m3) bytes, k order
-__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
-    int pk = 0;
-    pk = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, pk, false);
-    pk = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, pk, true);
-    return (unsigned)pk;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // W image.  Stage s = (ct * NG + g) * 2 + kind of 8 KiB each, ct = 64-column tile, g = 64-k group:
@@ -215,7 +157,7 @@ __device__ __forceinline__ void h8_image_item(const float* __restrict__ W, float
                     m = fmaxf(m, fabsf(x));
                 }
             }
-        const int sb = h6_scale_byte(m);
+        const int sb = e8m0_scale_byte(m);
         const float inv = __uint_as_float((unsigned)(254 - sb) << 23);   // 2^(127 - sb): exact
         f16x32 vh;
 #pragma unroll
@@ -505,9 +447,9 @@ __global__ __launch_bounds__(64 * NW, NG > 6 ? 1 : 2) void gemm_h8_astat_kernel(
                     }
                 __builtin_amdgcn_wave_barrier();
                 // the lane's 32 values of this group: element 16 t + 8 c + e = k 64 s + 32 t + 16 h + 8 c + e (the W stream's order)
-                const int bl = h6_scale_byte(h6_absmax32(la[0][0], la[0][1], la[1][0], la[1][1]));
-                const int bh = h6_scale_byte(h6_absmax32(fa[2 * s][0], fa[2 * s][1], fa[2 * s + 1][0], fa[2 * s + 1][1]));
-                const u32x6 pk = h6_pack32(la[0][0], la[0][1], la[1][0], la[1][1], h6_scale_of(bl));
+                const int bl = e8m0_scale_byte(absmax32(la[0][0], la[0][1], la[1][0], la[1][1]));
+                const int bh = e8m0_scale_byte(absmax32(fa[2 * s][0], fa[2 * s][1], fa[2 * s + 1][0], fa[2 * s + 1][1]));
+                const u32x6 pk = h6_pack32(la[0][0], la[0][1], la[1][0], la[1][1], e8m0_scale_of(bl));
 #pragma unroll
                 for (int e = 0; e < 6; ++e) alo[s][e] = (int)pk[e];
                 alo[s][6] = bl > H8_AL_EXP ? bl - H8_AL_EXP : 0;   // the MFMA's scale byte of the lo term: the block scale x 2^-11
@@ -761,7 +703,7 @@ __global__ __launch_bounds__(64 * NW, NG > 6 ? 1 : 2) void gemm_h8_astat_kernel(
                 // yh Wl: fp6(yh / block scale) of the group's 32 values in the image's order, one conversion instruction; the scale's
                 // exponent goes through `opq` (an opaque zero) so that the conversions of all groups are not hoisted out of the tile loop
                 const int bh = alo[gq][7] + opq;
-                const u32x6 pk = h6_pack32(fa[2 * gq][0], fa[2 * gq][1], fa[2 * gq + 1][0], fa[2 * gq + 1][1], h6_scale_of(bh));
+                const u32x6 pk = h6_pack32(fa[2 * gq][0], fa[2 * gq][1], fa[2 * gq + 1][0], fa[2 * gq + 1][1], e8m0_scale_of(bh));
                 const i32x8 a6 = {(int)pk[0], (int)pk[1], (int)pk[2], (int)pk[3], (int)pk[4], (int)pk[5], 0, 0};
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[j] = H6_MFMA(fbA[j], a6, acc[j], fbA[j][6], bh);

@@ -15,7 +15,7 @@
 // 256 x 128 / 128 x 256 tile (2 x 2 waves of 128 x 64 / 64 x 128) 48 per 64, and the 768 x 384 / 384 x 768 gradients of the shipped
 // model become 9 tiles per sample instead of 18 — 432 blocks, one round on the chip's 512 slots instead of 1.7 (opt-in: tn_f16_shape).
 // Slab loads are raw buffer loads (one per-lane offset per operand + scalar offsets), the AdaGN coefficients sit in LDS.
-#include "common.h"
+#include "kernel_prims.h"
 #include "kernels.h"
 #include "launch_state.h"
 
@@ -24,13 +24,6 @@
 #include <type_traits>
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
 
 __device__ __forceinline__ u32x2 cvt4(const f32x4& x) {
     f16x4 v;
@@ -325,12 +318,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f16_kernel(TnArgs g) {
 // conversion, no ds_write: the path that bound the register-staged form.  One barrier per slab; the next slab's DMA flies under this
 // slab's matrix instructions.  The bias gradient (column sums of dY) is one more matrix instruction per A fragment against a fragment
 // of ones (exact products, fp32 accumulation), by the waves of the first K tile's first wave column.
-// (a non-template device function: inside the kernel template the host pass would have to accept the 16-byte form of the builtin, which
-// only the gfx950 target has, and drops the whole instantiation without a word)
-__device__ __forceinline__ void tn_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, u16* lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
 template <int WNT, int WKT>
 __global__ __launch_bounds__(256, 2) void gemm_tn_f16_dma_kernel(TnArgs g) {
     constexpr int TN = 64 * WNT, TK = 64 * WKT, NCA = TN / 32, NCB = TK / 32;
@@ -371,7 +358,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f16_dma_kernel(TnArgs g) {
         u16* dst = lds + (s & 1) * (PA + PB) + (isB ? PA : 0) + q0 * 512;
 #pragma unroll
         for (int i = 0; i < NPW; ++i)
-            tn_dma16(rs, voff[i], so, dst + i * 512);
+            dma16_buf(rs, voff[i], so, dst + i * 512);
     };
     const int tq = (lane & 15) >> 2, tp = lane & 3, tcol = 16 * ((lane >> 4) & 1) + 4 * tp;
     auto frag = [&](const u16* plane, auto NC, int sg, int blk) -> f16x8 {

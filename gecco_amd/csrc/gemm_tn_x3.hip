@@ -12,33 +12,13 @@
 // 128 x 128 output tile per block, 2 x 2 waves of 64 x 64, 32 rows per step, next step's tiles in registers while this
 // one multiplies, two LDS stages (one barrier per step).  One partial per GROUP of samples, summed afterwards in a
 // fixed order (reduce_batch_kernel): bit-reproducible gradients, 1/8 of the partial traffic of one per sample.
-#include "common.h"
+#include "kernel_prims.h"
 #include "kernels.h"
 #include "launch_state.h"
 
 #include <stdlib.h>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-
-// 4 fp32 -> 4 bf16 hi (top 16 bits) and 4 bf16 lo = rne(x - hi), each packed in two dwords
-__device__ __forceinline__ void tn_split4(const f32x4& x, u32x2& hi, u32x2& lo) {
-    bf16x4 l;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const unsigned ua = __float_as_uint(x[2 * p]), uc = __float_as_uint(x[2 * p + 1]);
-        hi[p] = __builtin_amdgcn_perm(uc, ua, 0x07060302u);
-        l[2 * p] = (__bf16)(x[2 * p] - __uint_as_float(ua & 0xFFFF0000u));
-        l[2 * p + 1] = (__bf16)(x[2 * p + 1] - __uint_as_float(uc & 0xFFFF0000u));
-    }
-    lo = __builtin_bit_cast(u32x2, l);
-}
 
 // element offset of (row, col) in a [32][128] plane: 4-row x 32-column blocks of 128 elements (256 B = all 64 banks); the
 // row's 64-byte slot inside its block is rotated by the column block, so the four column blocks a store instruction touches
@@ -106,12 +86,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_x3_kernel(TnArgs g) {
             const int f = tid + i * 256, row = f >> 5, c4 = f & 31, o = tn_off(row, c4 * 4);
             u32x2 hi, lo;
             if (want_cs) cs += ra[i];
-            tn_split4(ra[i], hi, lo);
+            split4<false>(ra[i], hi, lo);
             *reinterpret_cast<u32x2*>(st + o) = hi;
             *reinterpret_cast<u32x2*>(st + TN_PLANE + o) = lo;
             // the AdaGN apply, if any, here — where the loaded values are consumed a step after their loads were issued (applied
             // at the load it would make every step wait for its own global loads)
-            tn_split4(PRO ? (bok ? rb[i] * pa4 + po4 : rb[i]) : rb[i], hi, lo);
+            split4<false>(PRO ? (bok ? rb[i] * pa4 + po4 : rb[i]) : rb[i], hi, lo);
             *reinterpret_cast<u32x2*>(st + 2 * TN_PLANE + o) = hi;
             *reinterpret_cast<u32x2*>(st + 3 * TN_PLANE + o) = lo;
         }

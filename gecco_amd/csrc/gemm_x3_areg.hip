@@ -20,20 +20,12 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 using dma::DBN;
 using dma::DNT;
 using dma::D_EPI;
 using dma::dma16;
 constexpr int RBK = 16;            // k per step
 constexpr int R_TILE = 128 * RBK;  // floats per W block (bf16 hi | lo planes of [128][16]) and per A image block
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
 
 constexpr int r_main_floats(int d) { return d * R_TILE > D_EPI ? d * R_TILE : D_EPI; }
 

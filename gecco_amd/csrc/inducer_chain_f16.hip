@@ -38,12 +38,6 @@ namespace {
 
 using dma::dma16;
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int CH_TILE = 2048;           // floats per 8 KiB weight block
 constexpr int CH_NT = 512;              // threads per block
 constexpr int CH_LDS_BYTES = 160 * 1024;
@@ -55,40 +49,6 @@ constexpr int chain_ns(int C, int WD) {
 }
 constexpr size_t chain_lds_bytes(int C, int WD) {
     return (size_t)chain_ns(C, WD) * CH_TILE * 4 + 64 * (2 * C + 16) + 4 * chain_par_floats(C, WD);
-}
-
-__device__ __forceinline__ void dma16_buf(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float* lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
-__device__ __forceinline__ unsigned swap_pair(unsigned v) {   // value of lane ^ 1 (DPP quad_perm [1, 0, 3, 2])
-    return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
-}
-
-// LDS writes of this wave have landed, then the block barrier (no vmcnt wait: the weight ring stays in flight)
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-// two fp32 -> one dword of two fp16, each rounded on its own (the asm keeps the compiler from folding a preceding
-// fma into v_fma_mixlo_f16, which would round once where every other kernel of the path rounds twice)
-__device__ __forceinline__ unsigned pack2(float v0, float v1) {
-    asm volatile("" : "+v"(v0), "+v"(v1));
-    f16x2 p;
-    p[0] = (_Float16)v0;
-    p[1] = (_Float16)v1;
-    return __builtin_bit_cast(unsigned, p);
-}
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
 #ifdef CHAIN_STAMPS   // diagnostic build (tools/probe): per-block s_memtime stamps of the phases

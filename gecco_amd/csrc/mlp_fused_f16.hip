@@ -27,10 +27,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int MF_NT = 512;             // threads per block
 constexpr int MF_TILE = 2048;          // floats per 8 KiB weight block
 constexpr int MF_RSH = 2 * 64 + 16;    // bytes per row of the hidden K-half buffer (16 B of padding)
@@ -42,26 +38,6 @@ constexpr int mf_ns(int C) {
     return n > 12 ? 12 : n;
 }
 constexpr size_t mf_lds_bytes(int C) { return (size_t)mf_ns(C) * MF_TILE * 4 + mf_fixed_bytes(C); }
-
-__device__ __forceinline__ void mf_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float* lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ unsigned mf_swap_pair(unsigned v) {   // value of lane ^ 1 (DPP quad_perm [1, 0, 3, 2])
-    return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
-}
-__device__ __forceinline__ void mf_lds_barrier() {   // this wave's LDS writes landed, then the block barrier (no vmcnt wait)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-// two fp32 -> two fp16 in one dword, each rounded on its own (the asm keeps a preceding fma out of v_fma_mixlo_f16)
-__device__ __forceinline__ unsigned mf_pack2(float v0, float v1) {
-    asm volatile("" : "+v"(v0), "+v"(v1));
-    f16x2 p;
-    p[0] = (_Float16)v0;
-    p[1] = (_Float16)v1;
-    return __builtin_bit_cast(unsigned, p);
-}
 
 #ifdef MLPF_STAMPS   // diagnostic build (tools/probe): per-block s_memtime stamps of the phases
 __device__ unsigned long long g_mlpf_stamps[2048 * 8];
@@ -119,7 +95,7 @@ __global__ __launch_bounds__(MF_NT, 1) void mlp_fused_f16_kernel(MlpArgs g) {
     int ioff = 0, issued = 0;   // float offset of the ring slot the next block goes to
     auto issue = [&]() {
 #ifndef MLPF_DIAG_NODMA
-        mf_dma16(wrsrc, voff, soff, ring + ioff + wave * 256);
+        dma16_buf(wrsrc, voff, soff, ring + ioff + wave * 256);
 #endif
         soff += MF_TILE * 4u;
 #ifndef MLPF_DIAG_NOADDR
@@ -151,7 +127,7 @@ __global__ __launch_bounds__(MF_NT, 1) void mlp_fused_f16_kernel(MlpArgs g) {
             x0[u] = *reinterpret_cast<const f32x4*>(src);
             x1[u] = *reinterpret_cast<const f32x4*>(src + 4);
         }
-        mf_lds_barrier();   // a | o are in LDS
+        lds_barrier();   // a | o are in LDS
 #pragma unroll
         for (int u = 0; u < ITEMS; ++u) {
             const int i = tid + u * MF_NT, row = i / (C / 8), c8 = i % (C / 8);
@@ -159,14 +135,14 @@ __global__ __launch_bounds__(MF_NT, 1) void mlp_fused_f16_kernel(MlpArgs g) {
             const f32x4 a0 = *reinterpret_cast<const f32x4*>(ap), a1 = *reinterpret_cast<const f32x4*>(ap + 4);
             const f32x4 o0 = *reinterpret_cast<const f32x4*>(ap + C), o1 = *reinterpret_cast<const f32x4*>(ap + C + 4);
             u32x4 pk;
-            pk[0] = mf_pack2(__builtin_fmaf(x0[u][0], a0[0], o0[0]), __builtin_fmaf(x0[u][1], a0[1], o0[1]));
-            pk[1] = mf_pack2(__builtin_fmaf(x0[u][2], a0[2], o0[2]), __builtin_fmaf(x0[u][3], a0[3], o0[3]));
-            pk[2] = mf_pack2(__builtin_fmaf(x1[u][0], a1[0], o1[0]), __builtin_fmaf(x1[u][1], a1[1], o1[1]));
-            pk[3] = mf_pack2(__builtin_fmaf(x1[u][2], a1[2], o1[2]), __builtin_fmaf(x1[u][3], a1[3], o1[3]));
+            pk[0] = pack2(__builtin_fmaf(x0[u][0], a0[0], o0[0]), __builtin_fmaf(x0[u][1], a0[1], o0[1]));
+            pk[1] = pack2(__builtin_fmaf(x0[u][2], a0[2], o0[2]), __builtin_fmaf(x0[u][3], a0[3], o0[3]));
+            pk[2] = pack2(__builtin_fmaf(x1[u][0], a1[0], o1[0]), __builtin_fmaf(x1[u][1], a1[1], o1[1]));
+            pk[3] = pack2(__builtin_fmaf(x1[u][2], a1[2], o1[2]), __builtin_fmaf(x1[u][3], a1[3], o1[3]));
             *reinterpret_cast<u32x4*>(ybuf + row * RSY + ((c8 ^ (row & 15)) << 4)) = pk;
         }
     }
-    mf_lds_barrier();   // y16 complete; a | o no longer needed (hbuf is free)
+    lds_barrier();   // y16 complete; a | o no longer needed (hbuf is free)
     MSTAMP(1);
 
     // ---- the step machine (inducer_chain_f16.hip): one weight block per step.  D = issued - s is NS at a primed
@@ -309,15 +285,15 @@ __global__ __launch_bounds__(MF_NT, 1) void mlp_fused_f16_kernel(MlpArgs g) {
                     v0 = act_apply(v0, neg_inv_2a2, act_mode);
                     v1 = act_apply(v1, neg_inv_2a2, act_mode);
                 }
-                const unsigned own = mf_pack2(v0, v1);
+                const unsigned own = pack2(v0, v1);
                 // even lanes keep row 2p of columns (n, n + 1), odd lanes row 2p + 1 of (n - 1, n)
-                hp[j][p] = __builtin_amdgcn_perm(mf_swap_pair(own), own, psel);
+                hp[j][p] = __builtin_amdgcn_perm(swap_pair(own), own, psel);
             }
         }
         // GEMM b: out += hidden[:, chunk] W2[:, chunk]^T, K-half by K-half (half hf = the columns of the wn == hf waves)
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-            if (hf) mf_lds_barrier();   // every wave is done reading half 0 (the steps of GEMM a separate chunks)
+            if (hf) lds_barrier();   // every wave is done reading half 0 (the steps of GEMM a separate chunks)
             if (wn == hf) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
@@ -327,7 +303,7 @@ __global__ __launch_bounds__(MF_NT, 1) void mlp_fused_f16_kernel(MlpArgs g) {
                         *reinterpret_cast<unsigned*>(hbuf + hr * MF_RSH + 2 * (j * 32 + (r & ~1))) = hp[j][p];
                     }
             }
-            mf_lds_barrier();
+            lds_barrier();
 #pragma unroll
             for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -357,7 +333,7 @@ __global__ __launch_bounds__(MF_NT, 1) void mlp_fused_f16_kernel(MlpArgs g) {
                 rres[set][it] = *reinterpret_cast<const f32x4*>(xw + (size_t)(it * 4 + lr) * C + t * 128);
         };
         fetch(0, 0);
-        mf_lds_barrier();   // every wave is done with the ring and the y16 buffer
+        lds_barrier();   // every wave is done with the ring and the y16 buffer
 #pragma unroll
         for (int t = 0; t < NT1; ++t) {
             const int set = t & 1;
@@ -397,7 +373,7 @@ __global__ __launch_bounds__(MF_NT, 1) void mlp_fused_f16_kernel(MlpArgs g) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the tile is read before the next one overwrites it
         }
         if (g.stats) {
-            mf_lds_barrier();
+            lds_barrier();
             for (int i = tid; i < 2 * C; i += MF_NT) {
                 const int which = i / C, c = i % C;
                 float t = 0.f;

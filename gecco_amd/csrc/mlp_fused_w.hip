@@ -50,7 +50,7 @@
 //
 // Translation units: this file alone is feature_dim 384 + the entry points (MFW_PART 0); mlp_fused_w_p1.hip (512) and mlp_fused_w_p2.hip
 // (128, 256) include it with MFW_PART 1 / 2 — sixteen instantiations of a fully unrolled kernel built side by side instead of in a row.
-#include "common.h"
+#include "kernel_prims.h"
 #include "h8_scales.h"
 #include "kernels.h"
 #include "launch_state.h"
@@ -64,14 +64,6 @@
 #include <utility>
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x32 __attribute__((ext_vector_type(32)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x6 __attribute__((ext_vector_type(6)));
 
 // Shape of an instantiation: feature_dim = 64 NG (NG = 2, 4, 6, 8: 128, 256, 384, 512), width = 2 feature_dim.
 // NG = 8 does not fit the register file in one go (y 128 + 48, the hidden fragments 256, two accumulator pairs 64 and two operand sets 64 are
@@ -114,23 +106,13 @@ constexpr int W_STG = 4096;                // wave-private staging tile of the y
 // the sample's AdaGN coefficients pa | po while the y build runs.  The biases ride in the weight stream's stage headers.
 static_assert(W_STG == 32 * 32 * 4, "the phase-2 tile");
 
-constexpr int waitcnt_imm(int vm, int lgkm) { return (vm & 0xF) | (0x7 << 4) | ((lgkm & 0xF) << 8) | ((vm >> 4) << 14); }
-template <int N>
-__device__ __forceinline__ void wait_vm() { __builtin_amdgcn_s_waitcnt(waitcnt_imm(N, 0xF)); }
 __device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0)); }
 
-template <int... I, class F>
-__device__ __forceinline__ void static_for_w(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { static_for_w(std::make_integer_sequence<int, N>{}, f); }
 #define W_IC(v) std::integral_constant<int, (v)>{}
 
 #ifdef MFW_DIAG_NOMFMA
-__device__ __forceinline__ f32x16 w_keep16(f16x8 a, f16x8 b, f32x16 c) { asm volatile("" ::"v"(a), "v"(b)); return c; }
 __device__ __forceinline__ f32x16 w_keep6(i32x8 a, i32x8 b, f32x16 c, int sa, int sb) { asm volatile("" ::"v"(a), "v"(b), "v"(sa), "v"(sb)); return c; }
-#define W_MFMA16(a, b, c) w_keep16(a, b, c)
+#define W_MFMA16(a, b, c) keep16(a, b, c)
 #define W_MFMA6_(a, b, c, osa, sa, osb, sb) w_keep6(a, b, c, sa, sb)
 #else
 #define W_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
@@ -163,28 +145,12 @@ __device__ unsigned long long g_mfw_stamps[1024 * 8];
 #define WACC_STORE()
 #endif
 
-// E8M0 byte of the block scale for a block whose largest magnitude is m: m / 2^(byte - 127) in (3.75, 7.5] (e2m3's top binades)
-__device__ __forceinline__ int w_scale_byte(float m) {
-    const int e = (int)(__float_as_uint(m * (16.0f / 15.0f)) >> 23) - 2;
-    return m > 0.f ? (e < 1 ? 1 : e) : 127;
-}
-__device__ __forceinline__ float w_scale_of(int byte) { return __uint_as_float((unsigned)byte << 23); }
 template <int K>
 __device__ __forceinline__ f16x8 w_sub(const f16x32& v) {
     return __builtin_shufflevector(v, v, 8 * K, 8 * K + 1, 8 * K + 2, 8 * K + 3, 8 * K + 4, 8 * K + 5, 8 * K + 6, 8 * K + 7);
 }
-// largest magnitude of a lane's 32 halves (gemm_h8_astat.hip's h6_absmax32: sign bits masked, packed fp16 maxima)
-__device__ __forceinline__ float w_absmax32(const f16x32& v) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    auto ab = [](f16x8 a) {
-        u32x4 u = __builtin_bit_cast(u32x4, a);
-        u &= 0x7fff7fffu;
-        return __builtin_bit_cast(f16x8, u);
-    };
-    const f16x8 m = __builtin_elementwise_max(__builtin_elementwise_max(ab(w_sub<0>(v)), ab(w_sub<1>(v))), __builtin_elementwise_max(ab(w_sub<2>(v)), ab(w_sub<3>(v))));
-    const h2 m2 = __builtin_elementwise_max(__builtin_elementwise_max(h2{m[0], m[1]}, h2{m[2], m[3]}), __builtin_elementwise_max(h2{m[4], m[5]}, h2{m[6], m[7]}));
-    return fmaxf((float)m2[0], (float)m2[1]);
-}
+// largest magnitude of a lane's 32 halves
+__device__ __forceinline__ float w_absmax32(const f16x32& v) { return absmax32(w_sub<0>(v), w_sub<1>(v), w_sub<2>(v), w_sub<3>(v)); }
 __device__ __forceinline__ i32x8 w_op6(const u32x4& a, const u32x2& b) {
     return i32x8{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], 0, 0};
 }
@@ -218,7 +184,7 @@ __device__ __forceinline__ WLo w_lo_pack(const float (&v)[32]) {
 #pragma unroll
     for (int i = 0; i < 32; ++i) m = fmaxf(m, fabsf(v[i]));
     WLo r;
-    r.sb = w_scale_byte(m);
+    r.sb = e8m0_scale_byte(m);
     const float inv = __uint_as_float((unsigned)(254 - r.sb) << 23);   // 2^(127 - sb): exact
     f16x32 vh;
 #pragma unroll
@@ -403,7 +369,7 @@ struct WSpan {
 // each matrix instruction (their issue cycles lie inside the 32 the matrix pipe is busy)
 template <int NM, int ND, int NV, int NA = 0, int NX = 1>
 __device__ __forceinline__ void w_interleave() {
-    sfor<NM>([&](auto I) {
+    static_for<NM>([&](auto I) {
         constexpr int i = decltype(I)::value;
         __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
         constexpr int nd = (i + 1) * ND / NM - i * ND / NM, nv = (i + 1) * NV / NM - i * NV / NM;
@@ -585,7 +551,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
             f32x4 xs[2][8];   // (all 48 loads in flight at once measured slower: 21.5 K ticks against 14.8 K for this two-slab ring)
 #pragma unroll
             for (int i = 0; i < 8; ++i) xs[0][i] = *reinterpret_cast<const f32x4*>(xw + (size_t)(4 * i + lrow) * W_C + 4 * c16);
-            sfor<W_NG>([&](auto G) {
+            static_for<W_NG>([&](auto G) {
                 constexpr int gg = decltype(G)::value;
                 if constexpr (gg + 1 < W_NG) {
 #pragma unroll
@@ -633,11 +599,11 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
                         la[8 * s + e] = l8[e];
                     }
                 }
-                const int bl = w_scale_byte(w_absmax32(la));
-                yl6[gg] = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(la, w_scale_of(bl));
+                const int bl = e8m0_scale_byte(w_absmax32(la));
+                yl6[gg] = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(la, e8m0_scale_of(bl));
                 ylp[gg >> 2] |= (bl > H8_AL_EXP ? bl - H8_AL_EXP : 0) << (8 * (gg & 3));
-                const int bh = w_scale_byte(w_absmax32(fa[gg]));
-                if constexpr (NPASS == 1) byf[gg] = w_scale_of(bh);
+                const int bh = e8m0_scale_byte(w_absmax32(fa[gg]));
+                if constexpr (NPASS == 1) byf[gg] = e8m0_scale_of(bh);
                 byp[gg >> 2] |= bh << (8 * (gg & 3));
                 asm volatile("" : "+v"(yl6[gg]));
             });
@@ -645,7 +611,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
         WSTAMP(2);
 
         // ---- the passes over the hidden width (one; two at feature_dim 512: WCfg)
-        sfor<NPASS>([&](auto PASS) {
+        static_for<NPASS>([&](auto PASS) {
         constexpr int pass = decltype(PASS)::value;
         // ---- phase 1.  Two accumulator pairs in turn: one takes the matrix instructions of hidden tile t (it starts as the tile's bias, read
         // from chunk 1 of the tile's first stage) while the other's — tile t - 1, complete — goes through the activation BETWEEN those matrix
@@ -690,7 +656,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
         // block scale of a tile's fp6 form: the bounded activations have a fixed one (|h| <= 2.5: 2^-1; exp(.) <= 1: 2^-2)
         auto act_done = [&](auto T) {
             constexpr int t = decltype(T)::value;
-            hsp[t >> 2] |= (ACT == 1 ? 126 : ACT == 2 ? 125 : w_scale_byte(mact)) << (8 * (t & 3));
+            hsp[t >> 2] |= (ACT == 1 ? 126 : ACT == 2 ? 125 : e8m0_scale_byte(mact)) << (8 * (t & 3));
             mact = 0.f;
         };
         // (diagnostics; the never-taken branch also keeps the register allocator from merging the tiles' live ranges: without one per
@@ -708,20 +674,20 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
         {
             // tile 0's bias: its stage is the next one to be entered (landed: the previous row tile's last stage entry, or the prologue's wait)
             lds_cptr bb = nb16 + (16 * h - 16 * lane);
-            sfor<8>([&](auto Q) { bias_quad(bb, Q, au0); });
+            static_for<8>([&](auto Q) { bias_quad(bb, Q, au0); });
         }
-        sfor<NTP>([&](auto T) {
+        static_for<NTP>([&](auto T) {
             constexpr int t = decltype(T)::value;
             f32x16 (&au)[2] = (t & 1) ? au1 : au0;      // this tile's accumulators
             f32x16 (&ap)[2] = (t & 1) ? au0 : au1;      // the previous tile's, then the next tile's bias
             asm volatile("" : "+s"(opq));
             if constexpr (t > 0) dbg_dump(W_IC(t > 0 ? t - 1 : 0), ap);
-            sfor<SPT>([&](auto SQ) {
+            static_for<SPT>([&](auto SQ) {
                 constexpr int sq = decltype(SQ)::value;      // stage of the tile: groups GS sq ..
                 stage_enter(W_IC(0));
                 const u32x4 hdr = rd16(sb16, 0);
                 lds_cptr nbias = nb16 + (16 * h - 16 * lane);
-                sfor<NSETS>([&](auto I) {
+                static_for<NSETS>([&](auto I) {
                     constexpr int i = decltype(I)::value, gi = i >> 1, k = i & 1, gg = GS * sq + gi, i12 = NSETS * sq + i;
                     WBuf& bc = (i & 1) ? bufB : bufA;
                     WBuf& bn = (i & 1) ? bufA : bufB;
@@ -730,7 +696,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
                     else if constexpr (t == NTP - 1 && sq == SPT - 1) load_p2(nb16, nb8, W_IC(0), W_IC(0), bn);
                     else load_p1(nb16, nb8, nb8b, W_IC(0), W_IC(0), bn);
                     if constexpr (k == 0) {
-                        sfor<3>([&](auto S) {
+                        static_for<3>([&](auto S) {
                             constexpr int s = decltype(S)::value;
 #pragma unroll
                             for (int j = 0; j < 2; ++j) au[j] = W_MFMA16(__builtin_bit_cast(f16x8, bc.q[2 * s + j]), w_sub<s>(fa[gg]), au[j]);
@@ -741,7 +707,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
                         // yh Wl: fp6(yh / block scale), one conversion instruction (the scale behind an opaque asm keeps it inside the tile)
                         float sc;
                         if constexpr (NPASS == 1) sc = byf[gg];
-                        else sc = w_scale_of((byp[gg >> 2] >> (8 * (gg & 3))) & 0xff);
+                        else sc = e8m0_scale_of((byp[gg >> 2] >> (8 * (gg & 3))) & 0xff);
                         asm volatile("" : "+v"(sc), "+s"(opq));
                         const u32x6 y6 = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(fa[gg], sc);
 #ifndef MFW_DIAG_NOT0
@@ -758,8 +724,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
                     // freed registers, QB quads per set: its stage is the next one (landed since this stage's entry)
                     constexpr bool acting = t > 0 && i12 < K::ACT_SETS;
                     constexpr bool biasing = t < NTP - 1 && i12 >= K::BIAS_START;
-                    if constexpr (acting) sfor<K::QA>([&](auto Q) { act_quad(W_IC((K::QA * i12 + decltype(Q)::value) & 7), ap, hf[t > 0 ? t - 1 : 0]); });
-                    if constexpr (biasing) sfor<K::QB>([&](auto Q) { bias_quad(nbias, W_IC((K::QB * (i12 - K::BIAS_START) + decltype(Q)::value) & 7), ap); });
+                    if constexpr (acting) static_for<K::QA>([&](auto Q) { act_quad(W_IC((K::QA * i12 + decltype(Q)::value) & 7), ap, hf[t > 0 ? t - 1 : 0]); });
+                    if constexpr (biasing) static_for<K::QB>([&](auto Q) { bias_quad(nbias, W_IC((K::QB * (i12 - K::BIAS_START) + decltype(Q)::value) & 7), ap); });
                     // the stage two ahead: phase-2 stages from the last two stages of the pass's last hidden tile on
                     constexpr bool ahead1 = !(t == NTP - 1 && sq >= SPT - 2);
                     issue_after(I, W_IC(NSETS), W_IC(ahead1 ? 1 : 0));
@@ -781,7 +747,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
         {
             WACC_BEGIN();
             dbg_dump(W_IC(NTP - 1), au1);
-            sfor<8>([&](auto Q) { act_quad(Q, au1, hf[NTP - 1]); });
+            static_for<8>([&](auto Q) { act_quad(Q, au1, hf[NTP - 1]); });
             act_done(W_IC(NTP - 1));
             asm volatile("" : "+a"(hf[NTP - 1]), "+v"(hsp[(NTP - 1) >> 2]));
             WACC_END(wacc_act);
@@ -795,9 +761,9 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
         constexpr bool H6_FLY = NPASS > 1;
         u32x6 h6[H6_FLY ? 1 : NTP];
         if constexpr (!H6_FLY) {
-            sfor<NTP>([&](auto T) {
+            static_for<NTP>([&](auto T) {
                 constexpr int t = decltype(T)::value;
-                h6[t] = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(hf[t], w_scale_of((hsp[t >> 2] >> (8 * (t & 3))) & 0xff));
+                h6[t] = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(hf[t], e8m0_scale_of((hsp[t >> 2] >> (8 * (t & 3))) & 0xff));
                 asm volatile("" : "+v"(h6[t]));   // these stay in the vector file (the accumulator file holds the 192 registers of hf)
             });
         }
@@ -813,7 +779,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
             float bias = 0.f;
             // the loop's big invariants keep their register files (left alone the allocator rotates the fp6 forms through the accumulator
             // file: 12 moves per hidden tile and output block)
-            sfor<NTP>([&](auto T) {
+            static_for<NTP>([&](auto T) {
                 constexpr int t = decltype(T)::value;
                 f16x32& a = hf[t];
                 if constexpr (H6_FLY) {
@@ -823,7 +789,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
                     asm volatile("" : "+a"(a), "+v"(c));
                 }
             });
-            sfor<2>([&](auto HALF) {
+            static_for<2>([&](auto HALF) {
                 constexpr int half = decltype(HALF)::value;
                 // pieces awaited: the next stage's.  Younger than them: the previous block's 4 stores (first stage of a block but the first)
                 stage_enter(W_IC((half == 0 && !first) ? 4 : 0));
@@ -843,21 +809,21 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_w_kernel(MlpWArgs g) {
                     bias = __uint_as_float(hdr[2]);
                 }
                 W_SCHED();
-                sfor<NSETS>([&](auto I) {
+                static_for<NSETS>([&](auto I) {
                     constexpr int i = decltype(I)::value, pi = i >> 1, tt = i & 1, t = NSETS * half + i;
                     WBuf& bc = (i & 1) ? bufB : bufA;
                     WBuf& bn = (i & 1) ? bufA : bufB;
                     if constexpr (i < NSETS - 1) load_p2(sb16, sb8, W_IC((i + 1) >> 1), W_IC((i + 1) & 1), bn);
                     else if constexpr (half == 0 || !last) load_p2(nb16, nb8, W_IC(0), W_IC(0), bn);
                     else load_p1(nb16, nb8, nb8b, W_IC(0), W_IC(0), bn);      // the next row tile's first set
-                    sfor<4>([&](auto S) {
+                    static_for<4>([&](auto S) {
                         constexpr int s = decltype(S)::value;
                         acc = W_MFMA16(w_sub<s>(hf[t]), __builtin_bit_cast(f16x8, bc.q[s]), (t == 0 && s == 0) ? z16 : acc);
                     });
 #ifndef MFW_DIAG_NOT2
                     u32x6 c6;
                     if constexpr (H6_FLY) {
-                        float sc6 = w_scale_of((hsp[t >> 2] >> (8 * (t & 3))) & 0xff);
+                        float sc6 = e8m0_scale_of((hsp[t >> 2] >> (8 * (t & 3))) & 0xff);
                         asm volatile("" : "+v"(sc6));   // (keeps the conversion inside its set)
                         c6 = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(hf[t], sc6);
                     } else {

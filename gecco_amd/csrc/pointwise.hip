@@ -1,6 +1,6 @@
 // HBM-bound pointwise / reduction kernels of the GECCO denoiser (gfx950): GroupNorm statistics,
 // AdaGN coefficient finalisation, EDM preconditioning, lift (3 -> d) and lower (d -> 3).
-#include "common.h"
+#include "kernel_prims.h"
 #include "kernels.h"
 #include "launch_state.h"
 
@@ -9,12 +9,6 @@
 namespace {
 
 constexpr int STATS_ROWS = 128;  // row-tile height of the stand-alone / lift statistics producers
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- column statistics of a (B, rows, C) tensor: stats[b][tile][{sum,sumsq}][c]
 // Used where no producer epilogue exists (unit-level AdaGN, cached-mode first touch).
@@ -199,7 +193,6 @@ __global__ __launch_bounds__(256) void affine_apply_kernel(const float* __restri
 
 // ---- y16[b,m,c] = fp16(a[b,c] * x[b,m,c] + o[b,c]): the AdaGN apply of the fp16 mode, one fma and one rounding per
 // element — the value the fp16 GEMM's prologue would have formed on the fragment, stored once as its fp16 A operand
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 __global__ __launch_bounds__(256) void affine_cast_f16_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                               const float* __restrict__ o, _Float16* __restrict__ y,
                                                               size_t total8, int rowsC8, int C8) {
@@ -210,7 +203,7 @@ __global__ __launch_bounds__(256) void affine_cast_f16_kernel(const float* __res
         const f32x4 x1 = GECCO_NT_LOAD(reinterpret_cast<const f32x4*>(x) + 2 * i + 1);
         const f32x4 a0 = reinterpret_cast<const f32x4*>(a)[(b * C8 + c8) * 2], a1 = reinterpret_cast<const f32x4*>(a)[(b * C8 + c8) * 2 + 1];
         const f32x4 o0 = reinterpret_cast<const f32x4*>(o)[(b * C8 + c8) * 2], o1 = reinterpret_cast<const f32x4*>(o)[(b * C8 + c8) * 2 + 1];
-        f16x8_t v;
+        f16x8 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             // two roundings, as everywhere else on the path (fp32 fma, then fp32 -> fp16): the empty asm keeps the
@@ -220,7 +213,7 @@ __global__ __launch_bounds__(256) void affine_cast_f16_kernel(const float* __res
             v[e] = (_Float16)f0;
             v[4 + e] = (_Float16)f1;
         }
-        reinterpret_cast<f16x8_t*>(y)[i] = v;
+        reinterpret_cast<f16x8*>(y)[i] = v;
     }
 }
 

@@ -23,13 +23,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-
 constexpr int MF_NT = 512;             // threads per block
 constexpr int MF_TILE = 2048;          // floats per 8 KiB weight block
 constexpr int UO_LDS_BYTES = 160 * 1024;
@@ -48,16 +41,6 @@ constexpr size_t uo_lds_bytes(int C, int HD) {
     const size_t a = (size_t)uo_ns(C, HD) * MF_TILE * 4 + uo_fixed_bytes(C, HD), b = uo_scratch_bytes(C);
     return a > b ? a : b;
 }
-
-__device__ __forceinline__ void mf_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float* lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ void mf_lds_barrier() {   // this wave's LDS writes landed, then the block barrier (no vmcnt wait)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ u32x4 uo_frag(const u16* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 template <int NT1, int HD>
 __global__ __launch_bounds__(MF_NT, 1) void unpool_outproj_f16_kernel(UnpoolProjArgs g) {
@@ -99,7 +82,7 @@ __global__ __launch_bounds__(MF_NT, 1) void unpool_outproj_f16_kernel(UnpoolProj
     unsigned soff = 0;
     int islot = 0, issued = 0;
     auto issue = [&]() {
-        mf_dma16(wrsrc, voff, soff, ring + islot * MF_TILE + wave * 256);
+        dma16_buf(wrsrc, voff, soff, ring + islot * MF_TILE + wave * 256);
         soff += MF_TILE * 4u;
         islot = islot + 1 == NS ? 0 : islot + 1;
         ++issued;
@@ -152,17 +135,17 @@ __global__ __launch_bounds__(MF_NT, 1) void unpool_outproj_f16_kernel(UnpoolProj
         };
         stage_load(0);
         q_load(0, 0);
-        mf_lds_barrier();   // zero fill done
+        lds_barrier();   // zero fill done
 #pragma unroll
         for (int hp = 0; hp < H / 2; ++hp) {
             const int set = hp & 1;
-            if (hp) mf_lds_barrier();   // every wave is done with the previous pair's keys / values
+            if (hp) lds_barrier();   // every wave is done with the previous pair's keys / values
             stage_store();
             if (hp + 1 < H / 2) {
                 stage_load(hp + 1);
                 q_load(hp + 1, set ^ 1);
             }
-            mf_lds_barrier();
+            lds_barrier();
             const u16* Kh = kvs + wn * KVH;
             const u16* Vt = Kh + 64 * KS;
             f32x16 sc[2];
@@ -174,7 +157,7 @@ __global__ __launch_bounds__(MF_NT, 1) void unpool_outproj_f16_kernel(UnpoolProj
             for (int c = 0; c < NC; ++c)
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt) {
-                    const u32x4 kf = uo_frag(Kh + (kt * 32 + r) * KS + c * 16 + 8 * h);
+                    const u32x4 kf = frag(Kh + (kt * 32 + r) * KS + c * 16 + 8 * h);
                     sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, kf),
                                                                     __builtin_bit_cast(f16x8, qf[set][c]), sc[kt], 0, 0, 0);
                 }
@@ -212,7 +195,7 @@ __global__ __launch_bounds__(MF_NT, 1) void unpool_outproj_f16_kernel(UnpoolProj
                     const int c16 = 2 * kt + sg;   // 16-key chunk of the 64 inducers
 #pragma unroll
                     for (int dt = 0; dt < DT; ++dt) {
-                        const u32x4 vf = uo_frag(Vt + (dt * 32 + r) * VS + c16 * 16 + 8 * h);
+                        const u32x4 vf = frag(Vt + (dt * 32 + r) * VS + c16 * 16 + 8 * h);
                         O[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, vf), pf, O[dt], 0, 0, 0);
                     }
                 }
@@ -239,7 +222,7 @@ __global__ __launch_bounds__(MF_NT, 1) void unpool_outproj_f16_kernel(UnpoolProj
                 }
         }
     }
-    mf_lds_barrier();   // the A operand of out_proj is complete
+    lds_barrier();   // the A operand of out_proj is complete
 
     // ---- the step machine (inducer_chain_f16.hip): one weight block per step.  D = issued - s is NS at a primed
     // step: the wait for block s + 1 leaves the NS - 2 younger pieces in flight, the barrier frees block s's slot and
@@ -358,7 +341,7 @@ __global__ __launch_bounds__(MF_NT, 1) void unpool_outproj_f16_kernel(UnpoolProj
                 rres[set][it] = *reinterpret_cast<const f32x4*>(xw + (size_t)(it * 4 + lr) * C + t * 128);
         };
         fetch(0, 0);
-        mf_lds_barrier();   // every wave is done with the ring and the attention-output buffer
+        lds_barrier();   // every wave is done with the ring and the attention-output buffer
 #pragma unroll
         for (int t = 0; t < NT1; ++t) {
             const int set = t & 1;
@@ -398,7 +381,7 @@ __global__ __launch_bounds__(MF_NT, 1) void unpool_outproj_f16_kernel(UnpoolProj
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the tile is read before the next one overwrites it
         }
         if (g.stats) {
-            mf_lds_barrier();
+            lds_barrier();
             for (int i = tid; i < 2 * C; i += MF_NT) {
                 const int which = i / C, c = i % C;
                 float t = 0.f;

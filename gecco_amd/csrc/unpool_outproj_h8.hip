@@ -36,15 +36,6 @@
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-
 constexpr int U_STAGE = 2048;          // floats per 8 KiB ring stage (two 4 KiB sub-tiles)
 constexpr int U_PW = 2;                // 1 KiB W pieces per wave and stage
 // Diagnostic builds (tools/probe/uo8_probe.hip): -DUO8_STAMPS per-block s_memtime stamps; -DUO8_DIAG_NOATT / _NOMFMA / _NOEPI /
@@ -68,15 +59,6 @@ constexpr int u_kv_bytes(int HD) { return ((64 * (HD + 8) + ((HD + 31) / 32) * 3
 // floats of the region that holds the four waves' residual tiles and, during the attention, two staged heads
 constexpr int u_tts_floats(int HD) { return 2 * u_kv_bytes(HD) > 4 * U_TT * 4 ? 2 * u_kv_bytes(HD) / 4 : 4 * U_TT; }
 
-__device__ __forceinline__ void dma16_buf(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, void* lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-
 #ifdef UO8_STAMPS
 __device__ unsigned long long g_uo8_stamps[2048 * 4];
 __device__ unsigned long long g_uo8_epi[2048 * 4];   // per block: ticks inside the epilogues: transposed phase | row phase | first K step of a tile
@@ -91,16 +73,8 @@ __device__ unsigned long long g_uo8_epi[2048 * 4];   // per block: ticks inside 
 
 #define U_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 #ifdef UO8_DIAG_NOMFMA
-__device__ __forceinline__ f32x16 u_keep16(f16x8 a, f16x8 b, f32x16 c) {
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-}
-__device__ __forceinline__ f32x16 u_keep8(i32x8 a, i32x8 b, f32x16 c) {
-    asm volatile("" ::"v"(a), "v"(b));
-    return c;
-}
-#define UG_MFMA16(a, b, c) u_keep16(a, b, c)
-#define UG_MFMA8(a, b, c, sa, sb) u_keep8(a, b, c)
+#define UG_MFMA16(a, b, c) keep16(a, b, c)
+#define UG_MFMA8(a, b, c, sa, sb) keep8(a, b, c)
 #else
 #define UG_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 #define UG_MFMA8(a, b, c, sa, sb) __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, sa, 0, sb)
@@ -115,15 +89,6 @@ __device__ __forceinline__ float max_halves(float v) {
 __device__ __forceinline__ float sum_halves(float v) {
     const auto a = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);
     return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-
-__device__ __forceinline__ float clamp448(float v) { return __builtin_fminf(__builtin_fmaxf(v, -448.f), 448.f); }
-
-__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
-    int pk = 0;
-    pk = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, pk, false);
-    pk = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, pk, true);
-    return (unsigned)pk;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
