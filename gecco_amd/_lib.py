@@ -234,6 +234,9 @@ SIGNATURES = {
     "gecco_normals_f32": (i, [vp, vp, vp, vp, vp, fl, vp, vp, vp, vp, i, i, i, i, vp]),
     "gecco_icp_f32": (i, [vp, vp, vp, vp, fl, i, i, db, db, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]),
     "gecco_icp_workspace_bytes": (sz, [i, i, i]),
+    "gecco_fpfh_f32": (i, [vp, vp, vp, fl, vp, vp, vp, i, i, i, vp]),
+    "gecco_feature_nn_f32": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
+    "gecco_feature_nn_workspace_bytes": (sz, [i, i, i]),
     "gecco_voxel_downsample_f32": (i, [vp, vp, fl, vp, vp, vp, vp, vp, vp, i, i, i, vp]),
     "gecco_voxel_workspace_bytes": (sz, [i, i]),
     "gecco_convnext_stem_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),

@@ -1,5 +1,5 @@
 // C ABI of libgecco_hip.so, part 4 of 4: point-cloud operators and metrics (distance matrix, Chamfer, set metrics, EMD,
-// Sinkhorn, farthest-point sampling, kNN, normals, ICP, voxel grid).
+// Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, voxel grid).
 #include "api_common.h"
 
 using namespace gecco_api;
@@ -232,6 +232,38 @@ int gecco_icp_f32(const float* source, const float* target, const float* normals
                               fitness, inlier_rmse, iterations, status, correspondence, ws, B, M, N, form, (hipStream_t)stream);
     if (rc == -3) return fail(-2, "icp: the grid for B = %d, M = %d, N = %d passes 2^31 - 1 workgroups", B, M, N);
     TRY(rc, "icp");
+    return 0;
+}
+
+// FPFH descriptors (fpfh.hip).  radius2 0: no radius; spfh and count are required (the first launch's outputs, read by the second)
+int gecco_fpfh_f32(const float* points, const float* normals, const int32_t* idx, float radius2, float* fpfh, float* spfh, int32_t* count,
+                   int B, int N, int k, void* stream) {
+    if (!points || !normals || !idx || !fpfh || !spfh || !count) return fail(-1, "fpfh: null argument");
+    if (B < 1 || N < 1) return fail(-2, "fpfh: B = %d, N = %d must both be >= 1", B, N);
+    if (k < 1 || k > GECCO_KNN_MAX_K) return fail(-2, "fpfh: k = %d is not in 1 .. %d", k, GECCO_KNN_MAX_K);
+    if (k > N) return fail(-2, "fpfh: k = %d above N = %d", k, N);
+    if (!(radius2 >= 0.f)) return fail(-2, "fpfh: radius2 = %g must be >= 0 (0: no radius)", (double)radius2);
+    const int rc = fpfh_launch(points, normals, idx, radius2, fpfh, spfh, count, B, N, k, (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "fpfh: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
+    TRY(rc, "fpfh");
+    return 0;
+}
+
+// nearest neighbour in feature space (fpfh.hip).  form as gecco_knn_f32; d2 nullable
+size_t gecco_feature_nn_workspace_bytes(int B, int M, int N) {
+    if (B < 1 || M < 1 || N < 1) return 0;
+    return GECCO_FEATURE_NN_WORKSPACE_BYTES(B, M, N);
+}
+int gecco_feature_nn_f32(const float* a, const float* b, int32_t* idx, float* d2, void* ws, int B, int M, int N, int C, int form,
+                         void* stream) {
+    if (!a || !b || !idx) return fail(-1, "feature_nn: null argument");
+    if (B < 1 || M < 1 || N < 1) return fail(-2, "feature_nn: B = %d, M = %d, N = %d must all be >= 1", B, M, N);
+    if (C < 1 || C > GECCO_FEATURE_MAX_DIM) return fail(-2, "feature_nn: C = %d is not in 1 .. %d", C, GECCO_FEATURE_MAX_DIM);
+    if (form < 0 || form > 2) return fail(-2, "feature_nn: form = %d is not 0 (auto), 1 (direct) or 2 (split)", form);
+    if (form == 2 && !ws) return fail(-1, "feature_nn: the split form needs ws");
+    const int rc = feature_nn_launch(a, b, idx, d2, ws, B, M, N, C, form, (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "feature_nn: the grid for B = %d, M = %d, N = %d passes 2^31 - 1 workgroups", B, M, N);
+    TRY(rc, "feature_nn");
     return 0;
 }
 

@@ -499,6 +499,13 @@ int normals_launch(const float* ref, const float* query, const int* idx, const f
 int icp_launch(const float* source, const float* target, const float* normals, const double* init, float r2, int method, int max_iterations,
                double rel_fitness, double rel_rmse, double* transformation, float* fitness, float* inlier_rmse, int* iterations, int* status,
                int* correspondence, void* ws, int B, int M, int N, int form, hipStream_t st);
+// fpfh.hip — FPFH descriptors from kNN lists and normals (definition: gecco_fpfh_f32): two launches, spfh and count are the first one's
+// outputs and required; radius2 <= 0 or +inf: no radius.  -2: sizes out of range, -3: a grid would pass 2^31 - 1 workgroups
+int fpfh_launch(const float* points, const float* normals, const int* idx, float radius2, float* fpfh, float* spfh, int* count, int B, int N,
+                int k, hipStream_t st);
+// fpfh.hip — nearest neighbour in feature space (definition: gecco_feature_nn_f32).  form as knn_launch; ws of
+// GECCO_FEATURE_NN_WORKSPACE_BYTES(B, M, N) for the split form; d2 nullable.  -2: arguments out of range, -3: as above
+int feature_nn_launch(const float* a, const float* b, int* idx, float* d2, void* ws, int B, int M, int N, int C, int form, hipStream_t st);
 // voxel.hip — voxel-grid downsampling (definition: gecco_voxel_downsample_f32).  origin, first, count, inverse nullable; ws of
 // GECCO_VOXEL_WORKSPACE_BYTES(B, N); V = max_voxels rows per cloud.  -2: sizes out of range, -3: a grid would pass 2^31 - 1 workgroups
 int voxel_launch(const float* points, const float* origin, float voxel_size, float* centroids, int* first, int* count, int* inverse,

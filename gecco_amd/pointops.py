@@ -1,7 +1,8 @@
 """Point-cloud operators on the HIP device: farthest-point sampling (csrc/fps.hip, gecco_fps_f32), k-nearest-neighbour search
 (csrc/knn.hip, gecco_knn_f32) with the statistical outlier filter built on it, surface normals with curvature from the neighbour
 lists (csrc/normals.hip, gecco_normals_f32), voxel-grid downsampling with attribute pooling (csrc/voxel.hip,
-gecco_voxel_downsample_f32), and rigid ICP registration, point-to-point and point-to-plane (csrc/icp.hip, gecco_icp_f32).
+gecco_voxel_downsample_f32), rigid ICP registration, point-to-point and point-to-plane (csrc/icp.hip, gecco_icp_f32), and FPFH
+descriptors with nearest-neighbour matching in feature space (csrc/fpfh.hip, gecco_fpfh_f32, gecco_feature_nn_f32).
 
 The reference reduces a dense cloud to a fixed size by random permutation (gecco-jax data/torch_shapenet.py:20-21, data/taskonomy.py:84),
 which keeps density clumps and loses thin structure.  `farthest_point_sample` is the well-spread cut: from a start point, each next point
@@ -116,6 +117,46 @@ iterations 2, T = the translation by (0.25, 0, 0).  Two launches per pass, 2 * (
 atomics, no workgroup waits on another and no host synchronisation, so a call can be captured in a hipGraph; a stopped cloud costs
 two empty launches per remaining pass.  The outputs are the same bits run to run, in any batch position and in both forms of the
 match ("direct" / "split", the forms and the auto rule of `knn`).
+
+FPFH descriptors and feature matching (`fpfh`, `match_features`).  `icp` converges only from a good `init`; what produces one is a
+global registration on local descriptors.  `fpfh` is Fast Point Feature Histograms (Rusu et al. 2009) in the form Open3D's
+`compute_fpfh_feature` and PCL's `FPFHEstimation` compute: FPFH_BINS = 33 numbers per point from the neighbour list and the normals
+the functions above already produce.  The route without it is `knn_gather`, about twenty torch ops with float atomics for the
+histograms, and `torch.cdist` (an M x N matrix) for the matching.  Definition (include/gecco_hip.h; tests/_fpfh_ref.py restates it in
+numpy).  For point i and neighbour j, in fp64 on the fp32 inputs, every operation rounded and none contracted into an FMA (bin edges
+make the histogram discontinuous; in fp32 two evaluations disagree on a bin every few thousand pairs):
+    1  P1, N1, P2, N2 = double(p_i, n_i, p_j, n_j);  dp = P2 - P1;  d = sqrt((dx dx + dy dy) + dz dz)
+    2  d == 0: f = (0, 0, 0)
+    3  a1 = ((N1x dpx + N1y dpy) + N1z dpz) / d;  a2 the same with N2
+    4  |a1| < |a2|: swap N1 <-> N2, negate dp, f2 = -a2; otherwise f2 = a1 (Open3D's acos(|a1|) > acos(|a2|) without the acos)
+    5  v = dp x N1;  vn = |v| in the spelling of d
+    6  vn == 0: f = (0, 0, 0), all three components, as in Open3D
+    7  v = v / vn;  w = N1 x v;  f1 = v . N2;  f0 = atan2(w . N2, N1 . N2)
+    8  u0 = (11 (f0 + pi)) / (2 pi);  u1 = (11 (f1 + 1)) 0.5;  u2 = (11 (f2 + 1)) 0.5;  b_g = clamp(floor(u_g), 0, 10)
+    9  the pair adds one count to each of the bins b0, 11 + b1, 22 + b2
+Normals are used as given.  The list idx[i, 0 .. k) is that of `knn(points, points, k, exclude_self=False)`, the list
+`estimate_normals` uses: one search serves both.  Entry t counts when 0 <= j < N; j != i, by index (an exact duplicate of the point
+stays a neighbour and contributes the zero triple: bins 5, 16, 27); with a radius, dist2(p_i, p_j) <= fp32(radius^2), the distance
+recomputed from the coordinates with the search's roundings; and all twelve numbers of p_i, n_i, p_j, n_j are finite.  m_i = the number
+of counted entries (`count`).
+    SPFH  spfh[i, b] = fp32((100.0 count_b) / m_i) in double, a zero row when m_i = 0: integer counts, one rounding; each of the three
+          groups of a non-empty row sums to 100
+    FPFH  over the entries of i's list in list order that were counted, have dist2 != 0 and m_j > 0: w_t = 1 / double(dist2_t),
+          W = sum w_t, acc[b] = sum w_t double(spfh[j_t, b]);  fpfh[i, b] = fp32(double(spfh[i, b]) + (W > 0 ? acc[b] / W : 0)).
+          Open3D's per-group factor 100 / sum_group is 1 / W because every non-empty SPFH group sums to 100; written this way no
+          cross-bin reduction order enters the definition.  The point's own SPFH is added unweighted, as in PCL and Open3D
+Points (0,0,0), (1,0,0), (0,1,0), all normals (0,0,1), k = 3: every pair gives f = (0, 0, 0), u = 5.5; every SPFH row is 100 at bins
+5, 16, 27 and every FPFH row 200 there, 0 elsewhere.  Points (0,0,0) with normal (0,0,1) and (1,0,0) with normal (0.6, 0, 0.8), k = 2:
+from point 0 a1 = 0, a2 = 0.6, the swap happens, f2 = -0.6, u2 = 2.2, v = (0,1,0), f1 = 0, u1 = 5.5, f0 = atan2(0.6, 0.8), u0 = 6.63;
+from point 1 no swap and the same triple: both SPFH rows are 100 at bins 6, 16, 24, both FPFH rows 200 there.
+`match_features`: for a (B, M, C) and b (B, N, C), 1 <= C <= FEATURE_MAX_DIM, d2(i, j) = sum_c (a_ic - b_jc)^2 accumulated from 0 in
+the order c = 0 .. C - 1, every operation rounded to fp32 and none contracted; a NaN d2 becomes +inf; the match of row i is the j of
+the smallest (d2, j), the LOWEST index among equal distances (one monotone 64-bit key per pair, the spelling of `knn`); a query whose
+every d2 is +inf gets j = 0 and d2 = +inf.  No M x N matrix is formed.  Mutual: corr[i] = j_i if the match of b[j_i] in a is i, else -1
+(the reverse search plus a gather and a compare in torch).  The forms "direct" / "split" and the auto rule are those of `knn`.
+No atomics and no thread waits on another: the same bits run to run, in any batch position, in both forms of either search and with
+`idx` given or searched.  A non-finite point or normal changes the SPFH rows whose lists name it and the FPFH rows whose lists name it
+or one of those rows, nothing else.
 HIP tensors only: there is no CPU fallback (`voxel_pool`, plain torch, runs on any device)."""
 from __future__ import annotations
 
@@ -139,6 +180,8 @@ VOXEL_MAX_POINTS = 1 << 30       # GECCO_VOXEL_MAX_POINTS
 ICP_MAX_ITERATIONS = 1000        # GECCO_ICP_MAX_ITERATIONS
 _ICP_STATE_BYTES = 160           # GECCO_ICP_STATE_BYTES
 _ICP_METHODS = {"point_to_point": 0, "point_to_plane": 1}
+FPFH_BINS = 33                   # GECCO_FPFH_BINS
+FEATURE_MAX_DIM = 64             # GECCO_FEATURE_MAX_DIM
 
 
 def _fps_workspace_bytes(B: int, N: int) -> int:
@@ -600,3 +643,129 @@ def transform_points(points: Tensor, transform) -> Tensor:
     T = T.to(device=p.device, dtype=p.dtype)
     out = p @ T[..., :3, :3].transpose(-1, -2) + T[..., None, :3, 3]
     return out[0] if single else out
+
+
+def fpfh(points: Tensor, normals: Tensor, k: int = 16, radius: float | None = None, idx: Tensor | None = None, return_spfh: bool = False,
+         form: str | None = None):
+    """FPFH descriptors of the points of a cloud from their k-neighbourhoods and normals (module docstring: the definition).  points and
+    normals (B, N, 3) or (N, 3) on the HIP device, any float dtype and strides (computed on fp32 contiguous copies); the normals are
+    used as given (`estimate_normals(points)` or any others).  The search is `knn(points, points, k, exclude_self=False)` through `form`
+    (None / "direct" / "split": same bits).  idx: the int64 or int32 (B, N, k) — (N, k) for single clouds — indices a caller already
+    holds from that search (the ones `estimate_normals` takes); the search is skipped and k is idx's last dimension.  radius: only
+    neighbours within it count.  Returns fpfh, fp32 (B, N, 33) or (N, 33); with return_spfh also spfh, fp32 of the same shape, and
+    count, int64 (B, N).  ValueError for bad shapes, normals that do not match the points, k outside 1 .. KNN_MAX_K or above N, a radius
+    that is not > 0, an idx whose shape disagrees with the clouds, mixed batched and single inputs, an unknown form; GeccoHipError for
+    CPU tensors.  No gradient: the inputs are detached."""
+    p, single = _cloud(points)
+    if not isinstance(normals, Tensor):
+        raise ValueError("normals must be a tensor")
+    n, nsingle = _cloud(normals)
+    if nsingle != single or n.shape != p.shape:
+        raise ValueError(f"normals of shape {tuple(normals.shape)} do not belong to points of shape {tuple(points.shape)}")
+    _check_form(form)
+    B, N, _ = p.shape
+    if B < 1 or N < 1:
+        raise ValueError("empty batch or cloud")
+    if idx is not None:
+        if not isinstance(idx, Tensor) or idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool:
+            raise ValueError("idx must be an integer tensor")
+        if idx.dim() != (2 if single else 3):
+            raise ValueError("idx must be (N, k) for single clouds and (B, N, k) for batched ones")
+        ix = idx[None] if single else idx
+        if ix.shape[0] != B or ix.shape[1] != N:
+            raise ValueError(f"idx of shape {tuple(idx.shape)} does not belong to {B} clouds of {N} points")
+        k = ix.shape[2]
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k = {k} is not in 1 .. {KNN_MAX_K}")
+    if k > N:
+        raise ValueError(f"k = {k} above the {N} points of a cloud")
+    radius2 = 0.0   # no radius
+    if radius is not None:
+        try:
+            radius = float(radius)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"radius = {radius!r} is not a number") from e
+        if not radius > 0:
+            raise ValueError(f"radius = {radius} must be > 0")
+        radius2 = radius * radius   # rounded to fp32 on its way into the library
+    x, px = _f32(p)
+    y, py = _f32(n)
+    if idx is None:
+        ix, _ = _knn(x, x, k, False, False, form)
+    else:
+        if not ix.is_cuda:
+            raise _lib.GeccoHipError("gecco_amd operators need tensors on the HIP device (no CPU fallback)")
+        ix = ix.detach().to(device=x.device, dtype=torch.int32).contiguous()
+    out = torch.empty(B, N, FPFH_BINS, device=x.device, dtype=torch.float32)
+    spfh = torch.empty(B, N, FPFH_BINS, device=x.device, dtype=torch.float32)
+    cnt = torch.empty(B, N, device=x.device, dtype=torch.int32)
+    _lib.check(_lib.load().gecco_fpfh_f32(px, py, _vp(ix), radius2, _vp(out), _vp(spfh), _vp(cnt), B, N, k, _stream()), "gecco_fpfh_f32")
+    res = _unbatch([out, spfh, cnt.long()] if return_spfh else [out], single)
+    return tuple(res) if return_spfh else res[0]
+
+
+def _feature_nn_workspace_bytes(B: int, M: int, N: int) -> int:
+    """GECCO_FEATURE_NN_WORKSPACE_BYTES(B, M, N)"""
+    return 8 * B * M * ((N + KNN_SPLIT_SLICE - 1) // KNN_SPLIT_SLICE)
+
+
+def _feature_nn(a: Tensor, b: Tensor, want_d2: bool, form):
+    """a (B, M, C), b (B, N, C) fp32 contiguous on the device -> idx (B, M) int32, d2 (B, M) fp32 or None"""
+    B, M, Cn = a.shape
+    N = b.shape[1]
+    idx = torch.empty(B, M, device=a.device, dtype=torch.int32)
+    d2 = torch.empty(B, M, device=a.device, dtype=torch.float32) if want_d2 else None
+    # a workspace is offered where the auto rule can take the split form; the library decides (as in _knn)
+    slices = (N + KNN_SPLIT_SLICE - 1) // KNN_SPLIT_SLICE
+    offer = form == "split" or (form is None and slices > 1
+                                and B * ((M + 63) // 64) < torch.cuda.get_device_properties(a.device).multi_processor_count)
+    ws = torch.empty(_feature_nn_workspace_bytes(B, M, N), device=a.device, dtype=torch.uint8) if offer else None
+    _lib.check(_lib.load().gecco_feature_nn_f32(_ptr(a), _ptr(b), _vp(idx), _ptr(d2), _vp(ws), B, M, N, Cn, _KNN_FORMS[form], _stream()),
+               "gecco_feature_nn_f32")
+    return idx, d2
+
+
+def _features(t, name: str):
+    if not isinstance(t, Tensor) or t.dim() not in (2, 3) or not t.is_floating_point():
+        raise ValueError(f"{name}: expected floating features of shape (B, M, C) or (M, C)")
+    single = t.dim() == 2
+    return (t[None] if single else t), single
+
+
+def match_features(source: Tensor, target: Tensor, mutual: bool = False, return_distances: bool = False, form: str | None = None):
+    """The nearest row of `target` to every row of `source` in feature space (module docstring: the definition).  source (B, M, C) or
+    (M, C), target (B, N, C) or (N, C) on the HIP device, 1 <= C <= FEATURE_MAX_DIM (what `fpfh` returns: C = 33), any float dtype and
+    strides (computed on fp32 contiguous copies).  Returns corr, int64 (B, M) — (M,) for single sets — the index in `target` of each
+    source row, equal distances going to the lowest index; with mutual, -1 where the match of that target row in `source` is not the
+    row itself.  With return_distances also dist = sqrt(d2), fp32 of the same shape (the distance to the nearest row, also where
+    `mutual` rejects it).  form None / "direct" / "split": the forms of `knn`, same bits either way.  ValueError for bad shapes, mixed
+    batched and single inputs, mismatched batch sizes or channel counts, C outside 1 .. FEATURE_MAX_DIM, an unknown form; GeccoHipError
+    for CPU tensors.  No gradient: indices (and the distances are detached)."""
+    a, single = _features(source, "source")
+    b, bsingle = _features(target, "target")
+    if bsingle != single:
+        raise ValueError("source and target must both be batched (B, ., C) or both single (., C)")
+    if b.shape[0] != a.shape[0]:
+        raise ValueError(f"source has {a.shape[0]} sets, target has {b.shape[0]}")
+    if b.shape[2] != a.shape[2]:
+        raise ValueError(f"source has {a.shape[2]} channels, target has {b.shape[2]}")
+    _check_form(form)
+    B, M, Cn = a.shape
+    N = b.shape[1]
+    if B < 1 or M < 1 or N < 1:
+        raise ValueError("empty batch or set")
+    if not 1 <= Cn <= FEATURE_MAX_DIM:
+        raise ValueError(f"C = {Cn} is not in 1 .. {FEATURE_MAX_DIM}")
+    x, _ = _f32(a)
+    y, _ = _f32(b)
+    idx, d2 = _feature_nn(x, y, return_distances, form)
+    corr = idx.long()
+    if mutual:
+        back, _ = _feature_nn(y, x, False, form)
+        corr = torch.where(back.long().gather(1, corr) == torch.arange(M, device=corr.device)[None], corr, torch.full_like(corr, -1))
+    out = [corr]
+    if return_distances:
+        out.append(d2.sqrt())
+    out = _unbatch(out, single)
+    return tuple(out) if return_distances else out[0]

@@ -1031,6 +1031,76 @@ int gecco_icp_f32(const float* source, const float* target, const float* normals
                   float* inlier_rmse, int32_t* iterations, int32_t* status, int32_t* correspondence, void* ws, int B, int M, int N, int form,
                   void* stream);
 size_t gecco_icp_workspace_bytes(int B, int M, int N);
+/* Fast Point Feature Histograms (csrc/fpfh.hip; Rusu et al. 2009) in the form Open3D's compute_fpfh_feature and PCL's FPFHEstimation
+ * compute: GECCO_FPFH_BINS = 33 numbers per point of points (B, N, 3) from the point's k-neighbourhood and normals (B, N, 3), the
+ * descriptor a global registration matches to find the init that gecco_icp_f32 needs.  The reference has nothing of the kind; without
+ * this entry the route is a gathered (B, N, k, .) tensor, the pair formulas elementwise, scatter_add histograms (float atomics) and a
+ * gather with a weighted mean.  tests/_fpfh_ref.py restates the definition in numpy.
+ *     pair feature   for point i and neighbour j, in fp64 on the fp32 inputs, every operation rounded and none contracted into an FMA
+ *                    (bin edges make the histogram discontinuous: in fp32 two evaluations disagree on a bin every few thousand pairs)
+ *                      1  P1, N1, P2, N2 = double(p_i, n_i, p_j, n_j);  dp = P2 - P1;  d = sqrt((dx dx + dy dy) + dz dz)
+ *                      2  d == 0: f = (0, 0, 0)
+ *                      3  a1 = ((N1x dpx + N1y dpy) + N1z dpz) / d;  a2 the same with N2
+ *                      4  |a1| < |a2|: swap N1 <-> N2, negate dp, f2 = -a2; otherwise f2 = a1 (Open3D's acos(|a1|) > acos(|a2|))
+ *                      5  v = dp x N1, each component a difference of two rounded products;  vn = |v| in the spelling of d
+ *                      6  vn == 0: f = (0, 0, 0), all three components, as in Open3D
+ *                      7  v = v / vn per component;  w = N1 x v;  f1 = v . N2;  f0 = atan2(w . N2, N1 . N2), every dot product
+ *                         (x + y) + z
+ *                      8  u0 = (11 (f0 + pi)) / (2 pi);  u1 = (11 (f1 + 1)) 0.5;  u2 = (11 (f2 + 1)) 0.5;  b_g = clamp(floor(u_g), 0, 10)
+ *                         (a NaN u: bin 0)
+ *                      9  the pair adds one count to each of the bins b0, 11 + b1 and 22 + b2
+ *                    Normals are used as given (not normalised)
+ *     neighbourhood  idx (B, N, k) int32 is the list of gecco_knn_f32(points, points, k) WITHOUT exclude_self, the list
+ *                    gecco_normals_f32 uses: one search serves both.  Entry t counts when 0 <= j < N (an index outside is never
+ *                    dereferenced);  j != i, by index, so an exact duplicate of the point stays a neighbour and contributes the zero
+ *                    triple (bins 5, 16, 27);  with a radius (radius2 > 0 and finite; 0 or +inf: none), dist2(p_i, p_j) <= radius2 in
+ *                    the spelling of gecco_knn_f32, recomputed from the coordinates;  and all twelve numbers of p_i, n_i, p_j, n_j are
+ *                    finite.  m_i is the number of counted entries: count (B, N)
+ *     SPFH           spfh[i, b] = fp32((100.0 count_b) / m_i) in double, a zero row when m_i = 0.  Counts are integers, so this pass
+ *                    is exact; each of the three groups of a non-empty row sums to 100
+ *     FPFH           over the entries of i's list in list order that were counted above, have dist2 != 0 and m_j > 0:
+ *                    w_t = 1 / double(dist2_t);  W = sum w_t;  acc[b] = sum w_t double(spfh[j_t, b]);
+ *                    fpfh[i, b] = fp32(double(spfh[i, b]) + (W > 0 ? acc[b] / W : 0)).  Open3D normalises each group of 11 bins by
+ *                    100 / sum_group; every non-empty SPFH group sums to 100, so that factor is 1 / W, written directly so that no
+ *                    cross-bin reduction order enters the definition.  The point's own SPFH is added unweighted, as in PCL and Open3D
+ * Worked examples.  (a) points (0,0,0), (1,0,0), (0,1,0), all normals (0,0,1), k = 3: every pair gives f = (0, 0, 0), u = 5.5, bin 5 of
+ * every group; every SPFH row is 100 at bins 5, 16, 27 and every FPFH row 200 there, 0 elsewhere.  (b) points (0,0,0) with normal
+ * (0,0,1) and (1,0,0) with normal (0.6, 0, 0.8), k = 2: from point 0, a1 = 0 and a2 = 0.6, so the swap happens, f2 = -0.6, u2 = 2.2,
+ * v = (0,1,0), f1 = 0, u1 = 5.5, f0 = atan2(0.6, 0.8), u0 = 6.63; from point 1 no swap and the same triple; both SPFH rows are 100 at
+ * bins 6, 16, 24 and both FPFH rows 200 there.
+ * Outputs, every element written: fpfh (B, N, 33) fp32; spfh (B, N, 33) fp32 and count (B, N) int32, REQUIRED: they are the first
+ * launch's outputs, which the second reads.  1 <= k <= GECCO_KNN_MAX_K, k <= N; any B, N >= 1.
+ * Two launches: one thread per point counts into 33 byte counters of its own in LDS; then 33 consecutive threads per point, one per
+ * bin, sum the neighbours' rows in list order.  No atomics and no thread waits on another; a row of spfh depends on that point's list
+ * and the points and normals it names, a row of fpfh on those and on the spfh rows of the points its list names, nothing else: the
+ * same bits run to run and in any batch position, and a non-finite point or normal changes only the rows that reach it this way.
+ * Negative return (and gecco_last_error) before anything is enqueued for: a null argument, B or N < 1, k outside 1 ..
+ * GECCO_KNN_MAX_K or above N, a negative or NaN radius2, a grid above 2^31 - 1 workgroups.  Asynchronous on `stream`, no allocation,
+ * no synchronisation. */
+#define GECCO_FPFH_BINS 33
+int gecco_fpfh_f32(const float* points, const float* normals, const int32_t* idx, float radius2, float* fpfh, float* spfh, int32_t* count,
+                   int B, int N, int k, void* stream);
+/* Nearest neighbour in feature space (csrc/fpfh.hip): for every row of a (B, M, C) the nearest row of b (B, N, C), 1 <= C <=
+ * GECCO_FEATURE_MAX_DIM, with no M x N matrix (the route without this entry is cdist -> argmin).
+ *     d2(i, j) = sum_c (a_ic - b_jc)^2, accumulated from 0 in the order c = 0 .. C - 1, every operation rounded to fp32 and none
+ *     contracted into an FMA; a NaN d2 becomes +inf.  The match of row i is the j of the smallest (d2, j): the LOWEST index among
+ *     equal distances, one monotone 64-bit key per pair (d2's bits above j), the spelling of gecco_knn_f32.  A query whose every d2 is
+ *     +inf (a NaN channel) gets j = 0 and d2 = +inf; a row of b with a NaN channel is never matched while a finite row exists.
+ * Zero-filling channels up to a multiple of 4 adds exact zeros and changes no bit: the kernel pads on load to a compile-time width
+ * (the smallest of 4, 16, 36, 64 that holds C) and makes no padded copy in memory.  idx (B, M) int32; d2 (B, M) fp32 or NULL.
+ * form 1: "direct", one launch, one thread per query, b streamed through LDS; form 2: "split", slices of GECCO_KNN_SPLIT_SLICE rows of
+ * b, one key per (query, slice), a second launch takes the minimum (exact); form 0: the auto rule of gecco_knn_f32 (without ws: direct).
+ * The same bits run to run, in any batch position and in both forms; no atomics, no thread waits on another.
+ * ws: gecco_feature_nn_workspace_bytes(B, M, N) = GECCO_FEATURE_NN_WORKSPACE_BYTES(B, M, N) = 8 B M ceil(N / GECCO_KNN_SPLIT_SLICE)
+ * bytes, 8-byte aligned, for the split form; never read before it is written.  Negative return (and gecco_last_error) before anything
+ * is enqueued for: a null a / b / idx, B, M or N < 1, C outside 1 .. GECCO_FEATURE_MAX_DIM, an unknown form, the split form without
+ * ws, a grid above 2^31 - 1 workgroups.  gecco_feature_nn_workspace_bytes needs no GPU and returns 0 for non-positive arguments. */
+#define GECCO_FEATURE_MAX_DIM 64
+#define GECCO_FEATURE_NN_WORKSPACE_BYTES(B, M, N) \
+    ((size_t)8 * (size_t)(B) * (size_t)(M) * (((size_t)(N) + GECCO_KNN_SPLIT_SLICE - 1) / GECCO_KNN_SPLIT_SLICE))
+int gecco_feature_nn_f32(const float* a, const float* b, int32_t* idx, float* d2, void* ws, int B, int M, int N, int C, int form,
+                         void* stream);
+size_t gecco_feature_nn_workspace_bytes(int B, int M, int N);
 /* Voxel-grid downsampling of 3-D clouds (csrc/voxel.hip): one output point per occupied cell of a regular grid of edge voxel_size, at
  * the centroid of the points of points (B, N, 3) that fall in the cell, with the point-to-voxel map.  What PCL and Open3D put before
  * the neighbour search; O(N) and a fixed number of launches whatever the output size.  The reference has nothing of the kind (its

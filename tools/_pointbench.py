@@ -1,5 +1,5 @@
-"""What tools/bench_{fps,knn,normals,voxel,icp}.py share: the HIP-event timer, the checks before a measurement, the raw-call plumbing, and
-the harness of the four that run one child process per shape under a time limit and stop at the first failure."""
+"""What tools/bench_{fps,knn,normals,voxel,icp,fpfh}.py share: the HIP-event timer, the checks before a measurement, the raw-call plumbing, and
+the harness of those that run one child process per shape under a time limit and stop at the first failure."""
 import argparse
 import ctypes as C
 import json
