@@ -77,7 +77,7 @@ class GeccoAdamEma(C.Structure):
                 ("ema_decay", C.c_double), ("grad_scale", C.c_float), ("step", C.c_int), ("do_ema", C.c_int)]
 
 
-i, sz, vp, fl, db = C.c_int, C.c_size_t, C.c_void_p, C.c_float, C.c_double
+i, sz, vp, fl, db, u64 = C.c_int, C.c_size_t, C.c_void_p, C.c_float, C.c_double, C.c_uint64
 PP = C.POINTER(C.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/gecco_hip.h declares
@@ -237,6 +237,8 @@ SIGNATURES = {
     "gecco_fpfh_f32": (i, [vp, vp, vp, fl, vp, vp, vp, i, i, i, vp]),
     "gecco_feature_nn_f32": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
     "gecco_feature_nn_workspace_bytes": (sz, [i, i, i]),
+    "gecco_ransac_f32": (i, [vp, vp, vp, fl, db, i, i, u64] + [vp] * 12 + [i, i, i, vp]),
+    "gecco_ransac_workspace_bytes": (sz, [i, i, i]),
     "gecco_voxel_downsample_f32": (i, [vp, vp, fl, vp, vp, vp, vp, vp, vp, i, i, i, vp]),
     "gecco_voxel_workspace_bytes": (sz, [i, i]),
     "gecco_convnext_stem_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),

@@ -1,5 +1,5 @@
 // C ABI of libgecco_hip.so, part 4 of 4: point-cloud operators and metrics (distance matrix, Chamfer, set metrics, EMD,
-// Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, voxel grid).
+// Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, RANSAC registration, voxel grid).
 #include "api_common.h"
 
 using namespace gecco_api;
@@ -264,6 +264,34 @@ int gecco_feature_nn_f32(const float* a, const float* b, int32_t* idx, float* d2
     const int rc = feature_nn_launch(a, b, idx, d2, ws, B, M, N, C, form, (hipStream_t)stream);
     if (rc == -3) return fail(-2, "feature_nn: the grid for B = %d, M = %d, N = %d passes 2^31 - 1 workgroups", B, M, N);
     TRY(rc, "feature_nn");
+    return 0;
+}
+
+// RANSAC registration from correspondences (ransac.hip).  inliers, hyp_triple, hyp_count, hyp_sum, candidates nullable
+size_t gecco_ransac_workspace_bytes(int B, int M, int hypotheses) {
+    if (B < 1 || M < 1 || hypotheses < 1 || hypotheses > GECCO_RANSAC_MAX_HYPOTHESES) return 0;
+    return GECCO_RANSAC_WORKSPACE_BYTES(B, M, hypotheses);
+}
+int gecco_ransac_f32(const float* source, const float* target, const int32_t* corr, float r, double edge_similarity, int hypotheses,
+                     int refine_passes, uint64_t seed, double* transformation, float* fitness, float* inlier_rmse, int32_t* n_pairs,
+                     int32_t* best, int32_t* status, int32_t* inliers, int32_t* hyp_triple, int32_t* hyp_count, double* hyp_sum,
+                     const double* candidates, void* ws, int B, int M, int N, void* stream) {
+    if (!source || !target || !corr || !transformation || !fitness || !inlier_rmse || !n_pairs || !best || !status || !ws)
+        return fail(-1, "ransac: null argument");
+    if (B < 1 || M < 1 || N < 1) return fail(-2, "ransac: B = %d, M = %d, N = %d must all be >= 1", B, M, N);
+    if (hypotheses < 1 || hypotheses > GECCO_RANSAC_MAX_HYPOTHESES)
+        return fail(-2, "ransac: hypotheses = %d is not in 1 .. %d", hypotheses, GECCO_RANSAC_MAX_HYPOTHESES);
+    if (refine_passes < 0 || refine_passes > GECCO_RANSAC_MAX_REFINE)
+        return fail(-2, "ransac: refine_passes = %d is not in 0 .. %d", refine_passes, GECCO_RANSAC_MAX_REFINE);
+    if (!(r > 0.f) || !(r <= 3.402823466e38f)) return fail(-2, "ransac: r = %g must be a finite number > 0", (double)r);
+    if (!(edge_similarity >= 0.0) || !(edge_similarity <= 1.0))
+        return fail(-2, "ransac: edge_similarity = %g is not in 0 .. 1", edge_similarity);
+    const float r2 = (float)((double)r * (double)r);
+    const int rc = ransac_launch(source, target, corr, r2, edge_similarity * edge_similarity, hypotheses, refine_passes,
+                                 (unsigned long long)seed, transformation, fitness, inlier_rmse, n_pairs, best, status, inliers, hyp_triple,
+                                 hyp_count, hyp_sum, candidates, ws, B, M, N, (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "ransac: the grid for B = %d, hypotheses = %d passes 2^31 - 1 workgroups", B, hypotheses);
+    TRY(rc, "ransac");
     return 0;
 }
 

@@ -506,6 +506,13 @@ int fpfh_launch(const float* points, const float* normals, const int* idx, float
 // fpfh.hip — nearest neighbour in feature space (definition: gecco_feature_nn_f32).  form as knn_launch; ws of
 // GECCO_FEATURE_NN_WORKSPACE_BYTES(B, M, N) for the split form; d2 nullable.  -2: arguments out of range, -3: as above
 int feature_nn_launch(const float* a, const float* b, int* idx, float* d2, void* ws, int B, int M, int N, int C, int form, hipStream_t st);
+// ransac.hip — RANSAC registration from correspondences (definition: gecco_ransac_f32): three launches.  s2 = edge_similarity^2; inliers,
+// hyp_triple, hyp_count, hyp_sum, candidates nullable; ws of GECCO_RANSAC_WORKSPACE_BYTES(B, M, H).  -2: arguments out of range, -3: a
+// grid would pass 2^31 - 1 workgroups
+int ransac_launch(const float* source, const float* target, const int* corr, float r2, double s2, int H, int refine_passes,
+                  unsigned long long seed, double* transformation, float* fitness, float* inlier_rmse, int* n_pairs, int* best, int* status,
+                  int* inliers, int* hyp_triple, int* hyp_count, double* hyp_sum, const double* candidates, void* ws, int B, int M, int N,
+                  hipStream_t st);
 // voxel.hip — voxel-grid downsampling (definition: gecco_voxel_downsample_f32).  origin, first, count, inverse nullable; ws of
 // GECCO_VOXEL_WORKSPACE_BYTES(B, N); V = max_voxels rows per cloud.  -2: sizes out of range, -3: a grid would pass 2^31 - 1 workgroups
 int voxel_launch(const float* points, const float* origin, float voxel_size, float* centroids, int* first, int* count, int* inverse,

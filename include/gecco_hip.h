@@ -1101,6 +1101,72 @@ int gecco_fpfh_f32(const float* points, const float* normals, const int32_t* idx
 int gecco_feature_nn_f32(const float* a, const float* b, int32_t* idx, float* d2, void* ws, int B, int M, int N, int C, int form,
                          void* stream);
 size_t gecco_feature_nn_workspace_bytes(int B, int M, int N);
+/* Global registration by RANSAC on correspondences (csrc/ransac.hip): the pose that gecco_icp_f32 needs as `init`, from the pairs
+ * gecco_feature_nn_f32 finds.  It is Open3D's registration_ransac_based_on_correspondence (the core of
+ * registration_ransac_based_on_feature_matching) with a fixed number of hypotheses.  The reference has nothing of the kind; without this
+ * entry the route is a host loop of randint triples, a batched SVD and an (H, K, 3) tensor per chunk.  tests/_ransac_ref.py restates the
+ * definition in numpy.  source (B, M, 3), target (B, N, 3) fp32; corr (B, M) int32, corr[i] the target index matched to source point
+ * i or -1 (what the matching returns, mutual or not).  Each cloud is independent and one seed serves every cloud, so a cloud's result
+ * does not depend on its batch position.  r2 = fp32(r * r) with the product taken in double, as in gecco_icp_f32.
+ *     pairs      the source indices i in ascending order with 0 <= corr[i] < N (an index outside is never dereferenced) and all six
+ *                coordinates of p_i and q_corr[i] finite.  K = their number (n_pairs); P_a, Q_a the a-th pair; c = double(Q_0)
+ *     draw       for h = 0 .. H - 1, all mod 2^64:
+ *                  mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *                  u_t = mix(seed + (3 h + t + 1) * 0x9E3779B97F4A7C15), t = 0, 1, 2;   draw_t = ((u_t >> 32) * (K - t)) >> 32
+ *                  a0 = draw_0;  a1 = draw_1 + (draw_1 >= a0);  lo = min(a0, a1), hi = max(a0, a1)
+ *                  a2 = draw_2;  a2 += (a2 >= lo);  a2 += (a2 >= hi)
+ *                three distinct indices in [0, K) without a rejection loop
+ *     checks     in this order, in fp64 on the fp32 coordinates, every operation rounded and none contracted into an FMA;
+ *                |d|^2 = (dx dx + dy dy) + dz dz; no division and no root
+ *                  1  degenerate triangle, for X = P and then X = Q: e1 = X_a1 - X_a0, e2 = X_a2 - X_a0, n = e1 x e2 (each component
+ *                     a difference of two rounded products); rejected when |n|^2 <= 2^-20 (|e1|^2 |e2|^2); this also catches
+ *                     coincident points.  Code 1
+ *                  2  edge length (Open3D's CorrespondenceCheckerBasedOnEdgeLength): s2 = edge_similarity^2 in double; every edge
+ *                     (a0, a1), (a1, a2), (a2, a0) needs |P_a - P_b|^2 >= s2 |Q_a - Q_b|^2 and |Q_a - Q_b|^2 >= s2 |P_a - P_b|^2;
+ *                     edge_similarity = 0 switches it off.  Code 2
+ *                  3  fit: Horn's quaternion on the three pairs from the fp64 moments about double(Q_a0) summed in the order a0, a1,
+ *                     a2, by the routine of gecco_icp_f32's step 5 (csrc/rigid_fit.h).  A non-finite T: code 4
+ *                  4  distance (Open3D's CorrespondenceCheckerBasedOnDistance): under Tf = fp32(T), with gecco_icp_f32's transform
+ *                     spelling and gecco_knn_f32's dist2 spelling (p' - q), each of the three pairs needs d2 <= r2.  Code 3
+ *                  5  score over all K pairs in pair order: count = the number with d2 <= r2, sum = the fp64 sum of double(d2) over
+ *                     those, accumulated SEQUENTIALLY in pair order (so that it can be restated bit for bit given T)
+ *                hyp_triple (B, H, 3): the drawn triple;  hyp_count (B, H): count, or -code for a rejected hypothesis;  hyp_sum
+ *                (B, H): sum, or +inf for a rejected hypothesis.  K < 3: every hypothesis has triple -1, count -1, sum +inf
+ *     candidates (B, H, 16) fp64 or NULL.  Given, T = candidates[b, h] replaces the draw and checks 1 - 3 and check 4 is skipped; a
+ *                non-finite entry gets code 4; hyp_triple is -1.  It scores poses of the caller's own (symmetric alternatives)
+ *     select     the winner is the surviving hypothesis with count >= 3 that is best under (count descending, then sum ascending,
+ *                then h ascending): a total order, so the shape of the reduction cannot change it.  best = its h, or -1
+ *     refine     refine_passes times, 0 <= refine_passes <= GECCO_RANSAC_MAX_REFINE: the inliers (d2 <= r2) of the current T among the
+ *                K pairs, their fp64 moments about c reduced in a fixed order as in gecco_icp_f32, Horn, T <- dT * double(Tf).  A
+ *                pass with fewer than 3 inliers or a non-finite dT leaves T unchanged and ends the refinement.  The refit is ALWAYS
+ *                accepted: it is a least-squares polish on the consensus set, not a second search (Open3D leaves refinement to ICP);
+ *                a rule "keep only if the count does not fall" would discard the better pose when one borderline pair drops out
+ * Outputs, every element written: transformation (B, 16) fp64, the identity when there is no winner; fitness (B) fp32 = n / K with n
+ * the number of inliers under the final T (Open3D divides by the number of correspondences), 0 without a winner; inlier_rmse (B) fp32
+ * = sqrt(sum / n), 0 when n = 0; n_pairs (B) = K; best (B); status (B): 0 found, 1 no surviving hypothesis with count >= 3, 2 K < 3;
+ * inliers (B, M) int32 or NULL: corr[i] for the pairs that are inliers under the final T, -1 elsewhere.  hyp_triple, hyp_count,
+ * hyp_sum: NULL or as above.
+ * Three launches whatever the data: a compaction of the pairs (one workgroup per cloud, an ordered scan, each pair as two 16-byte
+ * entries (P, i), (Q, j)); the hypothesis kernel (a workgroup of 256 threads per 1024 consecutive hypotheses of a cloud: draw and
+ * checks 1 - 2 for four hypotheses per thread, the survivors compacted in h order in LDS, then one thread per survivor fits and
+ * scores against the pairs streamed through LDS tiles; 16 bytes of result per hypothesis); select + refine (one workgroup per cloud).
+ * No atomics, no workgroup waits on another, no allocation and no host synchronisation: the call can be captured in a graph.  The
+ * outputs are the same bits run to run, in any batch position and however H is split across workgroups.
+ * ws: gecco_ransac_workspace_bytes(B, M, hypotheses) = GECCO_RANSAC_WORKSPACE_BYTES(B, M, H) bytes, 16-byte aligned; required; never
+ * read before it is written.  Negative return (and gecco_last_error) before anything is enqueued for: a null source / target / corr /
+ * required output / ws, non-positive sizes, hypotheses outside 1 .. GECCO_RANSAC_MAX_HYPOTHESES, r not a finite number > 0,
+ * edge_similarity outside [0, 1] or NaN, refine_passes out of range, a grid above 2^31 - 1 workgroups.  gecco_ransac_workspace_bytes
+ * needs no GPU and returns 0 for arguments out of range. */
+#define GECCO_RANSAC_MAX_HYPOTHESES (1 << 24)
+#define GECCO_RANSAC_MAX_REFINE 8
+#define GECCO_RANSAC_BLOCK_HYPOTHESES 1024
+#define GECCO_RANSAC_WORKSPACE_BYTES(B, M, H) \
+    ((size_t)16 * (size_t)(B) * (size_t)(H) + (size_t)32 * (size_t)(B) * (size_t)(M) + (size_t)16 * (size_t)(B))
+int gecco_ransac_f32(const float* source, const float* target, const int32_t* corr, float r, double edge_similarity, int hypotheses,
+                     int refine_passes, uint64_t seed, double* transformation, float* fitness, float* inlier_rmse, int32_t* n_pairs,
+                     int32_t* best, int32_t* status, int32_t* inliers, int32_t* hyp_triple, int32_t* hyp_count, double* hyp_sum,
+                     const double* candidates, void* ws, int B, int M, int N, void* stream);
+size_t gecco_ransac_workspace_bytes(int B, int M, int hypotheses);
 /* Voxel-grid downsampling of 3-D clouds (csrc/voxel.hip): one output point per occupied cell of a regular grid of edge voxel_size, at
  * the centroid of the points of points (B, N, 3) that fall in the cell, with the point-to-voxel map.  What PCL and Open3D put before
  * the neighbour search; O(N) and a fixed number of launches whatever the output size.  The reference has nothing of the kind (its

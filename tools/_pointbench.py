@@ -1,4 +1,4 @@
-"""What tools/bench_{fps,knn,normals,voxel,icp,fpfh}.py share: the HIP-event timer, the checks before a measurement, the raw-call plumbing, and
+"""What tools/bench_{fps,knn,normals,voxel,icp,fpfh,ransac}.py share: the HIP-event timer, the checks before a measurement, the raw-call plumbing, and
 the harness of those that run one child process per shape under a time limit and stop at the first failure."""
 import argparse
 import ctypes as C
