@@ -143,6 +143,9 @@ SIGNATURES = {
     "gecco_affine_cast_f16": (i, [vp, vp, vp, vp, i, i, i, vp]),
     "gecco_pool_attn_f16in": (i, [vp, vp, vp, i, i, i, i, i, i, vp, sz, vp]),
     "gecco_unpool_attn_f16io": (i, [vp, vp, vp, i, i, i, i, i, i, vp]),
+    "gecco_lift0_fold_f32": (i, [vp] * 8 + [i, i, i, vp]),
+    "gecco_lift0_rows": (i, [vp, vp, vp, vp, i, i, i, i, i, i, i, vp]),
+    "gecco_lift0_pool_f32": (i, [vp] * 5 + [i, i, i, i, vp, sz, vp]),
     "gecco_col_stats_f32": (i, [vp, vp, i, i, i, vp]),
     "gecco_stats_row_tiles": (i, [i]),
     "gecco_adagn_coeffs_f32": (i, [vp, i, i, vp, i, C.POINTER(GeccoAdaGN), vp, vp, i, i, i, fl, vp]),

@@ -52,6 +52,38 @@ int gecco_pool_attn_f16in(const void* KV16, const float* inducers, float* merged
     return 0;
 }
 
+int gecco_lift0_fold_f32(const float* kv_w, const float* q_w, const float* q_b, const float* lift_w, const float* lift_b, const float* a1,
+                         const float* o1, float* mc, int B, int C, int H, void* stream) {
+    if (!kv_w || !q_w || !lift_w || !a1 || !o1 || !mc) return fail(-1, "lift0_fold: null argument");
+    if (!lift0_supported(C, H)) return fail(-2, "lift0_fold: feature_dim must be a multiple of 8 and of the head count, at most 1024");
+    TRY(lift0_fold_launch(kv_w, q_w, q_b, lift_w, lift_b, a1, o1, mc, 0, 3 * C, B, C, (hipStream_t)stream), "lift0_fold");
+    return 0;
+}
+
+int gecco_lift0_rows(const float* x, const float* coef, const float* mc, void* out, int col0, int ncols, int head_dim, int out_f16,
+                     int B, int N, int C, void* stream) {
+    if (!x || !coef || !mc || !out) return fail(-1, "lift0_rows: null argument");
+    if (ncols <= 0 || ncols % 8 || col0 < 0 || col0 + ncols > 3 * C) return fail(-2, "lift0_rows: columns must be a multiple of 8 inside 0 .. 3 * feature_dim");
+    if (head_dim && (!lift0_head_major_ok(head_dim) || ncols % head_dim)) return fail(-2, "lift0_rows: head dim %d has no head-major form", head_dim);
+    const Lift0Seg seg{out, col0, ncols, head_dim};
+    TRY(lift0_rows_launch(x, coef, mc, &seg, 1, out_f16 != 0, B, N, C, (hipStream_t)stream), "lift0_rows");
+    return 0;
+}
+
+int gecco_lift0_pool_f32(const float* x, const float* coef, const float* mc, const float* inducers, float* merged, int B, int N, int C,
+                         int H, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !coef || !mc || !inducers || !merged || !ws) return fail(-1, "lift0_pool: null argument");
+    if (!lift0_pool_supported(C, H)) return fail(-2, "lift0_pool: feature_dim must be a multiple of 8, at most 1024, the head dim a multiple of 4");
+    if (ws_bytes < gecco_pool_attn_workspace_bytes(B, N, C, H, 64)) return fail(-7, "lift0_pool: workspace too small");
+    Carver c(ws);
+    const int ns = pool_attn_nsplit(B, N, H);
+    float* po = c.f32((size_t)B * H * ns * 64 * (C / H));
+    float* pml = c.f32((size_t)B * H * ns * 64 * 2);
+    TRY(lift0_pool_launch(x, coef, mc, inducers, po, pml, B, N, C, H, ns, (hipStream_t)stream), "lift0_pool");
+    TRY(pool_merge_launch(po, pml, merged, B, C, H, ns, (hipStream_t)stream), "lift0_pool merge");
+    return 0;
+}
+
 int gecco_unpool_attn_f16io(const void* q16, const float* kvh, void* out16, int B, int N, int C, int H, int I,
                             int head_major, void* stream) {
     int rc = unpool_attn_launch(static_cast<const float*>(q16), kvh, static_cast<float*>(out16), B, N, C, H, I,

@@ -14,11 +14,11 @@ using namespace gecco_api;
 namespace {
 
 // The option table (the OPT_* indices: api_common.h)
-std::atomic<int> g_options[OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-const char* const g_option_names[OPT_COUNT] = {"astat", "chain", "headmajor", "mlpfused", "unpoolfused", "lo8", "actimg", "h8", "kvq64", "h8areg", "chain2", "unpoolh8", "mlpw", "chaincl", "h6", "kvfold", "mlpwshare", "kvqperm", "imgproj16"};
+std::atomic<int> g_options[OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+const char* const g_option_names[OPT_COUNT] = {"astat", "chain", "headmajor", "mlpfused", "unpoolfused", "lo8", "actimg", "h8", "kvq64", "h8areg", "chain2", "unpoolh8", "mlpw", "chaincl", "h6", "kvfold", "mlpwshare", "kvqperm", "imgproj16", "lift0"};
 const char* const g_option_env[OPT_COUNT] = {"GECCO_ASTAT", "GECCO_CHAIN", "GECCO_HEADMAJOR", "GECCO_MLPFUSED", "GECCO_UNPOOLFUSED", "GECCO_LO8",
                                              "GECCO_ACTIMG", "GECCO_H8", "GECCO_KVQ64", "GECCO_H8AREG", "GECCO_CHAIN2", "GECCO_UNPOOLH8", "GECCO_MLPW", "GECCO_CHAINCL", "GECCO_H6", "GECCO_KVFOLD", "GECCO_MLPWSHARE",
-                                             "GECCO_KVQPERM", "GECCO_IMGPROJ16"};
+                                             "GECCO_KVQPERM", "GECCO_IMGPROJ16", "GECCO_LIFT0"};
 // A plan's own switches (GeccoSetTransformer.opt_mask / opt_vals: gecco_option_index(name) is the bit) win over the process-wide ones
 // while that plan's forward runs on this thread: two plans, or two host threads, never see each other's settings.
 thread_local const GeccoSetTransformer* t_plan = nullptr;
@@ -43,14 +43,20 @@ int fail(int rc, const char* fmt, ...) {
 }
 
 int option(int which) {
-    if (t_plan && ((t_plan->opt_mask >> which) & 1u)) return (int)((t_plan->opt_vals >> which) & 1u);
+    if (t_plan && ((t_plan->opt_mask >> which) & 1u)) {
+        const int v = (int)((t_plan->opt_vals >> which) & 1u);
+        return which == OPT_LIFT0 && v ? v + (int)((t_plan->opt_vals >> OPT_LIFT0_HI) & 1u) : v;
+    }
     int v = g_options[which].load(std::memory_order_relaxed);
     if (v < 0) {
         const char* e = getenv(g_option_env[which]);
         // "mlpwshare" (the one-launch MLP leaves CUs to a second stream's kernels) is off unless the caller runs two streams: hip_ops.py
         // sets it around a two-stream evaluation
         // "imgproj16" (img_feature_proj on one-term fp16 operands) is opt-in: 2 % of a C3 evaluation for a fifth of the w2 mode's error budget
-        const int fill = e ? (atoi(e) != 0) : (which != OPT_MLPWSHARE && which != OPT_IMGPROJ16);
+        // "lift0" (layer 0 of a LinearLift evaluation from the 3-D points) has levels: 1 the projection, 2 the pool attention too; unset, it is 3:
+        // level 2 at the widths where st_route finds it faster, 0 below them
+        const int fill = which == OPT_LIFT0 ? (e ? (atoi(e) < 0 ? 0 : atoi(e) > 2 ? 2 : atoi(e)) : 3)
+                         : e ? (atoi(e) != 0) : (which != OPT_MLPWSHARE && which != OPT_IMGPROJ16);
         // concurrent first reads fill in the same value; a gecco_set_option that got in between wins (v then holds its value)
         if (g_options[which].compare_exchange_strong(v, fill, std::memory_order_relaxed)) v = fill;
     }
@@ -124,8 +130,12 @@ struct STWorkspace {
     size_t o_pout, o_b0, o_b2, o_ukv, b2_half;   // the 64-inducer chain: pool.out_proj, broadcast mlp, unpool k|v; its one-launch forms walk mlp.2 K-half by K-half
     size_t o_mf, mf_chunk, mf_w2, mf_half;       // fused point MLP: W0 tile j | W2 K-slice j (two halves), j = 0 .. width/128 (fp16 mode: floats per j, W2's place, one half)
     size_t o_q16, o_kv_lo, o_q64;                // mixed mode: fp16 hi images of kv_proj | q_proj back to back, then kv_proj's lo image; the kvq stream's q tiles
+    float* mc;                         // option "lift0": layer 0's folded (M_b | c_b), (B, 3C, 4)
     size_t bytes;
 };
+
+// What layer 0 of a LinearLift evaluation is an affine function of (option "lift0"): the points, the EDM coefficients (c_in) and the lift
+struct Lift0In { const float *x, *coef, *lift_w, *lift_b; };
 
 int max_i(int a, int b) { return a > b ? a : b; }
 
@@ -179,6 +189,7 @@ STWorkspace carve_st(const GeccoSetTransformer* st, int B, int N, void* base) {
         w.o_q16 = (2 * C + 127) / 128 * 128 * C / 2; w.o_kv_lo = w.o_q16 + (C + 127) / 128 * 128 * C / 2;
         w.o_q64 = kvq_image_bytes(2 * (int)C, (int)C, (int)C) / sizeof(float);
     }
+    w.mc = c.f32((size_t)B * 3 * C * 4);   // (last: every other place is where it was)
     w.bytes = (c.off + 255) & ~size_t(255);
     return w;
 }
@@ -304,9 +315,14 @@ struct StRoute {
     // option "kvfold": the chain's last epilogue writes the fused unpool kernel's k | v image itself.  Only when EVERY layer runs the chain (no cached inducer states: their
     // layers bring the fp16 cast of x into the same buffer) — the image's pad positions are zeroed once per forward, and nothing else touches the buffer in between
     bool kvfold;
+    // option "lift0", a LinearLift evaluation (the caller hands the points over): layer 0's K | V | q are M_b (c_in p_n) + c_b (lift0.hip).  1: K | V and q are written
+    // from the points instead of by the (B N) x C -> 3C product; 2: q only, and the pool attention runs on the points — K | V of layer 0 never exist.  Any arithmetic
+    // mode, any N; the tensors keep the element type (io16) and layout (lift0_hm: head-major) their consumers read
+    int lift0;
+    bool lift0_hm;
 };
 
-StRoute st_route(const GeccoSetTransformer* st, int B, int N, const float* const* h_in) {
+StRoute st_route(const GeccoSetTransformer* st, int B, int N, const float* const* h_in, bool points) {
     StRoute r{};
     const int C = st->C, I = st->I, H = st->H, G = st->G, Wd = st->width, act = st->act;
     const int prec = st->precision == 4 ? 3 : st->precision;   // 4 ("w2"): the mixed mode with the point MLP as one launch
@@ -368,6 +384,13 @@ StRoute st_route(const GeccoSetTransformer* st, int B, int N, const float* const
     r.kvfold = r.uo8_on && r.chain && option(OPT_KVFOLD);
     for (int li = 0; r.kvfold && li < st->n_layers; ++li)
         if (h_in && h_in[li]) r.kvfold = false;
+    r.lift0 = points && lift0_supported(C, H) ? option(OPT_LIFT0) : 0;
+    // unset: where it pays.  The kernels that replace the product cost about the same at every width (the pool on the points does not depend on it), the product
+    // itself goes with C^2: B = 64, N = 2048, w2: C = 384 4.43 -> 4.33 ms per evaluation, C = 128 0.77 -> 0.80 ms (profiles/lift0_ab.txt)
+    if (r.lift0 == 3) r.lift0 = C >= 256 ? 2 : 0;
+    if (r.lift0 == 2 && !lift0_pool_supported(C, H)) r.lift0 = 1;
+    r.lift0_hm = r.lift0 && r.io16 && r.astat && r.hd_try && lift0_head_major_ok(C / H);
+    if (r.lift0 && r.uo8_on && !r.lift0_hm) r.lift0 = 0;   // (the fused unpool reads head-major q: every shape it takes has it)
     return r;
 }
 
@@ -405,15 +428,17 @@ int build_weight_images(const StRoute& r, const GeccoSetTransformer* st, const S
         float* base = w.wimg + (size_t)li * w.wimg_layer;
         const bool cached = h_in && h_in[li];   // the layer's inducer states come from the caller: only q, out_proj and the point MLP run
         const bool own_kvq = r.mixed || r.kvq16_on;   // kv_proj | q_proj in an A-stationary kernel's own format
+        const bool pts = li == 0 && r.lift0;          // layer 0's K | V | q come from the points: no stream of kv_proj / q_proj
+        const bool kv_img = !cached && !pts, q_img = !pts;
         if (r.kvq_on) {
             // the kvq stream: K | V tiles (the V half with L stages), then the q tiles
-            if (!cached) TRY(jobs8.push(L.kv_proj_w, base, 2 * C, C, C, 1 | r.kvq_p48 | ((C / 64) << 8) | ((2 * C / 64) << 20)), "split(kv_proj, kvq)");
-            TRY(jobs8.push(L.in_proj_w, base + w.o_q64, C, C, C, 1 | r.kvq_p48), "split(q_proj, kvq)");
+            if (kv_img) TRY(jobs8.push(L.kv_proj_w, base, 2 * C, C, C, 1 | r.kvq_p48 | ((C / 64) << 8) | ((2 * C / 64) << 20)), "split(kv_proj, kvq)");
+            if (q_img) TRY(jobs8.push(L.in_proj_w, base + w.o_q64, C, C, C, 1 | r.kvq_p48), "split(q_proj, kvq)");
         } else if (r.mixed) {
             // fp16 hi images of kv_proj | q_proj back to back (one stream for the A-stationary kernel), then kv_proj's lo image
-            if (!cached) TRY(jobs16.push(L.kv_proj_w, base, 2 * C, C, C, 0), "split(weights)");
-            TRY(jobs16.push(L.in_proj_w, base + w.o_q16, C, C, C, 0), "split(weights)");   // q_proj is one-term: no lo image
-            if (!cached) TRY(jobs16.push(L.kv_proj_w, base + w.o_kv_lo, 2 * C, C, C, r.lo8 ? 2 : 1), "split(weights)");
+            if (kv_img) TRY(jobs16.push(L.kv_proj_w, base, 2 * C, C, C, 0), "split(weights)");
+            if (q_img) TRY(jobs16.push(L.in_proj_w, base + w.o_q16, C, C, C, 0), "split(weights)");   // q_proj is one-term: no lo image
+            if (kv_img) TRY(jobs16.push(L.kv_proj_w, base + w.o_kv_lo, 2 * C, C, C, r.lo8 ? 2 : 1), "split(weights)");
         }
         const bool chain2_here = r.chain2_on && !cached;
         if (chain2_here) {
@@ -426,11 +451,11 @@ int build_weight_images(const StRoute& r, const GeccoSetTransformer* st, const S
             TRY(jobs16.push(L.in_proj_w + (size_t)C * C, base + w.o_ukv, 2 * C, C, C, 8), "split(unpool.in_proj kv, two-term)");
         }
         if (r.kvq16_on) {   // one-term kvq stream: K | V tiles, then the q tiles (o_q = the end of the kv image: 2 bytes per weight)
-            if (!cached) TRY(jobs8.push(L.kv_proj_w, base, 2 * C, C, C, 1), "split(kv_proj, kvq)");
-            TRY(jobs8.push(L.in_proj_w, base + w.o_q, C, C, C, 1), "split(q_proj, kvq)");
+            if (kv_img) TRY(jobs8.push(L.kv_proj_w, base, 2 * C, C, C, 1), "split(kv_proj, kvq)");
+            if (q_img) TRY(jobs8.push(L.in_proj_w, base + w.o_q, C, C, C, 1), "split(q_proj, kvq)");
         }
         if (!cached && !chain2_here) {
-            if (!own_kvq) TRY(jobs.push(L.kv_proj_w, base, 2 * C, C, C, 0), "split(kv_proj)");
+            if (!own_kvq && kv_img) TRY(jobs.push(L.kv_proj_w, base, 2 * C, C, C, 0), "split(kv_proj)");
             TRY(jobs.push(L.pool_out_w, base + w.o_pout, C, C, C, 0), "split(pool.out_proj)");
             TRY(jobs.push(L.bmlp.w0, base + w.o_b0, Wd, C, C, 0), "split(broadcast.mlp.0)");
             if (r.chain_on) {   // the one-launch chain walks mlp.2 K-half by K-half: one (C x C) image per half
@@ -441,7 +466,7 @@ int build_weight_images(const StRoute& r, const GeccoSetTransformer* st, const S
             }
         }
         if (!chain2_here) TRY(jobs.push(L.in_proj_w + (size_t)C * C, base + w.o_ukv, 2 * C, C, C, 0), "split(unpool.in_proj kv)");
-        if (!own_kvq) TRY(jobs.push(L.in_proj_w, base + w.o_q, C, C, C, 0), "split(q_proj)");
+        if (!own_kvq && q_img) TRY(jobs.push(L.in_proj_w, base + w.o_q, C, C, C, 0), "split(q_proj)");
         if (r.h8o) TRY(jobs8.push(L.unpool_out_w, base + w.o_out, C, C, C, r.uo8_on ? 16 : 2), "split(out_proj, h8)");   // 16: 64-column tiles, attention k order
         else TRY(jobs.push(L.unpool_out_w, base + w.o_out, C, C, C, 0), "split(out_proj)");
         if (r.mlpf_on) {   // one stream in consumption order: per hidden chunk j, W0 tile j, then W2[:, chunk j] in two K-halves
@@ -477,6 +502,7 @@ struct StLayer {
     float *hdst, *so;  // where this layer's own inducer states go; where the point MLP leaves the statistics of its output
     bool cached, q_done = false, kvh_done = false, kv_img_done = false;
     int hm = 0;        // K | V and q of this layer are head-major
+    const Lift0In* pts = nullptr;   // layer 0 on the route's "lift0" path: its K | V | q come from these
     const float* img(size_t off) const { return im ? im + off : nullptr; }
 };
 
@@ -513,12 +539,31 @@ int project_stage(StLayer& c, bool with_kv) {
     return 0;
 }
 
+// Layer 0 on the "lift0" path: the fold of (a1, o1) and the lift into kv_proj | q_proj, then K | V | q (level 1), or q alone (level 2, and over cached inducer
+// states), written from the points in the element type and layout project_stage leaves them in
+int project_from_points(StLayer& c, bool with_kv) {
+    const StRoute& r = c.r; const STWorkspace& w = c.w; const GeccoLayer& L = c.L;
+    const int C = c.st->C, H = c.st->H, B = c.B, N = c.N;
+    TRY(lift0_fold_launch(L.kv_proj_w, L.in_proj_w, L.in_proj_b, c.pts->lift_w, c.pts->lift_b, w.a1, w.o1, w.mc, with_kv ? 0 : 2 * C, 3 * C, B, C, c.s), "lift0 fold");
+    const int hd = r.lift0_hm ? C / H : 0;
+    const Lift0Seg segs[2] = {{w.q, 2 * C, C, hd}, {w.big, 0, 2 * C, hd}};
+    TRY(lift0_rows_launch(c.pts->x, c.pts->coef, w.mc, segs, with_kv && r.lift0 == 1 ? 2 : 1, r.io16, B, N, C, c.s), "lift0 rows");
+    c.hm = hd != 0;
+    c.q_done = true;
+    return 0;
+}
+
 // pool: the 64 inducer queries over the N points, then everything on the inducers up to the unpool's k | v — the one-launch chain, or
 // out_proj, h = norm_2(mlp(norm_1(h0))) as five launches (the unpool stage then projects k | v)
 int inducer_stage(StLayer& c) {
     const StRoute& r = c.r; const STWorkspace& w = c.w; const GeccoLayer& L = c.L; const GeccoSetTransformer* st = c.st; hipStream_t s = c.s;
     const int C = st->C, I = st->I, H = st->H, G = st->G, Wd = st->width, ctx = st->ctx_dim, act = st->act, B = c.B, pr = r.pr;
-    TRY(pool_attn_launch(w.big, L.inducers, w.part_o, w.part_ml, r.chain ? nullptr : w.merged, B, c.N, C, H, I, r.ns, s, r.apr, r.io16, c.hm), "pool_attn");
+    if (c.pts && r.lift0 == 2) {   // the pool on the points: the same partials, K | V (w.big) neither written nor read
+        TRY(lift0_pool_launch(c.pts->x, c.pts->coef, w.mc, L.inducers, w.part_o, w.part_ml, B, c.N, C, H, r.ns, s), "pool_attn (points)");
+        if (!r.chain) TRY(pool_merge_launch(w.part_o, w.part_ml, w.merged, B, C, H, r.ns, s), "pool_attn merge");
+    } else {
+        TRY(pool_attn_launch(w.big, L.inducers, w.part_o, w.part_ml, r.chain ? nullptr : w.merged, B, c.N, C, H, I, r.ns, s, r.apr, r.io16, c.hm), "pool_attn");
+    }
     if (r.chain) {
         ChainArgs ca{};
         ca.part_o = w.part_o; ca.part_ml = w.part_ml; ca.nsplit = r.ns; ca.H = H;
@@ -634,7 +679,7 @@ int mlp_stage(StLayer& c) {
 
 int st_forward(const GeccoSetTransformer* st, float* x, const float* t, const float* stats_x, int stats_T,
                const float* const* h_in, float* const* h_out, float* stats_out, int B, int N, void* ws,
-               size_t ws_bytes, hipStream_t s) {
+               size_t ws_bytes, hipStream_t s, const Lift0In* pts = nullptr) {   // pts: x is lift(c_in p) of these (LinearLift)
     if (!st || !x || !t || !ws) return fail(-1, "set_transformer: null argument");
     if (st->I != 64) return fail(-3, "set_transformer: num_inducers must be 64 (got %d)", st->I);
     if (st->C % st->H || st->C % st->G || st->C % 4) return fail(-3, "set_transformer: bad feature_dim %d", st->C);
@@ -642,7 +687,7 @@ int st_forward(const GeccoSetTransformer* st, float* x, const float* t, const fl
     PlanScope plan_scope(st);
     const STWorkspace w = carve_st(st, B, N, ws);
     if (ws_bytes < w.bytes) return fail(-7, "set_transformer: workspace too small (%zu < %zu)", ws_bytes, w.bytes);
-    const StRoute r = st_route(st, B, N, h_in);
+    const StRoute r = st_route(st, B, N, h_in, pts != nullptr);
     if (r.rc) return r.rc;
     if (r.chain && !chain_stream_fits(st, w)) return fail(-3, "set_transformer: the inducer chain's weight stream does not fill its places in the workspace");
     const int C = st->C, H = st->H, G = st->G;
@@ -662,7 +707,8 @@ int st_forward(const GeccoSetTransformer* st, float* x, const float* t, const fl
         StLayer c{st, r, w, L, li, r.imgs ? w.wimg + (size_t)li * w.wimg_layer : nullptr, x, t, B, N, s, cached ? h_in[li] : nullptr,
                   (h_out && h_out[li]) ? h_out[li] : w.h, (li + 1 < st->n_layers) ? w.stats_x : stats_out, cached};
         TRY(coeffs(sx, sT, N, t, st->ctx_dim, &L.broadcast_norm, w.a1, w.o1, B, C, G, s), "adagn_coeffs(broadcast_norm)");
-        rc = cached ? 0 : project_stage(c, true);
+        if (li == 0 && r.lift0) c.pts = pts;
+        rc = c.pts ? project_from_points(c, !cached) : cached ? 0 : project_stage(c, true);
         if (!rc && !cached) rc = inducer_stage(c);
         if (!rc) rc = unpool_stage(c);
         if (!rc) rc = mlp_stage(c);
@@ -743,10 +789,10 @@ int gecco_set_option(const char* name, int value) {
     if (!name) return fail(-1, "set_option: null name");
     for (int i = 0; i < OPT_COUNT; ++i)
         if (!strcmp(name, g_option_names[i])) {
-            g_options[i].store(value < 0 ? -1 : (value != 0), std::memory_order_relaxed);   // < 0: back to the environment / default
+            g_options[i].store(value < 0 ? -1 : i == OPT_LIFT0 ? (value > 2 ? 2 : value) : (value != 0), std::memory_order_relaxed);   // < 0: back to the environment / default
             return 0;
         }
-    return fail(-2, "set_option: unknown option '%s' (astat, chain, headmajor, mlpfused, unpoolfused, lo8, actimg, h8, kvq64, h8areg, chain2, unpoolh8, mlpw, chaincl, h6, kvfold, mlpwshare, kvqperm, imgproj16)", name);
+    return fail(-2, "set_option: unknown option '%s' (astat, chain, headmajor, mlpfused, unpoolfused, lo8, actimg, h8, kvq64, h8areg, chain2, unpoolh8, mlpw, chaincl, h6, kvfold, mlpwshare, kvqperm, imgproj16, lift0)", name);
 }
 
 size_t gecco_set_transformer_workspace_bytes(const GeccoSetTransformer* st, int B, int N) {
@@ -776,8 +822,9 @@ int gecco_linear_lift_fwd_f32(const GeccoLinearLift* m, const float* x, const fl
     // AdaGN reads t as a packed (B, ctx_dim) array; under EDMPrecond ctx_dim == 1 and t = c_noise,
     // which edm_coeffs also writes packed at coef[4B .. 5B).
     if (m->inner.ctx_dim != 1) return fail(-3, "linear_lift: t_embed_dim must be 1 under EDMPrecond");
+    const Lift0In pts{x, w.coef, m->lift_w, m->lift_b};
     int rc = st_forward(&m->inner, w.feat, w.coef + 4 * (size_t)B, w.stats, row_tiles_stats(N), h_in, h_out, nullptr, B,
-                        N, w.st_ws, w.st_bytes, s);
+                        N, w.st_ws, w.st_bytes, s, &pts);
     if (rc) return rc;
     TRY(lower_edm_launch(w.feat, x, w.coef, m->lower_w, m->lower_b, nullptr, nullptr, denoised, raw, B, N, C, 1e-5f, s),
         "lower_edm");

@@ -412,7 +412,12 @@ int pool_attn_launch(const float* KV, const float* inducers, float* part_o, floa
     }
     if (rc) return rc;
     if (!merged) return 0;   // the caller merges the partials itself (inducer_chain_f16.hip)
+    return pool_merge_launch(part_o, part_ml, merged, B, C, H, nsplit, st);
+}
+
+int pool_merge_launch(const float* part_o, const float* part_ml, float* merged, int B, int C, int H, int nsplit, hipStream_t st) {
     const size_t total = (size_t)B * 64 * C;
+    if (!total) return 0;
     hipLaunchKernelGGL(pool_merge_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_o, part_ml,
                        merged, B, C, H, nsplit);
     return (int)hipGetLastError();

@@ -314,6 +314,7 @@ int pool_attn_launch(const float* KV, const float* inducers, float* part_o, floa
                      int B, int N, int C, int H, int I, int nsplit, hipStream_t st, int precision = 0, int io16 = 0,
                      int hm = 0);   // hm (with io16): K | V / q are head-major (GemmArgs::hm_hd)
 int pool_attn_nsplit(int B, int N, int H);
+int pool_merge_launch(const float* part_o, const float* part_ml, float* merged, int B, int C, int H, int nsplit, hipStream_t st);   // the partials' merge alone
 int unpool_attn_launch(const float* q, const float* kvh, float* out, int B, int N, int C, int H, int I,
                        hipStream_t st, int precision = 0, int io16 = 0, int hm = 0, int out_img = 0);   // out_img: GemmArgs::a_img layout
 // attention_bwd_f32.hip (training path)
@@ -337,6 +338,21 @@ int pool_attn_x3_partials_launch(const float* KV, const float* inducers, float* 
                                  int C, int H, int nsplit, hipStream_t st, int precision, int io16 = 0, int hm = 0);   // 1 split-bf16, 2 fp16
 int unpool_attn_x3_launch(const float* q, const float* kvh, float* out, int B, int N, int C, int H, hipStream_t st,
                           int precision, int io16 = 0, int hm = 0, int out_img = 0);   // io16: KV / q / out are fp16 tensors (fp16 mode)
+
+// lift0.hip — layer 0 of a LinearLift evaluation from the 3-D points: [K | V | q](n) = M_b (c_in p_n) + c_b
+// mc (B, 3C, 4): per sample and output row of [kv_proj (2C) | q rows of in_proj (C)] the three entries of M_b and c_b; rows row0 .. row1 - 1
+int lift0_fold_launch(const float* kv_w, const float* q_w, const float* q_b, const float* lift_w, const float* lift_b, const float* a1,
+                      const float* o1, float* mc, int row0, int row1, int B, int C, hipStream_t st);
+// columns [col0, col0 + ncols) of mc's rows as one tensor: hd > 0 head-major (B, ncols / hd, N, hd), else (B, N, ncols); ncols % 8 == 0
+struct Lift0Seg { void* out; int col0, ncols, hd; };
+int lift0_rows_launch(const float* x, const float* coef, const float* mc, const Lift0Seg* segs, int nseg, int f16, int B, int N, int C,
+                      hipStream_t st);   // 1 or 2 tensors, fp16 (f16) or fp32 elements
+// the pool attention's partials (pool_attn_launch's layout and (m, l) convention for `nsplit`) from the points and mc: K | V never exist
+int lift0_pool_launch(const float* x, const float* coef, const float* mc, const float* inducers, float* part_o, float* part_ml, int B,
+                      int N, int C, int H, int nsplit, hipStream_t st);
+bool lift0_supported(int C, int H);        // fold + rows
+bool lift0_head_major_ok(int hd);          // the rows kernel writes head-major slabs of this head dim
+bool lift0_pool_supported(int C, int H);
 
 // lookup.hip
 struct LookupArgs {

@@ -52,14 +52,17 @@ def _option_bit(name: str) -> int:
 
 
 def _pin_option(table: GeccoSetTransformer, name: str, value: int) -> None:
-    """Pin (0 / 1) or release (negative) one switch in a plan's own table (GeccoSetTransformer.opt_mask / opt_vals)."""
+    """Pin (0 / 1) or release (negative) one switch in a plan's own table (GeccoSetTransformer.opt_mask / opt_vals).  "lift0" has the
+    levels 0 / 1 / 2: "level 2" is the bit above its own (include/gecco_hip.h)."""
     bit = 1 << _option_bit(name)
+    hi = bit << 1 if name == "lift0" else 0
+    table.opt_vals &= ~(bit | hi)
     if value < 0:
         table.opt_mask &= ~bit
-        table.opt_vals &= ~bit
     else:
         table.opt_mask |= bit
-        table.opt_vals = (table.opt_vals | bit) if value else (table.opt_vals & ~bit)
+        if value:
+            table.opt_vals |= bit | (hi if value >= 2 else 0)
 
 
 def default_precision() -> str:
@@ -466,6 +469,43 @@ def pool_attn_f16in(KV16: Tensor, inducers: Tensor, H: int, head_major: bool = F
     return merged
 
 
+def lift0_fold(kv_w: Tensor, in_proj_w: Tensor, in_proj_b: Tensor | None, lift_w: Tensor, lift_b: Tensor | None, a1: Tensor, o1: Tensor,
+               H: int) -> Tensor:
+    """Layer 0 from the points (option "lift0"): (B, 3C, 4) = {M_b rows, c_b} with [K | V | q](n) = M_b (c_in p_n) + c_b, for
+    broadcast_norm = (a1, o1) (B, C) and W = [kv_proj (2C, C) | the q rows of in_proj (3C, C)]."""
+    lib = _lib.load()
+    B, Cc = a1.shape
+    mc = torch.empty(B, 3 * Cc, 4, device=a1.device, dtype=torch.float32)
+    check(lib.gecco_lift0_fold_f32(_ptr(kv_w), _ptr(in_proj_w), _ptr(in_proj_b), _ptr(lift_w), _ptr(lift_b), _ptr(a1), _ptr(o1), _ptr(mc),
+                                   B, Cc, H, _stream()), "gecco_lift0_fold_f32")
+    return mc
+
+
+def lift0_rows(x: Tensor, coef: Tensor, mc: Tensor, col0: int, ncols: int, head_dim: int = 0, f16: bool = True) -> Tensor:
+    """Columns col0 .. col0 + ncols of M_b (c_in p_n) + c_b: (B, N, ncols), or head-major (B, ncols / head_dim, N, head_dim)."""
+    lib = _lib.load()
+    B, N, _ = x.shape
+    Cc = mc.shape[1] // 3
+    shape = (B, ncols // head_dim, N, head_dim) if head_dim else (B, N, ncols)
+    out = torch.empty(*shape, device=x.device, dtype=torch.float16 if f16 else torch.float32)
+    check(lib.gecco_lift0_rows(_ptr(x), _ptr(coef), _ptr(mc), C.c_void_p(out.data_ptr()), col0, ncols, head_dim, int(f16), B, N, Cc,
+                               _stream()), "gecco_lift0_rows")
+    return out
+
+
+def lift0_pool(x: Tensor, coef: Tensor, mc: Tensor, inducers: Tensor, H: int) -> Tensor:
+    """The merged pool attention (B, 64, C) of layer 0's inducers over the points, K | V never formed."""
+    lib = _lib.load()
+    B, N, _ = x.shape
+    Cc = mc.shape[1] // 3
+    merged = torch.empty(B, 64, Cc, device=x.device, dtype=torch.float32)
+    nb = lib.gecco_pool_attn_workspace_bytes(B, N, Cc, H, 64)
+    ws = _ws(nb, x.device)
+    check(lib.gecco_lift0_pool_f32(_ptr(x), _ptr(coef), _ptr(mc), _ptr(inducers), _ptr(merged), B, N, Cc, H, C.c_void_p(ws.data_ptr()), nb,
+                                   _stream()), "gecco_lift0_pool_f32")
+    return merged
+
+
 def unpool_attn_f16io(q16: Tensor, kvh: Tensor, H: int, out: Tensor | None = None, head_major: bool = False) -> Tensor:
     """q16: (B, N, C) fp16, or head-major (B, H, N, hd); out is (B, N, C) fp16 either way."""
     lib = _lib.load()
@@ -850,7 +890,7 @@ class LinearLiftPlan:
         return tbl.base.inner if isinstance(tbl, _lib.GeccoLinearLiftG) else tbl.inner
 
     def set_option(self, name: str, value: int) -> None:
-        """Pin a path switch for THIS plan (0 / 1; negative: follow the process-wide default again)."""
+        """Pin a path switch for THIS plan (0 / 1, "lift0" 0 / 1 / 2; negative: follow the process-wide default again)."""
         _pin_option(self._inner(self.table), name, value)
         self.st.set_option(name, value)
 

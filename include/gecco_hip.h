@@ -140,6 +140,11 @@ int gecco_linear_f32(const float* A, const float* W, const float* bias, const fl
  *   per-sample fp16 images of img_feature_proj's weight (and its offsets into the bias), and the product fp16(lookup) x fp16(W a) runs one
  *   term each on the fp16-operand streaming kernel instead of split-bf16: 280 -> 154 + 24 us at C3 (2 % of an evaluation) for F_x 2.3e-4 ->
  *   2.7e-4 at C3 and up to 3.2e-4 -> 4.7e-4 on small pyramids (the mode's bar is 5e-4) — off unless asked for.
+ *   "lift0" (levels 0 / 1 / 2; default: 2 at feature_dim >= 256, where it is faster, 0 below): gecco_linear_lift_fwd_f32 computes layer 0's K | V | q from the 3-D points — they are an affine map
+ *   of three numbers per point — instead of as a (B N) x C -> 3C matrix product: 1 writes K | V and q from the points (gecco_lift0_fold_f32 +
+ *   gecco_lift0_rows), 2 writes q only and runs the layer's pool attention on the points (gecco_lift0_pool_f32), so its K | V never exist;
+ *   0 the launches of every other layer.  Any arithmetic mode, any point count.  In a plan's table (opt_mask / opt_vals) the option takes its
+ *   own bit for "level >= 1" and the bit above it for "level 2".
  * value < 0 returns the option to its default / environment (GECCO_ASTAT, GECCO_CHAIN, GECCO_HEADMAJOR, GECCO_MLPFUSED,
  * GECCO_UNPOOLFUSED, GECCO_LO8, GECCO_ACTIMG, GECCO_H8, GECCO_KVQ64, GECCO_H8AREG, GECCO_CHAIN2).
  * Process-wide DEFAULT: a network forward consults its own table first (GeccoSetTransformer.opt_mask / opt_vals, ABI 14), so two
@@ -413,6 +418,19 @@ int gecco_pool_attn_f32(const float* KV, const float* inducers, float* merged, i
 int gecco_pool_attn_ex_f32(const float* KV, const float* inducers, float* merged, int B, int N, int C, int H, int I,
                            int precision, void* ws, size_t ws_bytes, void* stream);
 size_t gecco_pool_attn_workspace_bytes(int B, int N, int C, int H, int I);
+/* Layer 0 of gecco_linear_lift_fwd_f32 from the 3-D points (option "lift0"): its input is lift(c_in p), an affine map of the points, and
+ * broadcast_norm is a per-sample affine map (a1, o1), so [K | V | q](n) = M_b (c_in p_n) + c_b with M_b = W diag(a1_b) W_lift and
+ * c_b = W (a1_b * b_lift + o1_b) + bias, W = [kv_proj (2C) | q rows of in_proj (C)] (models/set_transformer.py:49,112,150-155).  The
+ * three kernels of that path, for tests: the fold writes mc (B, 3C, 4) = {M_b rows, c_b}; `rows` writes columns col0 .. col0 + ncols of
+ * M_b (c_in p_n) + c_b as fp16 (out_f16) or fp32, (B, N, ncols) or head-major (B, ncols / head_dim, N, head_dim); `pool` the merged pool
+ * attention (B, 64, C) of `inducers` over the points, K | V never formed (ws: gecco_pool_attn_workspace_bytes(B, N, C, H, 64)).
+ * coef: gecco_edm_coeffs_f32's output (c_in at coef[4b + 2]). */
+int gecco_lift0_fold_f32(const float* kv_w, const float* q_w, const float* q_b, const float* lift_w, const float* lift_b, const float* a1,
+                         const float* o1, float* mc, int B, int C, int H, void* stream);
+int gecco_lift0_rows(const float* x, const float* coef, const float* mc, void* out, int col0, int ncols, int head_dim, int out_f16,
+                     int B, int N, int C, void* stream);
+int gecco_lift0_pool_f32(const float* x, const float* coef, const float* mc, const float* inducers, float* merged, int B, int N, int C,
+                         int H, void* ws, size_t ws_bytes, void* stream);
 
 /* Training path: backward of the two attention cores (autograd through F.scaled_dot_product_attention,
  * models/set_transformer.py:55-63, and through nn.MultiheadAttention, :112, under loss.backward(), diffusion.py:213-222),
