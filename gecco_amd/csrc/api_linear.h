@@ -3,6 +3,8 @@
 #pragma once
 #include "api_common.h"
 
+#include <optional>
+
 namespace gecco_api {
 
 // One linear, C = act(A' W^T + bias) (+ residual, + statistics): its operands (g; linear() decides g.precision and g.w_img) and where its weight image comes from
@@ -37,35 +39,50 @@ int launch_each(const SplitJobs& jobs, hipStream_t s) {   // ... and a single-im
 }
 
 // The images of one weight, or of two that share K, built into `wsplit` by one call of `launch`: the second (W null: there is none) starts
-// `second_offset_bytes` behind the first.  flags: SplitJob::pad_
-struct ImageOf { const float* W; int Nout, ldw, flags; };
+// `second_offset_bytes` behind the first.  format: of the builder `launch` is (weight_images.h)
+struct ImageOf { const float* W; int Nout, ldw; ImageFormat format; };
 inline int build_images(ImageLaunch launch, void* wsplit, int K, hipStream_t s, ImageOf first, ImageOf second = {}, size_t second_offset_bytes = 0) {
     SplitJobs jobs;
     float* img = static_cast<float*>(wsplit);
     jobs.n = 0;
-    jobs.job[jobs.n++] = SplitJob{first.W, img, first.Nout, K, first.ldw, first.flags};
-    if (second.W) jobs.job[jobs.n++] = SplitJob{second.W, img + second_offset_bytes / sizeof(float), second.Nout, K, second.ldw, second.flags};
+    jobs.job[jobs.n++] = SplitJob{first.W, img, first.Nout, K, first.ldw, first.format};
+    if (second.W) jobs.job[jobs.n++] = SplitJob{second.W, img + second_offset_bytes / sizeof(float), second.Nout, K, second.ldw, second.format};
     return launch(jobs, s);
 }
 
-// A caller's batch of image jobs (the gecco_*_images_f32 entry points), a full table per launch.  flags_of(job) gives the job's SplitJob::pad_,
-// or < 0 where the format does not take the job: the call then fails with "<who>: job <i> needs <needs>"
-template <class FlagsOf>
-int image_batch(const char* who, const char* needs, const GeccoSplitJob* jobs, int n, FlagsOf flags_of, ImageLaunch launch, hipStream_t s) {
+// A caller's batch of image jobs (the gecco_*_images_f32 entry points), a full table per launch.  format_of(job) gives the job's format
+// (std::optional<ImageFormat>), or nothing where the builder does not take the job: the call then fails with "<who>: job <i> needs <needs>"
+template <class FormatOf>
+int image_batch(const char* who, const char* needs, const GeccoSplitJob* jobs, int n, FormatOf format_of, ImageLaunch launch, hipStream_t s) {
     if (n < 0 || (n > 0 && !jobs)) return fail(-1, "%s: null argument", who);
     SplitJobs sj;
     sj.n = 0;
     for (int i = 0; i < n; ++i) {
         const GeccoSplitJob& j = jobs[i];
-        const int flags = (j.W && j.img && j.Nout > 0 && j.K > 0) ? flags_of(j) : -1;
-        if (flags < 0) return fail(-2, "%s: job %d needs %s", who, i, needs);
-        sj.job[sj.n++] = SplitJob{j.W, static_cast<float*>(j.img), j.Nout, j.K, j.ldw, flags};
+        const std::optional<ImageFormat> format = (j.W && j.img && j.Nout > 0 && j.K > 0) ? format_of(j) : std::nullopt;
+        if (!format) return fail(-2, "%s: job %d needs %s", who, i, needs);
+        sj.job[sj.n++] = SplitJob{j.W, static_cast<float*>(j.img), j.Nout, j.K, j.ldw, *format};
         if (sj.n == (int)(sizeof sj.job / sizeof sj.job[0])) {
             TRY(launch(sj, s), who);
             sj.n = 0;
         }
     }
     TRY(launch(sj, s), who);
+    return 0;
+}
+
+// The jobs of one layer's mlp_fused_f16.hip stream at `stream`, in the order the kernel consumes it: per 128-wide hidden chunk j the fp16 image
+// of W0's tile j (128 x C), then W2[:, chunk j] (C x 128) as two 64-k halves.  push(W, img, Nout, K, ldw, F16Image, what) appends one job
+// (returns != 0 to stop; `what` names the job in the network's error texts).  The stream is as large as the two images it replaces: split_f16_image_bytes(width, C) + split_f16_image_bytes(C, width)
+template <class Push>
+int mlp_fused_f16_stream_jobs(const float* W0, const float* W2, int C, int width, float* stream, Push push) {
+    const size_t w0_tile = split_f16_image_bytes(128, C) / sizeof(float), w2_half = split_f16_image_bytes(C, 64) / sizeof(float);
+    for (int jc = 0; jc < width / 128; ++jc) {
+        float* chunk = stream + (size_t)jc * (w0_tile + 2 * w2_half);
+        if (const int rc = push(W0 + (size_t)jc * 128 * C, chunk, 128, C, C, F16_PLAIN, "split(mlp.0 tile)")) return rc;
+        for (int hf = 0; hf < 2; ++hf)
+            if (const int rc = push(W2 + (size_t)jc * 128 + hf * 64, chunk + w0_tile + hf * w2_half, C, 64, width, F16_PLAIN, "split(mlp.2 K-slice)")) return rc;
+    }
     return 0;
 }
 

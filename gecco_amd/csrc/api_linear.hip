@@ -70,13 +70,19 @@ int gecco_linear_image_ok_f16(int rows, int K, int Nout, int with_prologue) { re
 size_t gecco_split_f16_image_bytes(int Nout, int K) { return split_f16_image_bytes(Nout, K); }
 int gecco_split_f16_images_f32(const GeccoSplitJob* jobs, int n, void* stream) {
     return image_batch("split_f16_images", "K % 32 == 0 (and ldw % 4 == 0 unless transposed)", jobs, n,
-                       [](const GeccoSplitJob& j) { return (j.K % 32) || (!j.transposed && (j.ldw & 3)) ? -1 : (j.transposed ? 4 : 0); },
+                       [](const GeccoSplitJob& j) -> std::optional<ImageFormat> {
+                           if ((j.K % 32) || (!j.transposed && (j.ldw & 3))) return std::nullopt;
+                           return j.transposed ? F16_TRANSPOSED : F16_PLAIN;
+                       },
                        split_f16_tiled_multi_launch, (hipStream_t)stream);
 }
 size_t gecco_split_bf16_image_bytes(int Nout, int K) { return split_bf16_image_bytes(Nout, K); }
 int gecco_split_bf16_images_f32(const GeccoSplitJob* jobs, int n, void* stream) {
     return image_batch("split_bf16_images", "K % 16 == 0 (and ldw % 4 == 0 unless transposed)", jobs, n,
-                       [](const GeccoSplitJob& j) { return (j.K % 16) || (!j.transposed && (j.ldw & 3)) ? -1 : (j.transposed ? 4 : 0); },
+                       [](const GeccoSplitJob& j) -> std::optional<ImageFormat> {
+                           if ((j.K % 16) || (!j.transposed && (j.ldw & 3))) return std::nullopt;
+                           return j.transposed ? BF16_TRANSPOSED : BF16_PLAIN;
+                       },
                        split_bf16_tiled_multi_launch, (hipStream_t)stream);
 }
 
@@ -143,7 +149,10 @@ int gecco_linear_h8_train_ok(int rows, int K, int Nout) {
 }
 int gecco_h8_images_f32(const GeccoSplitJob* jobs, int n, void* stream) {
     return image_batch("h8_images", "Nout % 64 == 0, K % 64 == 0, ldw % 4 == 0, not transposed", jobs, n,
-                       [](const GeccoSplitJob& j) { return (j.Nout % 64) || (j.K % 64) || (j.ldw & 3) || j.transposed ? -1 : 0; },
+                       [](const GeccoSplitJob& j) -> std::optional<ImageFormat> {
+                           if ((j.Nout % 64) || (j.K % 64) || (j.ldw & 3) || j.transposed) return std::nullopt;
+                           return H8_MLP0;
+                       },
                        h8_image_multi_launch, (hipStream_t)stream);
 }
 
@@ -161,7 +170,7 @@ int gecco_linear_h8_train_f32(const float* x, const float* pro_a, const float* p
     g.pro_a = pro_a; g.pro_o = pro_o; g.alpha = alpha; g.act = act; g.pre_out = pre_out; g.precision = 1; g.w_img = wsplit;
     if (!gemm_h8_train_supported(g))
         return fail(-2, "linear_h8_train: needs rows %% 128 == 0, K in {128, 256, 384}, Nout (each segment) %% 64 == 0, Nout >= 128, act 0 .. 3");
-    if (W1) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W1, Nout1, K, 0}, {n2 ? W2 : nullptr, n2, K, 0}, h8_image_bytes(Nout1, K)), "linear_h8_train(image)");
+    if (W1) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W1, Nout1, K, H8_MLP0}, {n2 ? W2 : nullptr, n2, K, H8_MLP0}, h8_image_bytes(Nout1, K)), "linear_h8_train(image)");
     TRY(gemm_h8_train_launch(g, s), "linear_h8_train");
     return 0;
 }
@@ -174,7 +183,10 @@ int gecco_linear_astat16_ok(int rows, int K, int Nout) {
 }
 int gecco_astat16_images_f32(const GeccoSplitJob* jobs, int n, void* stream) {
     return image_batch("astat16_images", "Nout % 64 == 0, K % 64 == 0 (and ldw % 4 == 0 unless transposed)", jobs, n,
-                       [](const GeccoSplitJob& j) { return (j.Nout % 64) || (j.K % 64) || (!j.transposed && (j.ldw & 3)) ? -1 : (j.transposed ? 5 : 1); },
+                       [](const GeccoSplitJob& j) -> std::optional<ImageFormat> {   // the one-term kvq stream
+                           if ((j.Nout % 64) || (j.K % 64) || (!j.transposed && (j.ldw & 3))) return std::nullopt;
+                           return kvq_format(0, 0, j.transposed ? KVQ_TRANSPOSED : KVQ_PLAIN);
+                       },
                        h8_image_multi_launch, (hipStream_t)stream);
 }
 
@@ -198,7 +210,7 @@ int gecco_linear_astat16_f32(const float* x, const float* pro_a, const float* pr
         return fail(-2, "linear_astat16: needs rows %% 128 == 0, K in {128, 256, 384, 512}, Nout (each segment) %% 64 == 0, Nout >= 128");
     if (W1) {
         if (transposed && Nout2 > 0) return fail(-2, "linear_astat16: the transposed form takes one weight");
-        TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W1, Nout1, transposed ? Nout1 : K, transposed ? 5 : 1}, {n2 ? W2 : nullptr, n2, K, 1},
+        TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W1, Nout1, transposed ? Nout1 : K, kvq_format(0, 0, transposed ? KVQ_TRANSPOSED : KVQ_PLAIN)}, {n2 ? W2 : nullptr, n2, K, kvq_format(0, 0)},
                          kvq_image_bytes(Nout1, K, 0)), "linear_astat16(image)");
     }
     TRY(gemm_astat_train_launch(g, s), "linear_astat16");
@@ -221,7 +233,7 @@ int gecco_linear_astat16_keep_y16(const float* x, const float* pro_a, const floa
     g.pro_a = pro_a; g.pro_o = pro_o; g.alpha = alpha; g.act = act; g.pre_out = pre_out; g.precision = 2; g.w_img = wsplit; g.y16_out = y16;
     if (!gemm_astat_train_supported(g))
         return fail(-2, "linear_astat16_keep: needs rows %% 128 == 0, K in {128, 256, 384, 512}, Nout %% 64 == 0, act 1 / 2 (GaussianActivation) or 3 (ReLU)");
-    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, K, 1}), "linear_astat16_keep(image)");
+    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, K, kvq_format(0, 0)}), "linear_astat16_keep(image)");
     TRY(gemm_astat_train_launch(g, s), "linear_astat16_keep");
     return 0;
 }
@@ -236,7 +248,7 @@ int gecco_linear_astat16_actbwd(const float* dy, const float* W, const float* u,
     if (!gemm_astat_train_supported(g))
         return fail(-2, "linear_astat16_actbwd: needs rows %% 128 == 0, K in {128, 256, 384, 512}, Nout %% 64 == 0, kind 1 / 2 (GaussianActivation) or 3 (ReLU)");
     // the linear's own weight (K, Nout): the stream of its transpose, straight from it
-    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, Nout, 5}), "linear_astat16_actbwd(image)");
+    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, Nout, kvq_format(0, 0, KVQ_TRANSPOSED)}), "linear_astat16_actbwd(image)");
     TRY(gemm_astat_train_launch(g, s), "linear_astat16_actbwd");
     return 0;
 }
@@ -251,7 +263,7 @@ int gecco_linear_astat16_actbwd_h16(const float* dy, const float* W, const float
     g.alpha = alpha; g.mul_u = u; g.mul_kind = kind; g.agrad = (kind == 1 || kind == 2) ? agrad : nullptr; g.precision = 2; g.w_img = wsplit; g.c_f16 = 1;
     if (!gemm_astat_train_supported(g))
         return fail(-2, "linear_astat16_actbwd_h16: needs rows %% 128 == 0, K in {128, 256, 384, 512}, Nout %% 64 == 0");
-    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, Nout, 5}), "linear_astat16_actbwd_h16(image)");
+    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, Nout, kvq_format(0, 0, KVQ_TRANSPOSED)}), "linear_astat16_actbwd_h16(image)");
     TRY(gemm_astat_train_launch(g, s), "linear_astat16_actbwd_h16");
     return 0;
 }
@@ -304,7 +316,7 @@ int gecco_linear_astat_f16(const float* x, const float* pro_a, const float* pro_
     if (!image_ready && (W2 == nullptr) != (C2 == nullptr)) return fail(-1, "linear_astat: W2 and C2 go together");
     hipStream_t s = (hipStream_t)stream;
     if (!image_ready)
-        TRY(build_images(launch_each<split_f16_tiled_launch>, wsplit, K, s, {W1, Nout1, K, 0}, {W2, Nout2, K, 0}, split_f16_image_bytes(Nout1, K)), "linear_astat(split)");
+        TRY(build_images(launch_each<split_f16_tiled_launch>, wsplit, K, s, {W1, Nout1, K, F16_PLAIN}, {W2, Nout2, K, F16_PLAIN}, split_f16_image_bytes(Nout1, K)), "linear_astat(split)");
     GemmArgs g = gemm_args_pair(x, bias1, static_cast<float*>(C1), Nout1, bias2, static_cast<float*>(C2), C2 ? Nout2 : 0, B, rows, K);
     g.pro_a = pro_a; g.pro_o = pro_o; g.alpha = alpha; g.act = act; g.precision = 2; g.w_img = wsplit; g.c_f16 = 1; g.hm_hd = head_dim;
     if (int rc = check_alpha("linear_astat", act, alpha, -6)) return rc;
@@ -338,14 +350,14 @@ int gecco_linear_kvq_y16_f16(const float* x, const float* pro_a, const float* pr
     g.y16_out = y16;
     // (the two-term range must be whole 384-column segments: it is a range of TILES in the stream)
     g.kvq_perm = option(OPT_KVQPERM) && kvq_perm48_ok(head_dim, K, Nout1, Nout2) && lo_begin % 384 == 0 && lo_end % 384 == 0;
-    const int p48 = g.kvq_perm ? 64 : 0;
+    const KvqOrder order = g.kvq_perm ? KVQ_HEAD48 : KVQ_PLAIN;
     if (!gemm_kvq_astat_supported(g))
         return fail(-2, "linear_kvq: needs rows %% 128 == 0, Nout1 + Nout2 >= 128, K in {128, 256, 384, 512}; head-major: head_dim %% 8 == 0 "
                         "dividing both segment widths");
     if (W1) {   // NULL: wsplit still holds the stream a previous call made from the same weights
         if (Nout2 > 0 && !W2) return fail(-1, "linear_kvq: W2 missing");
-        TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W1, Nout1, K, 1 | p48 | ((lo_begin / 64) << 8) | ((lo_end / 64) << 20)},
-                         {Nout2 > 0 ? W2 : nullptr, Nout2, K, 1 | p48}, kvq_image_bytes(Nout1, K, lo_end - lo_begin)), "linear_kvq(image)");
+        TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W1, Nout1, K, kvq_format(lo_begin / 64, lo_end / 64, order)},
+                         {Nout2 > 0 ? W2 : nullptr, Nout2, K, kvq_format(0, 0, order)}, kvq_image_bytes(Nout1, K, lo_end - lo_begin)), "linear_kvq(image)");
     }
     TRY(gemm_kvq_astat_launch(g, s), "linear_kvq");
     return 0;
@@ -366,7 +378,7 @@ int gecco_linear_h8_img_f32(const float* x, const float* pro_a, const float* pro
     if (!gemm_h8_astat_supported(g))
         return fail(-2, "linear_h8_img: needs rows %% 128 == 0, Nout %% 64 == 0, Nout >= 128, K in {128, 256, 384}, act in 0 .. 3");
     // W == NULL: wsplit still holds the image a previous call made from the same weights
-    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, K, g.h6 ? 32 : 0}), "linear_h8_img(image)");
+    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, K, g.h6 ? H8_H6 : H8_MLP0}), "linear_h8_img(image)");
     TRY(gemm_h8_astat_launch(g, s), "linear_h8_img");
     return 0;
 }
@@ -380,7 +392,7 @@ int gecco_linear_h8_areg_f32(const void* a_img, const float* W, const float* bia
     if (!gemm_h8_areg_supported(g))
         return fail(-2, "linear_h8_areg: needs rows %% 128 == 0, K in {128, 256, 384, 512, 768, 1024}, Nout %% 4 == 0");
     // W == NULL: wsplit still holds the image a previous call made from the same weights
-    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, K, 2}), "linear_h8_areg(image)");
+    if (W) TRY(build_images(h8_image_multi_launch, wsplit, K, s, {W, Nout, K, H8_W128}), "linear_h8_areg(image)");
     TRY(gemm_h8_areg_launch(g, s), "linear_h8_areg");
     return 0;
 }
@@ -394,16 +406,16 @@ int gecco_mlp_fused_f16(float* x, const float* pro_a, const float* pro_o, const 
         return fail(-2, "mlp_fused: needs C in {128, 256, 384}, width == 2 C, rows %% 128 == 0");
     hipStream_t s = (hipStream_t)stream;
     float* img = static_cast<float*>(wsplit);
-    SplitJobs jobs;
-    jobs.n = 0;
-    const int nkb = C / 32;
-    for (int jc = 0; jc < width / 128; ++jc) {   // the stream order of mlp_fused_f16.hip
-        float* cb = img + (size_t)jc * 2 * nkb * 2048;
-        jobs.job[jobs.n++] = SplitJob{W0 + (size_t)jc * 128 * C, cb, 128, C, C, 0};
-        for (int hf = 0; hf < 2; ++hf)
-            jobs.job[jobs.n++] = SplitJob{W2 + (size_t)jc * 128 + hf * 64, cb + (size_t)(nkb + hf * (nkb / 2)) * 2048, C, 64, width, 0};
+    if (W0) {   // W0 == W2 == NULL: wsplit holds the image already
+        SplitJobs jobs;   // (3 jobs per hidden chunk, width <= 768: 18 of the table's 96)
+        jobs.n = 0;
+        TRY(mlp_fused_f16_stream_jobs(W0, W2, C, width, img, [&jobs](const float* W, float* at, int Nout, int K, int ldw, F16Image format, const char*) {
+                if (jobs.n >= (int)(sizeof jobs.job / sizeof jobs.job[0])) return -9;
+                jobs.job[jobs.n++] = SplitJob{W, at, Nout, K, ldw, format};
+                return 0;
+            }), "mlp_fused(split)");
+        TRY(split_f16_tiled_multi_launch(jobs, s), "mlp_fused(split)");
     }
-    if (W0) TRY(split_f16_tiled_multi_launch(jobs, s), "mlp_fused(split)");   // W0 == W2 == NULL: wsplit holds the image already
     MlpArgs ma{};
     ma.x = x; ma.pro_a = pro_a; ma.pro_o = pro_o; ma.w_stream = img; ma.b0 = b0; ma.b2 = b2; ma.alpha = alpha; ma.act = act;
     ma.stats = stats; ma.B = B; ma.rows = rows;
@@ -431,7 +443,7 @@ int gecco_unpool_outproj_h8(float* x, const void* q16, const float* kvh, const f
     if (!unpool_outproj_h8_supported(C, H, rows))
         return fail(-2, "unpool_outproj_h8: needs (C, head dim) in {(128, 16), (256, 32), (384, 48)}, rows %% 128 == 0");
     hipStream_t s = (hipStream_t)stream;
-    if (W) TRY(build_images(h8_image_multi_launch, wsplit, C, s, {W, C, C, 16}), "unpool_outproj_h8(split)");   // W == NULL: image ready
+    if (W) TRY(build_images(h8_image_multi_launch, wsplit, C, s, {W, C, C, H8_ATTN_ORDER}), "unpool_outproj_h8(split)");   // W == NULL: image ready
     void* kvimg = static_cast<char*>(wsplit) + h8_image_bytes(C, C);
     TRY(kvh_image_launch(kvh, kvimg, B, C, H, s), "unpool_outproj_h8(k | v image)");
     UnpoolH8Args ua{};

@@ -101,7 +101,8 @@ int linear_pair(const Lin& a, const float* W2, const float* b2, int Nout2, float
         } else {
             if (!a.wsplit) return 1;
             const bool x3 = precision == 1;
-            const int rc = build_images(x3 ? launch_each<split_bf16_tiled_launch> : launch_each<split_f16_tiled_launch>, a.wsplit, K, s, {g.W, Nout1, K, 0}, {W2, Nout2, K, 0},
+            const ImageFormat plain = x3 ? ImageFormat(BF16_PLAIN) : ImageFormat(F16_PLAIN);
+            const int rc = build_images(x3 ? launch_each<split_bf16_tiled_launch> : launch_each<split_f16_tiled_launch>, a.wsplit, K, s, {g.W, Nout1, K, plain}, {W2, Nout2, K, plain},
                                         x3 ? split_bf16_image_bytes(Nout1, K) : split_f16_image_bytes(Nout1, K));
             if (rc) return rc;
             g.w_img = a.wsplit;
@@ -124,11 +125,11 @@ struct STWorkspace {
     float *merged, *h0, *u, *h2, *h, *kvh;  // inducer chain (B,I,*)
     float* wsplit;                     // tiled bf16 hi | lo image of the weight in use (unit calls, split-bf16 mode)
     float* wimg;                       // images of every layer's N-token weights, built once per forward
-    // One layer's slot of `wimg`: where the image of each weight starts, in floats from the slot's start (kv_proj at 0), at 4 bytes per weight element
-    // (2 in fp16 mode); the mixed mode's narrower formats sit inside the same places.  The image builder and the launches both read these.
+    // One layer's slot of `wimg`: where the image of each weight starts, in floats from the slot's start (kv_proj at 0).  A place is as large as the
+    // weight's tiled image in the mode's own arithmetic (carve_st).  The image builder and the launches both read these.
     size_t wimg_layer, o_q, o_out, o_w0, o_w2;   // floats per layer; q_proj, unpool.out_proj, mlp.0, mlp.2
     size_t o_pout, o_b0, o_b2, o_ukv, b2_half;   // the 64-inducer chain: pool.out_proj, broadcast mlp, unpool k|v; its one-launch forms walk mlp.2 K-half by K-half
-    size_t o_mf, mf_chunk, mf_w2, mf_half;       // fused point MLP: W0 tile j | W2 K-slice j (two halves), j = 0 .. width/128 (fp16 mode: floats per j, W2's place, one half)
+    size_t o_mf;                                 // fused point MLP: fp16 mode, its one stream (mlp_fused_f16_stream_jobs); w2 mode, mlp_fused_w.hip's
     size_t o_q16, o_kv_lo, o_q64;                // mixed mode: fp16 hi images of kv_proj | q_proj back to back, then kv_proj's lo image; the kvq stream's q tiles
     float* mc;                         // option "lift0": layer 0's folded (M_b | c_b), (B, 3C, 4)
     size_t bytes;
@@ -168,25 +169,26 @@ STWorkspace carve_st(const GeccoSetTransformer* st, int B, int N, void* base) {
         w.wsplit = c.f32(((wmax + 127) / 128 * 128) * (size_t)(W > C ? W : C));
     }
     {   // per layer: kv_proj | q_proj (contiguous: the fused pair streams them as one image), out_proj, mlp.0, mlp.2
-        // (floats: 4 bytes per weight element in split-bf16 mode, 2 in fp16 mode)
         const int prec = st->precision == 4 ? 3 : st->precision;   // 4 ("w2") = the mixed mode with the one-launch point MLP
-        const size_t half = prec == 2 ? 2 : 1;
-        auto pad = [half](size_t n) { return (n + 127) / 128 * 128 / half; };
-        w.o_q = pad(2 * C) * C;
-        w.o_out = w.o_q + pad(C) * C;
-        w.o_w0 = w.o_out + pad(C) * C;
-        w.o_w2 = w.o_w0 + pad(W) * C;
-        w.o_pout = w.o_w2 + pad(C) * W;
-        w.o_b0 = w.o_pout + pad(C) * C;
-        w.o_b2 = w.o_b0 + pad(W) * C;
-        w.o_ukv = w.o_b2 + pad(C) * W;
-        w.o_mf = w.o_ukv + pad(2 * C) * C;
-        w.wimg_layer = w.o_mf + (prec == 2 ? pad(W) * C + pad(C) * W : 0);
+        // The size of a place, in floats: the weight's F16_PLAIN image in fp16 mode, else its BF16_PLAIN image.  The mixed mode keeps the split-bf16
+        // size and builds its own formats (H8_*, the kvq stream, F16_HI_LO, F16_PLAIN + a lo image) inside it: none of them is larger
+        auto img = [prec](size_t n, size_t k) { return (prec == 2 ? split_f16_image_bytes((int)n, (int)k) : split_bf16_image_bytes((int)n, (int)k)) / sizeof(float); };
+        w.o_q = img(2 * C, C);
+        w.o_out = w.o_q + img(C, C);
+        w.o_w0 = w.o_out + img(C, C);
+        w.o_w2 = w.o_w0 + img(W, C);
+        w.o_pout = w.o_w2 + img(C, W);
+        w.o_b0 = w.o_pout + img(C, C);
+        w.o_b2 = w.o_b0 + img(W, C);
+        w.o_ukv = w.o_b2 + img(C, W);
+        w.o_mf = w.o_ukv + img(2 * C, C);
+        w.wimg_layer = w.o_mf + (prec == 2 ? img(W, C) + img(C, W) : 0);   // (the stream of mlp_fused_f16_stream_jobs: as large as mlp.0's and mlp.2's images)
         // "w2" mode: the weight stream of the one-launch point MLP (mlp_fused_w.hip) at o_mf
         if (st->precision == 4 && mlp_fused_w_supported((int)C, (int)W, 128)) w.wimg_layer += mlp_fused_w_image_bytes((int)C, (int)W) / sizeof(float);
         w.wimg = prec >= 1 ? c.f32(w.wimg_layer * st->n_layers) : nullptr;
-        w.b2_half = C * C / half; w.mf_w2 = C / 32 * 2048; w.mf_half = C / 32 / 2 * 2048; w.mf_chunk = 2 * w.mf_w2;
-        w.o_q16 = (2 * C + 127) / 128 * 128 * C / 2; w.o_kv_lo = w.o_q16 + (C + 127) / 128 * 128 * C / 2;
+        w.b2_half = img(C, C);   // the image of one (C, C) K-half of the broadcast mlp.2: read by the one-launch chains only (chain_stream_fits)
+        const size_t f16_kv = split_f16_image_bytes(2 * (int)C, (int)C) / sizeof(float), f16_q = split_f16_image_bytes((int)C, (int)C) / sizeof(float);
+        w.o_q16 = f16_kv; w.o_kv_lo = f16_kv + f16_q;
         w.o_q64 = kvq_image_bytes(2 * (int)C, (int)C, (int)C) / sizeof(float);
     }
     w.mc = c.f32((size_t)B * 3 * C * 4);   // (last: every other place is where it was)
@@ -197,8 +199,10 @@ STWorkspace carve_st(const GeccoSetTransformer* st, int B, int N, void* base) {
 // The one-launch inducer chain reads pool.out_proj | broadcast.mlp.0 | mlp.2 | unpool k|v as ONE stream from o_pout: the four places must be consecutive and
 // exactly filled by their images (fp16; at 4 bytes per weight element the hi | lo blocks of a two-term one), mlp.2's by its width / C K-half images
 bool chain_stream_fits(const GeccoSetTransformer* st, const STWorkspace& w) {
-    const size_t C = st->C, W = st->width, half = st->precision == 2 ? 2 : 1;   // (false only after an edit that breaks carve_st: no shape the chain takes gets here)
-    auto img = [half](size_t n, size_t k) { return split_bf16_image_bytes((int)n, (int)k) / sizeof(float) / half; };
+    const size_t C = st->C, W = st->width;   // (false only after an edit that breaks carve_st: no shape the chain takes gets here)
+    const bool f16 = st->precision == 2;      // the chain's F16_PLAIN images; else its F16_HI_LO ones: twice those, a BF16_PLAIN image's size
+    auto img = [f16](size_t n, size_t k) { return (f16 ? split_f16_image_bytes((int)n, (int)k) : 2 * split_f16_image_bytes((int)n, (int)k)) / sizeof(float); };
+    if (C % 128) return false;   // (a K-half image pads its C rows up to the column tile: the halves fill mlp.2's place only without pad rows)
     return w.o_b0 - w.o_pout == img(C, C) && w.o_b2 - w.o_b0 == img(W, C) && w.o_ukv - w.o_b2 == W / C * w.b2_half && w.o_mf - w.o_ukv == img(2 * C, C);
 }
 
@@ -275,7 +279,7 @@ struct StRoute {
     // L stages)
     bool kvq16_on;
     int use64;    // astat_linear's kernel for kv_proj | q_proj: 2 the kvq stream with L stages, 1 the one-term kvq stream, 0 128-column tiles
-    int kvq_p48;  // 64 (the SplitJob bit): head dim 48 has the kvq stream in the head-aligned column order (option "kvqperm")
+    bool kvq_p48; // head dim 48 has the kvq stream in the head-aligned column order (KVQ_HEAD48; option "kvqperm")
     bool lo8;     // the lo image of kv_proj as fp8 x 2^19 in 64-k blocks, where the A-stationary kernel has that form (option "lo8")
     // ... and mlp.2 / out_proj as h8 products fed from h8 activation images (gemm_h8_areg.hip; option "h8areg")
     bool h8x, h8o;
@@ -367,7 +371,7 @@ StRoute st_route(const GeccoSetTransformer* st, int B, int N, const float* const
     r.astat = option(OPT_ASTAT);
     r.hd_try = option(OPT_HEADMAJOR) ? C / H : 0;
     r.use64 = r.kvq_on ? 2 : r.kvq16_on ? 1 : 0;
-    r.kvq_p48 = (r.kvq_on && option(OPT_KVQPERM) && r.hd_try && kvq_perm48_ok(C / H, C, 2 * C, C)) ? 64 : 0;
+    r.kvq_p48 = r.kvq_on && option(OPT_KVQPERM) && r.hd_try && kvq_perm48_ok(C / H, C, 2 * C, C);
     r.lo8 = mixed && !r.kvq_on && option(OPT_LO8) && gemm_f16_astat_lo8_supported(C);
     r.io16 = (pr == 2 || mixed) && r.imgs && N >= 128 && attn_x3_supported(C / H) && !(C % 8) && !(Wd % 8);
     if (mixed && !(r.io16 && !(N % 128) && !(C % 128))) {
@@ -407,17 +411,18 @@ struct JobQueue {   // a SplitJobs table and the kernel that takes it
     hipStream_t s;
     JobQueue(int (*launch_)(const SplitJobs&, hipStream_t), hipStream_t s_) : launch(launch_), s(s_) { jobs.n = 0; }
     int flush() { const int rc = launch(jobs, s); jobs.n = 0; return rc; }
-    int push(const float* Wp, float* img, int Nout, int K, int ldw, int kind) {
-        return push_job(jobs.job, jobs.n, SplitJob{Wp, img, Nout, K, ldw, kind}, [this] { return launch(jobs, s); });
+    int push(const float* Wp, float* img, int Nout, int K, int ldw, ImageFormat format) {   // (a format of the builder `launch` is)
+        return push_job(jobs.job, jobs.n, SplitJob{Wp, img, Nout, K, ldw, format}, [this] { return launch(jobs, s); });
     }
 };
 
-// Every N-token weight of every layer becomes its image in the layer's slot of w.wimg, in the format the route's consumer reads (SplitJob::pad_): ONE launch
+// Every N-token weight of every layer becomes its image in the layer's slot of w.wimg, in the format the route's consumer reads (weight_images.h): ONE launch
 // per image kernel and 6 layers (weights may change between calls: nothing is cached across forwards unless the caller vouches for the workspace's images —
 // GeccoSetTransformer.images_ready)
 int build_weight_images(const StRoute& r, const GeccoSetTransformer* st, const STWorkspace& w, const float* const* h_in, hipStream_t s) {
     const int C = st->C, Wd = st->width, act = st->act;
-    JobQueue jobs(r.pr == 2 ? split_f16_tiled_multi_launch : split_bf16_tiled_multi_launch, s);   // the tiled images of the mode's own arithmetic
+    JobQueue jobs(r.pr == 2 ? split_f16_tiled_multi_launch : split_bf16_tiled_multi_launch, s);   // the tiled images of the mode's own arithmetic ...
+    const ImageFormat plain = r.pr == 2 ? ImageFormat(F16_PLAIN) : ImageFormat(BF16_PLAIN);          // ... all in its builder's plain format
     JobQueue jobs16(split_f16_tiled_multi_launch, s);   // the fp16 images of the mixed mode (kv_proj | q_proj, hi and lo; the two-term chain)
     JobQueue jobs8(h8_image_multi_launch, s);           // the h8 images and the kvq streams
     MlpWImageJob mjobs[16];   // the one-launch point MLP's streams (w2 mode)
@@ -432,58 +437,57 @@ int build_weight_images(const StRoute& r, const GeccoSetTransformer* st, const S
         const bool kv_img = !cached && !pts, q_img = !pts;
         if (r.kvq_on) {
             // the kvq stream: K | V tiles (the V half with L stages), then the q tiles
-            if (kv_img) TRY(jobs8.push(L.kv_proj_w, base, 2 * C, C, C, 1 | r.kvq_p48 | ((C / 64) << 8) | ((2 * C / 64) << 20)), "split(kv_proj, kvq)");
-            if (q_img) TRY(jobs8.push(L.in_proj_w, base + w.o_q64, C, C, C, 1 | r.kvq_p48), "split(q_proj, kvq)");
+            const KvqOrder order = r.kvq_p48 ? KVQ_HEAD48 : KVQ_PLAIN;
+            if (kv_img) TRY(jobs8.push(L.kv_proj_w, base, 2 * C, C, C, kvq_format(C / 64, 2 * C / 64, order)), "split(kv_proj, kvq)");
+            if (q_img) TRY(jobs8.push(L.in_proj_w, base + w.o_q64, C, C, C, kvq_format(0, 0, order)), "split(q_proj, kvq)");
         } else if (r.mixed) {
             // fp16 hi images of kv_proj | q_proj back to back (one stream for the A-stationary kernel), then kv_proj's lo image
-            if (kv_img) TRY(jobs16.push(L.kv_proj_w, base, 2 * C, C, C, 0), "split(weights)");
-            if (q_img) TRY(jobs16.push(L.in_proj_w, base + w.o_q16, C, C, C, 0), "split(weights)");   // q_proj is one-term: no lo image
-            if (kv_img) TRY(jobs16.push(L.kv_proj_w, base + w.o_kv_lo, 2 * C, C, C, r.lo8 ? 2 : 1), "split(weights)");
+            if (kv_img) TRY(jobs16.push(L.kv_proj_w, base, 2 * C, C, C, F16_PLAIN), "split(weights)");
+            if (q_img) TRY(jobs16.push(L.in_proj_w, base + w.o_q16, C, C, C, F16_PLAIN), "split(weights)");   // q_proj is one-term: no lo image
+            if (kv_img) TRY(jobs16.push(L.kv_proj_w, base + w.o_kv_lo, 2 * C, C, C, r.lo8 ? F16_LO_FP8 : F16_LO), "split(weights)");
         }
         const bool chain2_here = r.chain2_on && !cached;
         if (chain2_here) {
             // one stream of fp16 blocks, hi | lo per column tile, in the order the chain consumes them: pool.out_proj, broadcast.mlp.0,
             // broadcast.mlp.2 K-half by K-half, unpool k|v (carve_st: the four places are consecutive and as large as these images)
-            TRY(jobs16.push(L.pool_out_w, base + w.o_pout, C, C, C, 8), "split(pool.out_proj, two-term)");
-            TRY(jobs16.push(L.bmlp.w0, base + w.o_b0, Wd, C, C, 8), "split(broadcast.mlp.0, two-term)");
+            TRY(jobs16.push(L.pool_out_w, base + w.o_pout, C, C, C, F16_HI_LO), "split(pool.out_proj, two-term)");
+            TRY(jobs16.push(L.bmlp.w0, base + w.o_b0, Wd, C, C, F16_HI_LO), "split(broadcast.mlp.0, two-term)");
             for (int hf = 0; hf < Wd / C; ++hf)
-                TRY(jobs16.push(L.bmlp.w2 + (size_t)hf * C, base + w.o_b2 + hf * w.b2_half, C, C, Wd, 8), "split(broadcast.mlp.2 K-half, two-term)");
-            TRY(jobs16.push(L.in_proj_w + (size_t)C * C, base + w.o_ukv, 2 * C, C, C, 8), "split(unpool.in_proj kv, two-term)");
+                TRY(jobs16.push(L.bmlp.w2 + (size_t)hf * C, base + w.o_b2 + hf * w.b2_half, C, C, Wd, F16_HI_LO), "split(broadcast.mlp.2 K-half, two-term)");
+            TRY(jobs16.push(L.in_proj_w + (size_t)C * C, base + w.o_ukv, 2 * C, C, C, F16_HI_LO), "split(unpool.in_proj kv, two-term)");
         }
         if (r.kvq16_on) {   // one-term kvq stream: K | V tiles, then the q tiles (o_q = the end of the kv image: 2 bytes per weight)
-            if (kv_img) TRY(jobs8.push(L.kv_proj_w, base, 2 * C, C, C, 1), "split(kv_proj, kvq)");
-            if (q_img) TRY(jobs8.push(L.in_proj_w, base + w.o_q, C, C, C, 1), "split(q_proj, kvq)");
+            if (kv_img) TRY(jobs8.push(L.kv_proj_w, base, 2 * C, C, C, kvq_format(0, 0)), "split(kv_proj, kvq)");
+            if (q_img) TRY(jobs8.push(L.in_proj_w, base + w.o_q, C, C, C, kvq_format(0, 0)), "split(q_proj, kvq)");
         }
         if (!cached && !chain2_here) {
-            if (!own_kvq && kv_img) TRY(jobs.push(L.kv_proj_w, base, 2 * C, C, C, 0), "split(kv_proj)");
-            TRY(jobs.push(L.pool_out_w, base + w.o_pout, C, C, C, 0), "split(pool.out_proj)");
-            TRY(jobs.push(L.bmlp.w0, base + w.o_b0, Wd, C, C, 0), "split(broadcast.mlp.0)");
+            if (!own_kvq && kv_img) TRY(jobs.push(L.kv_proj_w, base, 2 * C, C, C, plain), "split(kv_proj)");
+            TRY(jobs.push(L.pool_out_w, base + w.o_pout, C, C, C, plain), "split(pool.out_proj)");
+            TRY(jobs.push(L.bmlp.w0, base + w.o_b0, Wd, C, C, plain), "split(broadcast.mlp.0)");
             if (r.chain_on) {   // the one-launch chain walks mlp.2 K-half by K-half: one (C x C) image per half
                 for (int hf = 0; hf < Wd / C; ++hf)
-                    TRY(jobs.push(L.bmlp.w2 + (size_t)hf * C, base + w.o_b2 + hf * w.b2_half, C, C, Wd, 0), "split(broadcast.mlp.2 K-half)");
+                    TRY(jobs.push(L.bmlp.w2 + (size_t)hf * C, base + w.o_b2 + hf * w.b2_half, C, C, Wd, plain), "split(broadcast.mlp.2 K-half)");
             } else {
-                TRY(jobs.push(L.bmlp.w2, base + w.o_b2, C, Wd, Wd, 0), "split(broadcast.mlp.2)");
+                TRY(jobs.push(L.bmlp.w2, base + w.o_b2, C, Wd, Wd, plain), "split(broadcast.mlp.2)");
             }
         }
-        if (!chain2_here) TRY(jobs.push(L.in_proj_w + (size_t)C * C, base + w.o_ukv, 2 * C, C, C, 0), "split(unpool.in_proj kv)");
-        if (!own_kvq && q_img) TRY(jobs.push(L.in_proj_w, base + w.o_q, C, C, C, 0), "split(q_proj)");
-        if (r.h8o) TRY(jobs8.push(L.unpool_out_w, base + w.o_out, C, C, C, r.uo8_on ? 16 : 2), "split(out_proj, h8)");   // 16: 64-column tiles, attention k order
-        else TRY(jobs.push(L.unpool_out_w, base + w.o_out, C, C, C, 0), "split(out_proj)");
-        if (r.mlpf_on) {   // one stream in consumption order: per hidden chunk j, W0 tile j, then W2[:, chunk j] in two K-halves
-            for (int jc = 0; jc < Wd / 128; ++jc) {
-                float* cb = base + w.o_mf + jc * w.mf_chunk;
-                TRY(jobs.push(L.mlp.w0 + (size_t)jc * 128 * C, cb, 128, C, C, 0), "split(mlp.0 tile)");
-                for (int hf = 0; hf < 2; ++hf)
-                    TRY(jobs.push(L.mlp.w2 + (size_t)jc * 128 + hf * 64, cb + w.mf_w2 + hf * w.mf_half, C, 64, Wd, 0), "split(mlp.2 K-slice)");
-            }
+        if (!chain2_here) TRY(jobs.push(L.in_proj_w + (size_t)C * C, base + w.o_ukv, 2 * C, C, C, plain), "split(unpool.in_proj kv)");
+        if (!own_kvq && q_img) TRY(jobs.push(L.in_proj_w, base + w.o_q, C, C, C, plain), "split(q_proj)");
+        if (r.h8o) TRY(jobs8.push(L.unpool_out_w, base + w.o_out, C, C, C, r.uo8_on ? H8_ATTN_ORDER : H8_W128), "split(out_proj, h8)");
+        else TRY(jobs.push(L.unpool_out_w, base + w.o_out, C, C, C, plain), "split(out_proj)");
+        if (r.mlpf_on) {   // one stream in the kernel's consumption order (fp16 mode: `jobs` is the fp16 builder's queue)
+            const int rc = mlp_fused_f16_stream_jobs(L.mlp.w0, L.mlp.w2, C, Wd, base + w.o_mf, [&jobs](const float* W, float* at, int Nout, int K, int ldw, F16Image format, const char* what) {
+                return check(jobs.push(W, at, Nout, K, ldw, format), what);   // "split(mlp.0 tile)" / "split(mlp.2 K-slice)"
+            });
+            if (rc) return rc;
         } else if (r.mfw_on) {   // the one-launch point MLP's streams: all layers in one launch, behind the loop
             TRY(push_job(mjobs, nmj, MlpWImageJob{L.mlp.w0, L.mlp.b0, L.mlp.w2, L.mlp.b2, base + w.o_mf, L.mlp.alpha}, flush_mj), "split(mlp, w2 streams)");
         } else {
             // h8: same bytes as the split-bf16 image it replaces: fp16 hi + fp8 lo + fp8 W per element
-            if (r.h8_on) TRY(jobs8.push(L.mlp.w0, base + w.o_w0, Wd, C, C, r.h6_on ? 32 : 0), "split(mlp.0, h8)");
-            else TRY(jobs.push(L.mlp.w0, base + w.o_w0, Wd, C, C, 0), "split(mlp.0)");
-            if (r.h8x) TRY(jobs8.push(L.mlp.w2, base + w.o_w2, C, Wd, Wd, 2), "split(mlp.2, h8)");
-            else TRY(jobs.push(L.mlp.w2, base + w.o_w2, C, Wd, Wd, 0), "split(mlp.2)");
+            if (r.h8_on) TRY(jobs8.push(L.mlp.w0, base + w.o_w0, Wd, C, C, r.h6_on ? H8_H6 : H8_MLP0), "split(mlp.0, h8)");
+            else TRY(jobs.push(L.mlp.w0, base + w.o_w0, Wd, C, C, plain), "split(mlp.0)");
+            if (r.h8x) TRY(jobs8.push(L.mlp.w2, base + w.o_w2, C, Wd, Wd, H8_W128), "split(mlp.2, h8)");
+            else TRY(jobs.push(L.mlp.w2, base + w.o_w2, C, Wd, Wd, plain), "split(mlp.2)");
         }
     }
     TRY(jobs.flush(), "split(weights)");

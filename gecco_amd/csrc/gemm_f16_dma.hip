@@ -246,17 +246,17 @@ __global__ __launch_bounds__(DNT, A16 ? 3 : 2) void gemm_f16_kernel(GemmArgs g) 
 // at float offset (ct * K/32 + kt) * 2048 holds row rb at rb * 16 floats (64 B = 32 fp16); its 16-byte chunk
 // s ^ ((rb >> 2) & 3) holds k = 16 (s >> 1) + 8 (s & 1) .. +7 (lane half s >> 1, MFMA s & 1 of the step).  Rows past
 // Nout repeat the last row (masked in the GEMM epilogue).  One thread per (block, row, chunk).
-// lo == 1: the image of the LOW part, fp16(W - float(fp16(W))) — the second term of a two-term fp16 weight (mixed mode);
-// lo == 4: W is (K, ldw) and the image is of W^T (the training path's dX products)
+// F16_LO: the image of the LOW part, fp16(W - float(fp16(W))) — the second term of a two-term fp16 weight (mixed mode);
+// F16_TRANSPOSED: W is (K, ldw) and the image is of W^T (the training path's dX products)
 __device__ __forceinline__ void f16_image_item(const float* __restrict__ W, float* __restrict__ img, int Nout, int K,
-                                               int ldw, size_t i, int lo = 0) {
+                                               int ldw, size_t i, F16Image form = F16_PLAIN) {
     const int nk = K / FBK;
     const int chp = (int)(i & 3), rb = (int)((i >> 2) & 127);
     const size_t blk = i >> 9;
     const int kt = (int)(blk % nk), ct = (int)(blk / nk);
     const int s = chp ^ ((rb >> 2) & 3);
     f32x4 w0, w1;
-    if (lo == 4) {   // the image of W^T from W (K, ldw) itself (the dX product of a linear is linear(dY, W^T)): eight strided reads
+    if (form == F16_TRANSPOSED) {   // the image of W^T from W (K, ldw) itself (the dX product of a linear is linear(dY, W^T)): eight strided reads
         const float* src = W + (size_t)(kt * FBK + 16 * (s >> 1) + 8 * (s & 1)) * ldw + min(ct * DBN + rb, Nout - 1);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -269,7 +269,7 @@ __device__ __forceinline__ void f16_image_item(const float* __restrict__ W, floa
         w1 = *reinterpret_cast<const f32x4*>(src + 4);
     }
     f16x8 v = cvt8(w0, w1);
-    if (lo == 1) {
+    if (form == F16_LO) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             w0[e] -= (float)v[e];
@@ -365,18 +365,18 @@ __device__ __forceinline__ void f16_image_item_hilo(const float* __restrict__ W,
     const int idx = (int)(blk2 % (2 * nk)), ct = (int)(blk2 / (2 * nk)), lo = idx >= nk, kt = idx % nk;
     const size_t src_item = (((size_t)ct * nk + kt) << 9) | (i & 511);
     // the plain item writes to img + (ct nk + kt) FB_TILE: shift the base so that it lands on block blk2
-    f16_image_item(W, img + ((ptrdiff_t)blk2 - (ptrdiff_t)((size_t)ct * nk + kt)) * FB_TILE, Nout, K, ldw, src_item, lo);
+    f16_image_item(W, img + ((ptrdiff_t)blk2 - (ptrdiff_t)((size_t)ct * nk + kt)) * FB_TILE, Nout, K, ldw, src_item, lo ? F16_LO : F16_PLAIN);
 }
 
 __global__ void split_f16_tiled_multi_kernel(SplitJobs jobs) {
     const SplitJob j = jobs.job[blockIdx.y];
-    if (j.pad_ == 8) {
+    if (j.format.bits() == F16_HI_LO) {
         const size_t total2 = (size_t)((j.Nout + DBN - 1) / DBN) * (j.K / FBK) * 1024;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total2; i += (size_t)gridDim.x * blockDim.x)
             f16_image_item_hilo(j.W, j.img, j.Nout, j.K, j.ldw, i);
         return;
     }
-    if (j.pad_ == 2) {
+    if (j.format.bits() == F16_LO_FP8) {
         const size_t total8 = (size_t)((j.Nout + DBN - 1) / DBN) * (j.K / 64) * 512;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total8; i += (size_t)gridDim.x * blockDim.x)
             f8lo_image_item(j.W, j.img, j.Nout, j.K, j.ldw, i);
@@ -384,7 +384,7 @@ __global__ void split_f16_tiled_multi_kernel(SplitJobs jobs) {
     }
     const size_t total = (size_t)((j.Nout + DBN - 1) / DBN) * (j.K / FBK) * 512;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
-        f16_image_item(j.W, j.img, j.Nout, j.K, j.ldw, i, j.pad_);
+        f16_image_item(j.W, j.img, j.Nout, j.K, j.ldw, i, static_cast<F16Image>(j.format.bits()));   // F16_PLAIN, F16_LO or F16_TRANSPOSED
 }
 
 template <int DNS, int BM, bool A16, bool C16>

@@ -427,7 +427,7 @@ __global__ void split_bf16_tiled_multi_kernel(SplitJobs jobs) {
         const int kt = (int)(blk % nk), ct = (int)(blk / nk);
         const int c = ch ^ ((rb >> 3) & 1);
         f32x4 x0, x1;
-        if (j.pad_ == 4) {
+        if (j.format.bits() == BF16_TRANSPOSED) {
             // the image of W^T from W (K, ldw) itself (the dX product of a linear is linear(dY, W^T)): row n of the image is
             // column n of W — eight strided reads, consecutive n in consecutive threads
             const float* src = j.W + (size_t)(kt * DBK + c * 8) * j.ldw + min(ct * DBN + rb, j.Nout - 1);

@@ -250,20 +250,19 @@ __device__ __forceinline__ void kvq_image_item(const float* __restrict__ W, floa
     *reinterpret_cast<u32x4*>(img + st * H_STAGE + sub * 1024 + n * 16 + pc * 4) = out;
 }
 
-// SplitJob::pad_ = 0: the h8 stream of mlp.0 (64-column tiles), 32: its h6 form (fp6 cross terms with block scales); 2: the same in 128-column tiles (gemm_h8_areg.hip); 16: 64-column
-// tiles in the attention accumulator's k order (unpool_outproj_h8.hip);
-// pad_ = 1 | lo_begin << 8 | lo_end << 20 (64-column tiles): the kv | q stream; | 4: of W^T, from W (K, ldw) (one-term)
+// One job per blockIdx.y, in the format its SplitJob::format names (H8Image / kvq_format, weight_images.h)
 __global__ void h8_image_multi_kernel(SplitJobs jobs) {
     const SplitJob j = jobs.job[blockIdx.y];
-    if (j.pad_ & 1) {
-        const int lb = (j.pad_ >> 8) & 0xFFF, le = (j.pad_ >> 20) & 0xFFF, NG = j.K / 64;
+    const int fmt = j.format.bits();
+    if (fmt & H8_KVQ) {
+        const int lb = kvq_lo_begin(j.format), le = kvq_lo_end(j.format), NG = j.K / 64;
         const size_t total = ((size_t)(j.Nout / H_BN) * NG + (size_t)(le - lb) * (NG / 2)) * 512;
-        if (j.pad_ & 4) {   // the stream of W^T from W (K, ldw): one-term (lb == le)
+        if (fmt & KVQ_TRANSPOSED) {   // the stream of W^T from W (K, ldw): one-term (lb == le)
             for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
                 kvq_image_item<true>(j.W, j.img, j.Nout, j.K, j.ldw, lb, lb, i);
             return;
         }
-        if (j.pad_ & 64) {   // head-aligned column order (head dim 48; Nout a multiple of 384)
+        if (fmt & KVQ_HEAD48) {   // head-aligned column order (head dim 48; Nout a multiple of 384)
             for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
                 kvq_image_item<false, true>(j.W, j.img, j.Nout, j.K, j.ldw, lb, le, i);
             return;
@@ -272,20 +271,20 @@ __global__ void h8_image_multi_kernel(SplitJobs jobs) {
             kvq_image_item(j.W, j.img, j.Nout, j.K, j.ldw, lb, le, i);
         return;
     }
-    if (j.pad_ & 16) {   // 64-column tiles in the attention accumulator's k order (unpool_outproj_h8.hip)
+    if (fmt & H8_ATTN_ORDER) {   // 64-column tiles in the attention accumulator's k order (unpool_outproj_h8.hip)
         const size_t total = (size_t)(j.Nout / H_BN) * (j.K / 64) * 1024;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
             h8_image_item<64, true>(j.W, j.img, j.Nout, j.K, j.ldw, i);
         return;
     }
-    if (j.pad_ & 2) {   // 128-column tiles (gemm_h8_areg.hip); Nout padded up to whole tiles (the pad rows repeat the last row)
+    if (fmt & H8_W128) {   // 128-column tiles (gemm_h8_areg.hip); Nout padded up to whole tiles (the pad rows repeat the last row)
         const size_t total = (size_t)((j.Nout + 127) / 128) * (j.K / 64) * 2048;
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
             h8_image_item<128>(j.W, j.img, j.Nout, j.K, j.ldw, i);
         return;
     }
     const size_t total = (size_t)(j.Nout / H_BN) * (j.K / 64) * 1024;
-    if (j.pad_ & 32) {   // the "h6" stream: fp6 cross-term operands with block scales
+    if (fmt & H8_H6) {   // the "h6" stream: fp6 cross-term operands with block scales
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
             h8_image_item<64, false, true>(j.W, j.img, j.Nout, j.K, j.ldw, i);
         return;
@@ -1252,8 +1251,11 @@ size_t h8_image_bytes(int Nout, int K) { return (size_t)((Nout + H_BN - 1) / H_B
 
 int h8_image_multi_launch(const SplitJobs& jobs, hipStream_t st) {
     if (jobs.n <= 0) return 0;
-    for (int i = 0; i < jobs.n; ++i)
-        if (jobs.job[i].K % 64 || (!(jobs.job[i].pad_ & 2) && jobs.job[i].Nout % H_BN) || (jobs.job[i].ldw & 3)) return -9;
+    for (int i = 0; i < jobs.n; ++i) {
+        const SplitJob& j = jobs.job[i];
+        if (j.format.bits() == H8_INVALID) return -9;   // a kvq lo range that kvq_format could not pack
+        if (j.K % 64 || (!(j.format.bits() & H8_W128) && j.Nout % H_BN) || (j.ldw & 3)) return -9;
+    }
     hipLaunchKernelGGL(h8_image_multi_kernel, dim3(48, jobs.n), dim3(256), 0, st, jobs);
     return (int)hipGetLastError();
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include "weight_images.h"
 
 struct GemmArgs {
     const float* A;         // (B, rows, lda)
@@ -31,8 +32,8 @@ struct GemmArgs {
     // nseg columns goes to element ((b * nseg / hd + n / hd) * rows + row) * hd + n % hd: one contiguous (rows, hd)
     // slab per (sample, head) — what the attention kernels stream — instead of hd-wide pieces of (rows, nseg) rows.
     int hm_hd;
-    // A-stationary fp16 kernel only: image of the weights' LOW part fp16(W - fp16(W)) (same layout as w_img; split jobs with
-    // pad_ = 1): two-term fp16 weights, 2 MFMAs per product ("mixed" mode).  Null: one-term weights.
+    // A-stationary fp16 kernel only: image of the weights' LOW part fp16(W - fp16(W)) (same layout as w_img; F16_LO split
+    // jobs): two-term fp16 weights, 2 MFMAs per product ("mixed" mode).  Null: one-term weights.
     const void* w_img2;
     int lo_tiles;           // with w_img2: only the 128-column tiles [lo_begin, lo_tiles) have a lo part (lo_tiles 0: all)
     int lo_begin;
@@ -66,19 +67,18 @@ struct GemmArgs {
     int h8_rev;                // gemm_h8_astat.hip: blocks walk the row panels last to first (the producer wrote them first to last)
     // gemm_kvq_astat_kernel, head-major fp16 outputs at head dim 48 (feature_dim 384, 8 heads): the columns of every 384-column segment
     // (K, V, q) are dealt to its six 64-column tiles HEAD-ALIGNED — tile t = head t's 48 columns + the (t % 3)-th 16-column third of head
-    // 6 + t / 3 — by the stream builder (SplitJob::pad_ | 64; kvq_perm48_col); a wave then owns a head's whole (32 rows, 48) slab = 3 KiB
+    // 6 + t / 3 — by the stream builder (KVQ_HEAD48; kvq_perm48_col); a wave then owns a head's whole (32 rows, 48) slab = 3 KiB
     // of CONTIGUOUS head-major memory per tile, written as three 1 KiB stores through its LDS tile instead of as 32-byte pieces.  A
     // column's dot product does not depend on where in a tile it sits: the outputs are bit-identical to the plain order.
     int kvq_perm;
     // gemm_kvq_astat_kernel (training forward, round 6): also store the A operand the kernel forms, y16 = fp16(A * pro_a + pro_o), as an
     // fp16 tensor (B, rows, K) — the weight gradient of this very linear reads it back as its fp16 X operand (gemm_tn_f16.hip, DMA form)
     void* y16_out;
-    int h6;                    // gemm_h8_astat.hip (c_img == 2): the cross terms in fp6 with block scales; w_img is the h6 stream (SplitJob::pad_ 32)
+    int h6;                    // gemm_h8_astat.hip (c_img == 2): the cross terms in fp6 with block scales; w_img is the h6 stream (H8_H6)
     int h8_stagger, h8_pair;   // gemm_h8_astat.hip: start offset of every second block of a CU (set by its launcher)
 };
 
-struct SplitJob { const float* W; float* img; int Nout, K, ldw, pad_; };   // pad_ = 1 (fp16 images): the LOW part fp16(W - fp16(W)); 2: the same as fp8 x 2^19 in 64-k blocks; 8: hi | lo blocks interleaved per column tile; 4 (bf16 images): W is (K, ldw) and the image is of W^T; h8 images (h8_image_multi_launch): see gemm_h8_astat.hip
-struct SplitJobs { SplitJob job[96]; int n; };   // 3 KiB of kernel arguments
+// (SplitJob / SplitJobs and the formats a job names: weight_images.h)
 int gemm_row_tile(int rows);  // row-tile height the GEMM uses for `rows` rows per sample
 int gemm_f32_launch(const GemmArgs& g, hipStream_t st);
 // gemm_f32_dma.hip — LDS-DMA fast path of the same contract
@@ -106,7 +106,7 @@ struct ChainArgs {
     const float* part_ml;     // (B, H, nsplit, 64, 2)
     int nsplit, H;
     const float* w_stream;    // fp16 tiled images of pool.out_proj | mlp.0 | mlp.2 | unpool k|v, back to back
-    int two_term;             // the images carry hi | lo blocks per column tile (SplitJob::pad_ = 8): two-term weights (mixed mode)
+    int two_term;             // the images carry hi | lo blocks per column tile (F16_HI_LO): two-term weights (mixed mode)
     const float *b0, *b2, *bkv, *alpha;
     int act;
     const float *n1_scale_w, *n1_scale_b, *n1_bias_w, *n1_bias_b;
@@ -165,7 +165,7 @@ struct UnpoolH8Args {
     float* x;                 // (B, rows, C) fp32 residual stream, updated in place
     const void* q16;          // head-major fp16 q (B, H, rows, hd)
     const void* kv_img;       // kvh_image_launch: per (sample, head) the fp16 LDS image of the inducers' k | v
-    const void* w_img;        // h8 stream of out_proj.weight, 64-column tiles, attention k order (SplitJob::pad_ = 16)
+    const void* w_img;        // h8 stream of out_proj.weight, 64-column tiles, attention k order (H8_ATTN_ORDER)
     const float* bias;        // (C) or null
     float* stats;             // (B, rows / 128, 2, C) or null
     int B, rows, H;
@@ -246,11 +246,11 @@ int gemm_f16_astat_launch(const GemmArgs& g, hipStream_t st);
 size_t h8_image_bytes(int Nout, int K);   // Nout * K * 4 (Nout % 64 == 0)
 int h8_image_multi_launch(const SplitJobs& jobs, hipStream_t st);   // K % 64 == 0, Nout % 64 == 0, ldw % 4 == 0 per job
 bool gemm_h8_astat_supported(const GemmArgs& g);
-// kv_proj | q_proj of the mixed mode on the same structure: fp16 outputs, w_img = the stream of kvq image jobs (SplitJob::pad_ =
-// 1 | lo_begin << 8 | lo_end << 20, 64-column tiles with a second fp8 weight term); GemmArgs::lo_begin / lo_tiles in 64-column tiles
+// kv_proj | q_proj of the mixed mode on the same structure: fp16 outputs, w_img = the stream of kvq image jobs (kvq_format(lo_begin,
+// lo_end): 64-column tiles with a second fp8 weight term); GemmArgs::lo_begin / lo_tiles in 64-column tiles
 size_t kvq_image_bytes(int Nout, int K, int lo_cols);
 bool gemm_kvq_astat_supported(const GemmArgs& g);
-// head-aligned column order (GemmArgs::kvq_perm, SplitJob::pad_ | 64): head dim 48, both segments whole multiples of 384 columns
+// head-aligned column order (GemmArgs::kvq_perm, KVQ_HEAD48): head dim 48, both segments whole multiples of 384 columns
 bool kvq_perm48_ok(int hm_hd, int K, int n_first, int n_second);
 int gemm_kvq_astat_launch(const GemmArgs& g, hipStream_t st);
 // gemm_h8_astat_kernel with fp32 outputs: the training forward in h8 arithmetic (w_img = the h8 stream)
@@ -263,7 +263,7 @@ int gemm_h8_astat_launch(const GemmArgs& g, hipStream_t st);
 
 // gemm_h8_areg.hip — mixed mode's mlp.2 / out_proj in h8 arithmetic: A is an h8 activation image (a_img == 2: fp16 hi + fp8 lo,
 // written by gemm_h8_astat.hip with c_img == 2 or by the unpool attention with out_img == 2), W the 128-column-tile h8 stream
-// (SplitJob::pad_ = 2); residual / bias / statistics epilogue of the LDS-DMA kernels
+// (H8_W128); residual / bias / statistics epilogue of the LDS-DMA kernels
 size_t h8_w128_image_bytes(int Nout, int K);
 bool gemm_h8_areg_supported(const GemmArgs& g);
 int gemm_h8_areg_launch(const GemmArgs& g, hipStream_t st);

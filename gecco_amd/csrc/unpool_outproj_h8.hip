@@ -17,7 +17,7 @@
 //   * O^T holds, per lane, ONE query and head-dim indices 8 g + 4 h + e: v = O / l is split as hi = fp16(v), lo = fp8(2^14 (v -
 //     hi)) in place — no transpose: the k order of the stationary operand is whatever the accumulator gives (element e of
 //     fragment (k-step s, lane half h) is k = 16 s + 8 (e >> 2) + 4 h + (e & 3)), and the W image is written in the same order
-//     (h8_image_item<64, true>, SplitJob::pad_ = 16).
+//     (h8_image_item<64, true>, H8_ATTN_ORDER).
 //   * out_proj = gemm_h8_astat.hip's main loop (A W = Ah Wh + fp8(Ah 2^-3) fp8(2^16 Wl) + fp8(2^11 Al) fp8(2^5 W), h8_scales.h; 64-column tiles, W
 //     streamed through an LDS ring in consumption order).
 //   * epilogue per 64-column tile: the residual rows of the tile were fetched by LDS-DMA into a wave-private tile when the tile's
