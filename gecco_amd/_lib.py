@@ -244,6 +244,8 @@ SIGNATURES = {
     "gecco_ransac_workspace_bytes": (sz, [i, i, i]),
     "gecco_voxel_downsample_f32": (i, [vp, vp, fl, vp, vp, vp, vp, vp, vp, i, i, i, vp]),
     "gecco_voxel_workspace_bytes": (sz, [i, i]),
+    "gecco_dbscan_f32": (i, [vp, vp, vp, vp, vp, vp, vp, i, i, fl, i, i, vp]),
+    "gecco_dbscan_workspace_bytes": (sz, [i, i, i]),
     "gecco_convnext_stem_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),
     "gecco_convnext_dwconv_ln_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),
     "gecco_convnext_ln_patch2_f32": (i, [vp] * 4 + [i, i, i, i, fl, vp]),

@@ -1,5 +1,5 @@
 // C ABI of libgecco_hip.so, part 4 of 4: point-cloud operators and metrics (distance matrix, Chamfer, set metrics, EMD,
-// Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, RANSAC registration, voxel grid).
+// Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, RANSAC registration, voxel grid, DBSCAN).
 #include "api_common.h"
 
 using namespace gecco_api;
@@ -312,6 +312,25 @@ int gecco_voxel_downsample_f32(const float* points, const float* origin, float v
                                 (hipStream_t)stream);
     if (rc == -3) return fail(-2, "voxel_downsample: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
     TRY(rc, "voxel_downsample");
+    return 0;
+}
+
+// DBSCAN clustering (dbscan.hip).  eps2 = fp32(eps * eps) from the caller; count, rounds nullable
+size_t gecco_dbscan_workspace_bytes(int B, int N, int max_rounds) {
+    if (B < 1 || N < 1 || max_rounds < 0 || max_rounds > GECCO_DBSCAN_MAX_ROUNDS) return 0;
+    return GECCO_DBSCAN_WORKSPACE_BYTES(B, N, max_rounds);
+}
+int gecco_dbscan_f32(const float* points, int32_t* labels, int32_t* n_clusters, int32_t* count, int32_t* rounds, int32_t* status, void* ws,
+                     int B, int N, float eps2, int min_points, int max_rounds, void* stream) {
+    if (!points || !labels || !n_clusters || !status || !ws) return fail(-1, "dbscan: null argument");
+    if (B < 1 || N < 1) return fail(-2, "dbscan: B = %d, N = %d must both be >= 1", B, N);
+    if (!(eps2 > 0.f) || !(eps2 <= 3.402823466e38f)) return fail(-2, "dbscan: eps2 = %g must be a finite number > 0", (double)eps2);
+    if (min_points < 1) return fail(-2, "dbscan: min_points = %d must be >= 1", min_points);
+    if (max_rounds < 0 || max_rounds > GECCO_DBSCAN_MAX_ROUNDS)
+        return fail(-2, "dbscan: max_rounds = %d is not in 0 .. %d", max_rounds, GECCO_DBSCAN_MAX_ROUNDS);
+    const int rc = dbscan_launch(points, labels, n_clusters, count, rounds, status, ws, B, N, eps2, min_points, max_rounds, (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "dbscan: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
+    TRY(rc, "dbscan");
     return 0;
 }
 

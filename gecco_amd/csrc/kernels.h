@@ -533,6 +533,11 @@ int ransac_launch(const float* source, const float* target, const int* corr, flo
 // GECCO_VOXEL_WORKSPACE_BYTES(B, N); V = max_voxels rows per cloud.  -2: sizes out of range, -3: a grid would pass 2^31 - 1 workgroups
 int voxel_launch(const float* points, const float* origin, float voxel_size, float* centroids, int* first, int* count, int* inverse,
                  int* n_voxels, void* ws, int B, int N, int V, hipStream_t st);
+// dbscan.hip — DBSCAN clustering (definition: gecco_dbscan_f32).  eps2 = fp32(eps * eps); count, rounds nullable; ws of
+// GECCO_DBSCAN_WORKSPACE_BYTES(B, N, R); 1 + 2 R + 2 launches for R = max_rounds.  -2: arguments out of range, -3: the grid would pass
+// 2^31 - 1 workgroups
+int dbscan_launch(const float* points, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
+                  int min_points, int R, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

@@ -3,7 +3,7 @@
 lists (csrc/normals.hip, gecco_normals_f32), voxel-grid downsampling with attribute pooling (csrc/voxel.hip,
 gecco_voxel_downsample_f32), rigid ICP registration, point-to-point and point-to-plane (csrc/icp.hip, gecco_icp_f32), FPFH
 descriptors with nearest-neighbour matching in feature space (csrc/fpfh.hip, gecco_fpfh_f32, gecco_feature_nn_f32), and RANSAC
-registration from correspondences (csrc/ransac.hip, gecco_ransac_f32).
+registration from correspondences (csrc/ransac.hip, gecco_ransac_f32), and DBSCAN clustering (csrc/dbscan.hip, gecco_dbscan_f32).
 
 The reference reduces a dense cloud to a fixed size by random permutation (gecco-jax data/torch_shapenet.py:20-21, data/taskonomy.py:84),
 which keeps density clumps and loses thin structure.  `farthest_point_sample` is the well-spread cut: from a start point, each next point
@@ -198,7 +198,29 @@ correspondences), 0 without a winner; inlier_rmse = sqrt(sum / n); status 0 foun
 inliers[i] = corr[i] for the final inliers, -1 elsewhere.  Three launches whatever the data, no atomics, no workgroup waits on another,
 no allocation inside the library and no host synchronisation: a call can be captured in a hipGraph.  One seed serves every cloud: the
 outputs are the same bits run to run, in any batch position and however the hypotheses are split across workgroups.
-HIP tensors only: there is no CPU fallback (`voxel_pool`, plain torch, runs on any device)."""
+
+DBSCAN clustering (`cluster_dbscan`, `cluster_sizes`).  "Which points belong together": the step Open3D (`cluster_dbscan`), PCL
+(`EuclideanClusterExtraction`, the same thing with every point a core point) and scikit-learn (`DBSCAN`) put behind the voxel filter
+and the outlier filter, before a registration per object.  The route without it is an N x N adjacency matrix (`cdist <= eps`: 10 GB of
+booleans at 100 000 points) and a host loop over it.  Definition (include/gecco_hip.h; tests/_dbscan_ref.py restates it in numpy
+float32).  Per cloud, with eps2 = fp32(eps * eps) and min_points >= 1:
+    dist2      the spelling of `knn`: (dx dx + dy dy) + dz dz, every operation rounded to fp32, none contracted, NaN -> +inf.  It is
+               bitwise symmetric; a point with a non-finite coordinate is nobody's neighbour, not even its own
+    neighbour  dist2(i, j) <= eps2, inclusive; a finite point is its own neighbour.  count_i = the number of neighbours of i
+    core       count_i >= min_points.  The core points form a graph with an edge wherever two of them are neighbours; root_i = the
+               lowest index of i's connected component; a component's cluster id is the rank of its root among all roots, ascending
+    border     a non-core point with a core neighbour takes the lowest cluster id among its core neighbours
+    noise      everything else: -1
+The result is unique and equals Open3D's and scikit-learn's label for label (both visit points in index order and finish a cluster
+before they open the next).  Points x = 0, 1, 2, 10, 11, 5.5 on a line, eps = 1, min_points = 2: labels [0, 0, 0, 1, 1, -1]; with
+min_points = 3 only point 1 is core and the labels are [0, 0, 0, -1, -1, -1].  1 + 2 max_rounds + 2 launches whatever the data: a
+count scan, max_rounds rounds of hook (a scan: Shiloach-Vishkin minimum hooking on a forest of stars, integer atomicMin) + compress
+(pointer chasing), a border scan and one labelling workgroup per cloud; the scans are `knn`'s loop.  A round that hooks nothing has
+found the fixed point (`rounds` counts it, `status` 0) and the cloud's later workgroups return at once; the default limit
+ceil(log2 max(N, 2)) + 2 cannot be exceeded; a cloud that runs out of an explicit limit has status 1 and labels that refine the true
+clusters.  In every launch what is read is written by no thread of that launch, so labels, rounds and status are the same bits run to
+run and in any batch position, also at the limit; no float atomics, no host synchronisation.
+HIP tensors only: there is no CPU fallback (`voxel_pool` and `cluster_sizes`, plain torch, run on any device)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -226,6 +248,7 @@ FPFH_BINS = 33                   # GECCO_FPFH_BINS
 FEATURE_MAX_DIM = 64             # GECCO_FEATURE_MAX_DIM
 RANSAC_MAX_HYPOTHESES = 1 << 24  # GECCO_RANSAC_MAX_HYPOTHESES
 RANSAC_MAX_REFINE = 8            # GECCO_RANSAC_MAX_REFINE
+DBSCAN_MAX_ROUNDS = 64            # GECCO_DBSCAN_MAX_ROUNDS
 
 
 def _fps_workspace_bytes(B: int, N: int) -> int:
@@ -925,3 +948,84 @@ def ransac_registration(source: Tensor, target: Tensor, correspondences: Tensor,
     out = _unbatch([T, fit, rmse, npairs.long(), best.long(), status.long(), None if inl is None else inl.long()], single)
     hyp = tuple(_unbatch([tri.long(), cnt.long(), sums], single)) if return_hypotheses else None
     return RANSACResult(*out, hyp)
+
+
+class DBSCANResult(NamedTuple):
+    """What `cluster_dbscan` returns (module docstring: the definition).  status 0: the fixed point was reached, 1: the round limit was
+    hit and the labels describe a refinement of the true clusters."""
+    labels: Tensor          # int64 (B, N): the cluster of each point, -1 for noise
+    n_clusters: Tensor      # int64 (B,)
+    core: Tensor            # bool (B, N): counts >= min_points
+    status: Tensor          # int64 (B,)
+    rounds: Tensor          # int64 (B,): hook + compress rounds run, the one that found the fixed point included
+    counts: Tensor | None   # int64 (B, N): the neighbours of each point within eps, itself included
+
+
+def _dbscan_workspace_bytes(B: int, N: int, R: int) -> int:
+    """GECCO_DBSCAN_WORKSPACE_BYTES(B, N, R)"""
+    return (4 * B * (5 * N + R) + 7) & ~7
+
+
+def dbscan_default_rounds(N: int) -> int:
+    """ceil(log2 max(N, 2)) + 2: the round limit `cluster_dbscan` takes by default, which no cloud of N points can exceed"""
+    return (max(int(N), 2) - 1).bit_length() + 2
+
+
+def cluster_dbscan(points: Tensor, eps: float, min_points: int = 10, max_rounds: int | None = None,
+                   return_counts: bool = False) -> DBSCANResult:
+    """DBSCAN clusters of each cloud (module docstring: the definition): Open3D's `cluster_dbscan`, scikit-learn's `DBSCAN`, and with
+    min_points = 1 PCL's Euclidean cluster extraction, label for label.  points (B, N, 3) or (N, 3) on the HIP device, any float dtype
+    and strides (computed on an fp32 contiguous copy); eps: the neighbourhood radius, a finite fp32 number > 0 whose square is one too
+    (the bound dist2 <= fp32(eps * eps) is inclusive); min_points >= 1: the neighbours, itself included, that make a point a core
+    point.  max_rounds in 0 .. DBSCAN_MAX_ROUNDS: the hook + compress rounds to launch; None takes ceil(log2 max(N, 2)) + 2, which
+    cannot be exceeded, so status 1 only ever follows an explicit limit.  Returns a DBSCANResult: labels int64 (B, N) with -1 for noise,
+    n_clusters int64 (B,), core bool (B, N), status and rounds int64 (B,), counts int64 (B, N) with return_counts and None without; for
+    a single cloud the batch dimension is dropped.  The call makes 1 + 2 max_rounds + 2 launches and never synchronises: it can be
+    captured in a hipGraph.  ValueError, before any device call, for bad shapes, an eps that is not a finite fp32 number > 0 with a
+    finite square > 0, min_points or max_rounds that are not integers or out of range; GeccoHipError for CPU tensors.  No gradient:
+    labels."""
+    p, single = _cloud(points)
+    B, N, _ = p.shape
+    if B < 1 or N < 1:
+        raise ValueError("empty batch or cloud")
+    e = _positive_f32(eps, "eps", (TypeError, ValueError, OverflowError))
+    eps2 = C.c_float(e * e).value   # exact in double, rounded to fp32 once
+    if not (math.isfinite(eps2) and eps2 > 0):
+        raise ValueError(f"eps = {eps!r}: its square must be a finite fp32 number > 0")
+    min_points = _integer(min_points, "min_points")
+    if min_points < 1:
+        raise ValueError(f"min_points = {min_points} must be >= 1")
+    R = dbscan_default_rounds(N) if max_rounds is None else _integer(max_rounds, "max_rounds")
+    if not 0 <= R <= DBSCAN_MAX_ROUNDS:
+        raise ValueError(f"max_rounds = {R} is not in 0 .. {DBSCAN_MAX_ROUNDS}")
+    x, px = _f32(p)
+    dev = x.device
+    labels = torch.empty(B, N, device=dev, dtype=torch.int32)
+    ncl = torch.empty(B, device=dev, dtype=torch.int32)
+    cnt = torch.empty(B, N, device=dev, dtype=torch.int32)   # always: `core` comes from it
+    rounds = torch.empty(B, device=dev, dtype=torch.int32)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    ws = torch.empty(_dbscan_workspace_bytes(B, N, R), device=dev, dtype=torch.uint8)   # written by the library before it is read
+    _lib.check(_lib.load().gecco_dbscan_f32(px, _vp(labels), _vp(ncl), _vp(cnt), _vp(rounds), _vp(status), _vp(ws), B, N, eps2, min_points,
+                                            R, _stream()), "gecco_dbscan_f32")
+    out = [labels.long(), ncl.long(), cnt >= min_points, status.long(), rounds.long(), cnt.long() if return_counts else None]
+    return DBSCANResult(*_unbatch(out, single))
+
+
+def cluster_sizes(labels: Tensor, n_clusters) -> Tensor:
+    """The number of points of each cluster of `cluster_dbscan`: labels (B, N) or (N,), integers with -1 for noise -> int64 (B, C) or
+    (C,), a `bincount` per cloud, which is what PCL's min / max cluster size filter needs.  n_clusters: C as an int (use it inside a
+    graph), or the n_clusters tensor, which is read on the host (C = max(n_clusters.max(), 1)); columns at or after a cloud's own
+    n_clusters are 0, labels outside [0, C) are skipped.  Plain torch on any device."""
+    if not isinstance(labels, Tensor) or labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool or \
+            labels.dim() not in (1, 2):
+        raise ValueError("labels must be an integer tensor of shape (B, N) or (N,)")
+    single = labels.dim() == 1
+    lab = (labels[None] if single else labels).long()
+    Cn = max(int(n_clusters.max()), 1) if isinstance(n_clusters, Tensor) else _integer(n_clusters, "n_clusters")
+    if Cn < 1:
+        raise ValueError(f"n_clusters = {Cn} must be >= 1")
+    B = lab.shape[0]
+    rows = torch.where((lab >= 0) & (lab < Cn), lab, Cn) + (Cn + 1) * torch.arange(B, device=lab.device)[:, None]   # column C: skipped
+    out = torch.bincount(rows.reshape(-1), minlength=B * (Cn + 1)).view(B, Cn + 1)[:, :Cn]
+    return out[0] if single else out

@@ -1231,6 +1231,54 @@ size_t gecco_ransac_workspace_bytes(int B, int M, int hypotheses);
 int gecco_voxel_downsample_f32(const float* points, const float* origin, float voxel_size, float* centroids, int32_t* first, int32_t* count,
                                int32_t* inverse, int32_t* n_voxels, void* workspace, int B, int N, int max_voxels, void* stream);
 size_t gecco_voxel_workspace_bytes(int B, int N);
+/* DBSCAN clustering of 3-D clouds (csrc/dbscan.hip): the cluster of every point of points (B, N, 3), "which points belong together",
+ * the step Open3D (cluster_dbscan), PCL (EuclideanClusterExtraction: the same thing with min_points = 1, every point a core point) and
+ * scikit-learn (DBSCAN) put behind the voxel filter and the outlier filter.  The reference has nothing of the kind and this entry
+ * replaces nothing in it; without it the route is an N x N adjacency matrix (cdist <= eps: 10 GB of booleans at 100 000 points) and a
+ * host loop of masked row minima.  tests/_dbscan_ref.py restates the definition in numpy float32.  Per cloud, with eps2 a finite fp32
+ * number > 0 (the caller's fp32(eps * eps), formed once on the host as the radius2 of gecco_normals_f32 is) and min_points >= 1:
+ *     dist2(i, j)  (dx dx + dy dy) + dz dz on the coordinate differences, every operation rounded to fp32 and none contracted into an
+ *                  FMA, a NaN replaced by +inf: the spelling of gecco_knn_f32.  It is bitwise symmetric in i and j.  A point with a
+ *                  non-finite coordinate is nobody's neighbour, not even its own
+ *     neighbour    dist2(i, j) <= eps2, the bound INCLUSIVE; a finite point is its own neighbour
+ *     core         count_i = the number of neighbours of i (count, (B, N));  i is a core point when count_i >= min_points
+ *     clusters     the core points form a graph with an edge wherever two of them are neighbours;  root_i of a core point is the
+ *                  lowest index of its connected component;  the cluster id of a component is the rank of its root among all roots,
+ *                  ascending: 0 .. C - 1 (n_clusters = C)
+ *     border       a non-core point with at least one core neighbour takes the LOWEST cluster id among its core neighbours, which is
+ *                  the cluster of the lowest root among them
+ *     noise        everything else: label -1
+ * This is the labelling of Open3D's cluster_dbscan and scikit-learn's DBSCAN, index for index: both visit the points in index order
+ * and finish cluster c before they open c + 1, so clusters are numbered by their lowest core index and a border point keeps the first
+ * cluster that reached it.  The result is unique: no order of evaluation enters it.
+ * Worked example: points x = 0, 1, 2, 10, 11, 5.5 on a line, eps2 = 1, min_points = 2: counts 2, 3, 2, 2, 2, 1; labels 0, 0, 0, 1,
+ * 1, -1.  With min_points = 3 only point 1 is core: labels 0, 0, 0, -1, -1, -1 (points 0 and 2 are border points).
+ * 1 + 2 max_rounds + 2 launches whatever the data: count (count_i, the core flag, parent_i = i); max_rounds rounds of hook + compress
+ * (Shiloach-Vishkin with minimum hooking on a forest of stars: every core i takes m_i = the minimum parent over its core neighbours
+ * and, when m_i < parent_i, does an integer atomicMin of m_i into hook[parent_i]; then every point chases hook from its parent to a
+ * fixed point); border + roots; label (one workgroup per cloud, an exclusive prefix count of the roots over the point index).  A round
+ * that hooked nothing has found the fixed point: rounds (B) = the number of rounds run, that one included, status (B) = 0, and the
+ * cloud's later workgroups return at once.  A cloud whose every round hooked has rounds = max_rounds and status = 1: its labels
+ * describe the forest as it stood, a refinement of the true clusters (max_rounds = 0: every core point its own cluster).  ceil(log2 N)
+ * + 2 rounds cannot be exceeded: of two joined stars the one with the higher root hooks, so at most ceil(log2 N) rounds change the
+ * forest, one more sees no change and one is slack.  In every launch a buffer that is read is written by no thread of that launch
+ * (parents and hooks ping-pong; the atomicMin target and the round's flag are written only), so the state after a round is a pure
+ * function of the state before it: labels, rounds and status are the same bits run to run and in any batch position, also for a run
+ * that hit the limit.  No float atomics, no thread waits on another, no allocation, no host synchronisation: the call can be captured
+ * in a graph.
+ * labels (B, N), n_clusters (B) and status (B) int32 are required; count (B, N) and rounds (B) int32 may each be NULL; every element of
+ * a given output is written.  ws: gecco_dbscan_workspace_bytes(B, N, max_rounds) = GECCO_DBSCAN_WORKSPACE_BYTES(B, N, max_rounds)
+ * bytes, 4-byte aligned = 20 B N (two parent buffers, two hook buffers, the roots) + 4 B max_rounds (the round flags), rounded up to
+ * 8; required; never read before the call has written it.  Negative return (and gecco_last_error) before anything is enqueued for:
+ * null points / labels / n_clusters / status / ws, B or N < 1, an eps2 that is not a finite number > 0, min_points < 1, max_rounds
+ * outside 0 .. GECCO_DBSCAN_MAX_ROUNDS, a grid above 2^31 - 1 workgroups.  Asynchronous on `stream`.  gecco_dbscan_workspace_bytes
+ * needs no GPU and returns 0 for arguments out of range. */
+#define GECCO_DBSCAN_MAX_ROUNDS 64
+#define GECCO_DBSCAN_WORKSPACE_BYTES(B, N, R) \
+    (((size_t)4 * (size_t)(B) * (5 * (size_t)(N) + (size_t)(R)) + 7) & ~(size_t)7)
+int gecco_dbscan_f32(const float* points, int32_t* labels, int32_t* n_clusters, int32_t* count, int32_t* rounds, int32_t* status, void* ws,
+                     int B, int N, float eps2, int min_points, int max_rounds, void* stream);
+size_t gecco_dbscan_workspace_bytes(int B, int N, int max_rounds);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
