@@ -242,6 +242,8 @@ SIGNATURES = {
     "gecco_feature_nn_workspace_bytes": (sz, [i, i, i]),
     "gecco_ransac_f32": (i, [vp, vp, vp, fl, db, i, i, u64] + [vp] * 12 + [i, i, i, vp]),
     "gecco_ransac_workspace_bytes": (sz, [i, i, i]),
+    "gecco_plane_ransac_f32": (i, [vp, vp, fl, i, i, u64, vp, db, i] + [vp] * 15 + [i, i, vp]),
+    "gecco_plane_ransac_workspace_bytes": (sz, [i, i, i]),
     "gecco_voxel_downsample_f32": (i, [vp, vp, fl, vp, vp, vp, vp, vp, vp, i, i, i, vp]),
     "gecco_voxel_workspace_bytes": (sz, [i, i]),
     "gecco_dbscan_f32": (i, [vp, vp, vp, vp, vp, vp, vp, i, i, fl, i, i, vp]),

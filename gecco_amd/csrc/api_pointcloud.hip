@@ -295,6 +295,34 @@ int gecco_ransac_f32(const float* source, const float* target, const int32_t* co
     return 0;
 }
 
+// RANSAC plane segmentation (plane.hip).  mask, axis, viewpoint, candidates, inliers and the four hyp_ outputs nullable
+size_t gecco_plane_ransac_workspace_bytes(int B, int N, int hypotheses) {
+    if (B < 1 || N < 1 || hypotheses < 1 || hypotheses > GECCO_PLANE_RANSAC_MAX_HYPOTHESES) return 0;
+    return GECCO_PLANE_RANSAC_WORKSPACE_BYTES(B, N, hypotheses);
+}
+int gecco_plane_ransac_f32(const float* points, const uint8_t* mask, float r, int hypotheses, int refine_passes, uint64_t seed,
+                           const double* axis, double cos2, int min_inliers, const float* viewpoint, const double* candidates,
+                           double* plane, float* fitness, float* inlier_rmse, int32_t* n_points, int32_t* n_inliers, int32_t* best,
+                           int32_t* status, uint8_t* inliers, int32_t* hyp_triple, float* hyp_plane, int32_t* hyp_count, double* hyp_sum,
+                           void* ws, int B, int N, void* stream) {
+    if (!points || !plane || !fitness || !inlier_rmse || !n_points || !n_inliers || !best || !status || !ws)
+        return fail(-1, "plane_ransac: null argument");
+    if (B < 1 || N < 1) return fail(-2, "plane_ransac: B = %d, N = %d must both be >= 1", B, N);
+    if (hypotheses < 1 || hypotheses > GECCO_PLANE_RANSAC_MAX_HYPOTHESES)
+        return fail(-2, "plane_ransac: hypotheses = %d is not in 1 .. %d", hypotheses, GECCO_PLANE_RANSAC_MAX_HYPOTHESES);
+    if (refine_passes < 0 || refine_passes > GECCO_PLANE_RANSAC_MAX_REFINE)
+        return fail(-2, "plane_ransac: refine_passes = %d is not in 0 .. %d", refine_passes, GECCO_PLANE_RANSAC_MAX_REFINE);
+    if (!(r > 0.f) || !(r <= 3.402823466e38f)) return fail(-2, "plane_ransac: r = %g must be a finite number > 0", (double)r);
+    if (min_inliers < 0) return fail(-2, "plane_ransac: min_inliers = %d must be >= 0", min_inliers);
+    if (axis && (!(cos2 >= 0.0) || !(cos2 <= 1.0))) return fail(-2, "plane_ransac: cos2 = %g is not in 0 .. 1", cos2);
+    const int rc = plane_ransac_launch(points, mask, r, hypotheses, refine_passes, (unsigned long long)seed, axis, cos2, min_inliers, viewpoint,
+                                       candidates, plane, fitness, inlier_rmse, n_points, n_inliers, best, status, inliers, hyp_triple,
+                                       hyp_plane, hyp_count, hyp_sum, ws, B, N, (hipStream_t)stream);
+    if (rc == -3) return fail(-2, "plane_ransac: the grid for B = %d, hypotheses = %d passes 2^31 - 1 workgroups", B, hypotheses);
+    TRY(rc, "plane_ransac");
+    return 0;
+}
+
 // voxel-grid downsampling (voxel.hip).  origin null: 0; first, count, inverse nullable
 size_t gecco_voxel_workspace_bytes(int B, int N) {
     if (B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return 0;

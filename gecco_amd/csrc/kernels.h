@@ -529,6 +529,13 @@ int ransac_launch(const float* source, const float* target, const int* corr, flo
                   unsigned long long seed, double* transformation, float* fitness, float* inlier_rmse, int* n_pairs, int* best, int* status,
                   int* inliers, int* hyp_triple, int* hyp_count, double* hyp_sum, const double* candidates, void* ws, int B, int M, int N,
                   hipStream_t st);
+// plane.hip — RANSAC plane segmentation (definition: gecco_plane_ransac_f32): three launches.  cos2 = cos(max_angle)^2, read with axis
+// only; mask, axis, viewpoint, candidates, inliers, hyp_triple, hyp_plane, hyp_count, hyp_sum nullable; ws of
+// GECCO_PLANE_RANSAC_WORKSPACE_BYTES(B, N, H).  -2: arguments out of range, -3: a grid would pass 2^31 - 1 workgroups
+int plane_ransac_launch(const float* points, const unsigned char* mask, float r, int H, int refine_passes, unsigned long long seed,
+                        const double* axis, double cos2, int min_inliers, const float* viewpoint, const double* candidates, double* plane,
+                        float* fitness, float* inlier_rmse, int* n_points, int* n_inliers, int* best, int* status, unsigned char* inliers,
+                        int* hyp_triple, float* hyp_plane, int* hyp_count, double* hyp_sum, void* ws, int B, int N, hipStream_t st);
 // voxel.hip — voxel-grid downsampling (definition: gecco_voxel_downsample_f32).  origin, first, count, inverse nullable; ws of
 // GECCO_VOXEL_WORKSPACE_BYTES(B, N); V = max_voxels rows per cloud.  -2: sizes out of range, -3: a grid would pass 2^31 - 1 workgroups
 int voxel_launch(const float* points, const float* origin, float voxel_size, float* centroids, int* first, int* count, int* inverse,

@@ -1185,6 +1185,79 @@ int gecco_ransac_f32(const float* source, const float* target, const int32_t* co
                      int32_t* best, int32_t* status, int32_t* inliers, int32_t* hyp_triple, int32_t* hyp_count, double* hyp_sum,
                      const double* candidates, void* ws, int B, int M, int N, void* stream);
 size_t gecco_ransac_workspace_bytes(int B, int M, int hypotheses);
+/* RANSAC plane segmentation (csrc/plane.hip): the dominant plane of each cloud of points (B, N, 3) and the points on it, the step
+ * between the filters and gecco_dbscan_f32 (a support plane joins every object standing on it into one cluster).  It is Open3D's
+ * segment_plane and PCL's SACSegmentation with SACMODEL_PLANE (with `axis`: SACMODEL_PERPENDICULAR_PLANE) at a fixed number of
+ * hypotheses.  The reference has nothing of the kind; without this entry the route is a host loop of randint triples, cross products,
+ * an (H, N) distance matrix in chunks, argmax and eigh.  tests/_plane_ref.py restates the definition in numpy.  Each cloud is
+ * independent and one seed serves every cloud, so a cloud's result does not depend on its batch position.  r is the distance
+ * threshold, an fp32 value.
+ *     usable     the indices i in ascending order whose three coordinates are finite and, with mask (B, N) uint8, whose mask[i] != 0.
+ *                K = their number (n_points); c0 = double(the first usable point).  Every later step streams the packed list
+ *                (x, y, z, bits of i), 16 bytes per point
+ *     draw       hypothesis h = 0 .. H - 1 draws three distinct usable points a0, a1, a2 with the generator of gecco_ransac_f32 (its
+ *                `draw` paragraph, with K the number of usable points): the same bits for the same seed, h and K
+ *     checks     in fp64 on the fp32 coordinates, every operation rounded and none contracted; no division and no root
+ *                  1  degenerate triangle: check 1 of gecco_ransac_f32 on the three points.  Code 1
+ *                  2  only with axis (B, 3) fp64: n_raw = e1 x e2 (e1 = p_a1 - p_a0, e2 = p_a2 - p_a0, each component a difference
+ *                     of two rounded products); rejected when (n_raw . a)^2 < (cos2 |n_raw|^2) |a|^2 with a = axis[b],
+ *                     n_raw . a = (n0 a0 + n1 a1) + n2 a2 and cos2 = cos(max_angle)^2, formed in double by the caller: the angle
+ *                     between the normal and the axis, either sense, is above max_angle.  Code 2
+ *     plane      of a hypothesis: the fp32 pair (nf, cf).  n = n_raw / sqrt(|n_raw|^2) in fp64, nf = fp32(n); c = double(p_a0) and
+ *                cf = p_a0 itself: exact, so no d = -n . p cancellation happens on a cloud far from the origin
+ *     candidates (B, H, 4) fp64 or NULL.  Given, [a, b, c, d] = candidates[b, h] replaces the draw and check 1: a non-finite entry or
+ *                an |abc|^2 that is zero or not finite gets code 4; check 2 applies to n_raw = abc; s = 1 / sqrt(|abc|^2),
+ *                n = abc s, c = -(d s) n, nf = fp32(n), cf = fp32(c); hyp_triple is -1
+ *     distance   t = ((px - cx) nx + (py - cy) ny) + (pz - cz) nz on (nf, cf), every operation rounded to fp32 and none contracted;
+ *                p is an inlier iff |t| <= r, so a NaN is never an inlier
+ *     score      count = the number of inliers among the K usable points, sum = the fp64 sum of double(t) double(t) (exact
+ *                products) over them, accumulated SEQUENTIALLY in list order (so that it can be restated bit for bit given (nf, cf))
+ *                hyp_triple (B, H, 3): the drawn triple;  hyp_plane (B, H, 6) fp32: the (nf, cf) scored, zeros for a rejected
+ *                hypothesis;  hyp_count (B, H): count, or -code;  hyp_sum (B, H): sum, or +inf for a rejected hypothesis.  K < 3:
+ *                every hypothesis has triple -1, count -1, sum +inf
+ *     select     the winner is the hypothesis with code 0 and count >= max(3, min_inliers) that is best under (count descending,
+ *                then sum ascending, then h ascending): the total order of gecco_ransac_f32, so neither the shape of the reduction
+ *                nor the way the hypotheses fall into workgroups can change it.  best = its h, or -1
+ *     refit      refine_passes times, 0 <= refine_passes <= GECCO_PLANE_RANSAC_MAX_REFINE, on the inliers of the current plane
+ *                (fp32(n), fp32(c)): the fp64 sums about c0 of 1, t^2, d = double(p) - c0 and the six distinct entries of d d^T
+ *                (products rounded, none contracted), each thread over its strided points, the wave by a fixed shuffle tree, the waves
+ *                in order.  C = S / n - m m^T with m the mean of d, scaled by its largest magnitude; 8 cyclic Jacobi sweeps over
+ *                (0, 1), (0, 2), (1, 2) with the guarded rotation of gecco_icp_f32's step 5; the eigenvector of the smallest
+ *                eigenvalue (the lowest index among equals), normalised, is the new n and c0 + m the new c.  A pass with fewer than 3
+ *                inliers or a result that is not finite leaves the plane unchanged and ends the refits.  The refit is ALWAYS
+ *                accepted, as in gecco_ransac_f32
+ *     final      the last evaluation under (fp32(n), fp32(c)) gives inliers (B, N) uint8 (1 for an inlier, 0 elsewhere, unusable
+ *                points included), n_inliers, fitness = fp32(n_inliers / K) and inlier_rmse = fp32(sqrt(sum / n_inliers))
+ *     plane      (B, 4) fp64 [a, b, c, d]: the unit normal n in fp64 and d = -((a cx + b cy) + c cz) with c the fp64 point above.
+ *                Sign, the rule of gecco_normals_f32 in fp64: with viewpoint (B, 3) fp32, n . (v - c) >= 0; without, the component
+ *                of largest magnitude is positive, the lowest axis among equal magnitudes
+ *     status     0 found;  1 no hypothesis reached the inlier bar: plane = [0, 0, 1, 0], inliers all 0, n_inliers, fitness and rmse
+ *                0, best -1;  2 K < 3: the same outputs
+ * Every element of every given output is written.  mask, axis, viewpoint, candidates, inliers, hyp_triple, hyp_plane, hyp_count and
+ * hyp_sum may each be NULL.  Three launches whatever the data: the compaction (one workgroup per cloud, an ordered scan); the
+ * hypothesis kernel (a workgroup of 256 threads per GECCO_PLANE_RANSAC_BLOCK_HYPOTHESES consecutive hypotheses of a cloud: draw and
+ * checks for four hypotheses per thread, the survivors compacted in h order in LDS, one thread per survivor scoring against the list
+ * streamed through LDS tiles, then the workgroup's own winner under the total order: ONE 16-byte record per workgroup); select + refit
+ * (one workgroup per cloud).  No atomics, no workgroup waits on another, no allocation and no host synchronisation: the call can be
+ * captured in a graph.  The outputs are the same bits run to run, in any batch position and however H is split across workgroups.
+ * ws: gecco_plane_ransac_workspace_bytes(B, N, hypotheses) = GECCO_PLANE_RANSAC_WORKSPACE_BYTES(B, N, H) bytes, 16-byte aligned;
+ * required; never read before it is written.  Negative return (and gecco_last_error) before anything is enqueued for: a null points /
+ * required output / ws, non-positive sizes, hypotheses outside 1 .. GECCO_PLANE_RANSAC_MAX_HYPOTHESES, r not a finite number > 0,
+ * refine_passes out of range, min_inliers < 0, cos2 outside [0, 1] or NaN when axis is given, a grid above 2^31 - 1 workgroups.
+ * gecco_plane_ransac_workspace_bytes needs no GPU and returns 0 for arguments out of range. */
+#define GECCO_PLANE_RANSAC_MAX_HYPOTHESES (1 << 24)
+#define GECCO_PLANE_RANSAC_MAX_REFINE 8
+#define GECCO_PLANE_RANSAC_BLOCK_HYPOTHESES 1024
+#define GECCO_PLANE_RANSAC_WORKSPACE_BYTES(B, N, H)                                                                           \
+    ((size_t)16 * (size_t)(B) * (size_t)(N) +                                                                                 \
+     (size_t)16 * (size_t)(B) * (((size_t)(H) + GECCO_PLANE_RANSAC_BLOCK_HYPOTHESES - 1) / GECCO_PLANE_RANSAC_BLOCK_HYPOTHESES) + \
+     (size_t)16 * (size_t)(B))
+int gecco_plane_ransac_f32(const float* points, const uint8_t* mask, float r, int hypotheses, int refine_passes, uint64_t seed,
+                           const double* axis, double cos2, int min_inliers, const float* viewpoint, const double* candidates,
+                           double* plane, float* fitness, float* inlier_rmse, int32_t* n_points, int32_t* n_inliers, int32_t* best,
+                           int32_t* status, uint8_t* inliers, int32_t* hyp_triple, float* hyp_plane, int32_t* hyp_count, double* hyp_sum,
+                           void* ws, int B, int N, void* stream);
+size_t gecco_plane_ransac_workspace_bytes(int B, int N, int hypotheses);
 /* Voxel-grid downsampling of 3-D clouds (csrc/voxel.hip): one output point per occupied cell of a regular grid of edge voxel_size, at
  * the centroid of the points of points (B, N, 3) that fall in the cell, with the point-to-voxel map.  What PCL and Open3D put before
  * the neighbour search; O(N) and a fixed number of launches whatever the output size.  The reference has nothing of the kind (its
