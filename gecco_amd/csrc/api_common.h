@@ -61,6 +61,9 @@ inline GemmArgs gemm_args_pair(const float* A, const float* bias1, float* C1, in
     return g;
 }
 
+// "a finite fp32 number > 0": false for zero, negatives, NaN and +inf
+inline bool finite_positive(float x) { return x > 0.f && x <= 3.402823466e38f; }
+
 // The checks the unit entry points repeat.  `who` is the entry point's name in its messages; return codes and texts are part of the ABI's
 // contract (tests/golden/api_errors.json), so an entry point keeps its own spelling (`spaced`: "pro_a / pro_o") and its own code (`rc`).
 inline int check_pro_pair(const char* who, const float* pro_a, const float* pro_o, bool spaced = false) {

@@ -224,7 +224,7 @@ int gecco_icp_f32(const float* source, const float* target, const float* normals
     if (form < 0 || form > 2) return fail(-2, "icp: form = %d is not 0 (auto), 1 (direct) or 2 (split)", form);
     if (max_iterations < 0 || max_iterations > GECCO_ICP_MAX_ITERATIONS)
         return fail(-2, "icp: max_iterations = %d is not in 0 .. %d", max_iterations, GECCO_ICP_MAX_ITERATIONS);
-    if (!(r > 0.f) || !(r <= 3.402823466e38f)) return fail(-2, "icp: r = %g must be a finite number > 0", (double)r);
+    if (!finite_positive(r)) return fail(-2, "icp: r = %g must be a finite number > 0", (double)r);
     if (!(relative_fitness >= 0.0) || !(relative_rmse >= 0.0))
         return fail(-2, "icp: relative_fitness = %g and relative_rmse = %g must both be >= 0", relative_fitness, relative_rmse);
     const float r2 = (float)((double)r * (double)r);
@@ -283,7 +283,7 @@ int gecco_ransac_f32(const float* source, const float* target, const int32_t* co
         return fail(-2, "ransac: hypotheses = %d is not in 1 .. %d", hypotheses, GECCO_RANSAC_MAX_HYPOTHESES);
     if (refine_passes < 0 || refine_passes > GECCO_RANSAC_MAX_REFINE)
         return fail(-2, "ransac: refine_passes = %d is not in 0 .. %d", refine_passes, GECCO_RANSAC_MAX_REFINE);
-    if (!(r > 0.f) || !(r <= 3.402823466e38f)) return fail(-2, "ransac: r = %g must be a finite number > 0", (double)r);
+    if (!finite_positive(r)) return fail(-2, "ransac: r = %g must be a finite number > 0", (double)r);
     if (!(edge_similarity >= 0.0) || !(edge_similarity <= 1.0))
         return fail(-2, "ransac: edge_similarity = %g is not in 0 .. 1", edge_similarity);
     const float r2 = (float)((double)r * (double)r);
@@ -312,7 +312,7 @@ int gecco_plane_ransac_f32(const float* points, const uint8_t* mask, float r, in
         return fail(-2, "plane_ransac: hypotheses = %d is not in 1 .. %d", hypotheses, GECCO_PLANE_RANSAC_MAX_HYPOTHESES);
     if (refine_passes < 0 || refine_passes > GECCO_PLANE_RANSAC_MAX_REFINE)
         return fail(-2, "plane_ransac: refine_passes = %d is not in 0 .. %d", refine_passes, GECCO_PLANE_RANSAC_MAX_REFINE);
-    if (!(r > 0.f) || !(r <= 3.402823466e38f)) return fail(-2, "plane_ransac: r = %g must be a finite number > 0", (double)r);
+    if (!finite_positive(r)) return fail(-2, "plane_ransac: r = %g must be a finite number > 0", (double)r);
     if (min_inliers < 0) return fail(-2, "plane_ransac: min_inliers = %d must be >= 0", min_inliers);
     if (axis && (!(cos2 >= 0.0) || !(cos2 <= 1.0))) return fail(-2, "plane_ransac: cos2 = %g is not in 0 .. 1", cos2);
     const int rc = plane_ransac_launch(points, mask, r, hypotheses, refine_passes, (unsigned long long)seed, axis, cos2, min_inliers, viewpoint,
@@ -334,7 +334,7 @@ int gecco_voxel_downsample_f32(const float* points, const float* origin, float v
     if (B < 1 || N < 1) return fail(-2, "voxel_downsample: B = %d, N = %d must both be >= 1", B, N);
     if (N > GECCO_VOXEL_MAX_POINTS) return fail(-2, "voxel_downsample: N = %d above %d", N, GECCO_VOXEL_MAX_POINTS);
     if (max_voxels < 1 || max_voxels > N) return fail(-2, "voxel_downsample: max_voxels = %d is not in 1 .. N = %d", max_voxels, N);
-    if (!(voxel_size > 0.f) || !(voxel_size <= 3.402823466e38f))
+    if (!finite_positive(voxel_size))
         return fail(-2, "voxel_downsample: voxel_size = %g must be a finite number > 0", (double)voxel_size);
     const int rc = voxel_launch(points, origin, voxel_size, centroids, first, count, inverse, n_voxels, workspace, B, N, max_voxels,
                                 (hipStream_t)stream);
@@ -352,7 +352,7 @@ int gecco_dbscan_f32(const float* points, int32_t* labels, int32_t* n_clusters, 
                      int B, int N, float eps2, int min_points, int max_rounds, void* stream) {
     if (!points || !labels || !n_clusters || !status || !ws) return fail(-1, "dbscan: null argument");
     if (B < 1 || N < 1) return fail(-2, "dbscan: B = %d, N = %d must both be >= 1", B, N);
-    if (!(eps2 > 0.f) || !(eps2 <= 3.402823466e38f)) return fail(-2, "dbscan: eps2 = %g must be a finite number > 0", (double)eps2);
+    if (!finite_positive(eps2)) return fail(-2, "dbscan: eps2 = %g must be a finite number > 0", (double)eps2);
     if (min_points < 1) return fail(-2, "dbscan: min_points = %d must be >= 1", min_points);
     if (max_rounds < 0 || max_rounds > GECCO_DBSCAN_MAX_ROUNDS)
         return fail(-2, "dbscan: max_rounds = %d is not in 0 .. %d", max_rounds, GECCO_DBSCAN_MAX_ROUNDS);

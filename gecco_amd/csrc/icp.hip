@@ -253,23 +253,12 @@ __global__ __launch_bounds__(ICP_UPDATE_THREADS) void icp_update_kernel(
         }
     }
 
-    // a fixed tree inside the wave, then the waves in order
-#pragma unroll
-    for (int e = 0; e < NACC; ++e) {
-        double v = acc[e];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if ((tid & 63) == 0) part[tid >> 6][e] = v;
-    }
+    icp_wave_sums(acc, part);
     __syncthreads();
     if (tid != 0) return;   // (no barrier below)
 
     double sum[NACC];
-    for (int e = 0; e < NACC; ++e) {
-        double v = part[0][e];
-        for (int w = 1; w < WAVES; ++w) v += part[w][e];
-        sum[e] = v;
-    }
+    icp_block_sums(part, sum);
     const double n = sum[0];
     const double fit = n / (double)M;
     const double rmse = n > 0.0 ? sqrt(sum[1] / n) : 0.0;
@@ -305,12 +294,7 @@ __global__ __launch_bounds__(ICP_UPDATE_THREADS) void icp_update_kernel(
         st[18] = 1.0;
         return;
     }
-    // T <- dT * double(Tf), dT's bottom row being (0, 0, 0, 1)
-    for (int r = 0; r < 3; ++r)
-        for (int e = 0; e < 4; ++e)
-            st[4 * r + e] = ((dT[4 * r] * (double)tf[e] + dT[4 * r + 1] * (double)tf[4 + e]) + dT[4 * r + 2] * (double)tf[8 + e]) +
-                            dT[4 * r + 3] * (double)tf[12 + e];
-    for (int e = 0; e < 4; ++e) st[12 + e] = (double)tf[12 + e];
+    icp_compose(dT, tf, st);
     st[16] = fit;
     st[17] = rmse;
     st[18] = 0.0;

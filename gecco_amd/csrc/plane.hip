@@ -50,13 +50,6 @@ constexpr int PLANE_UNROLL = 8;             // points of a tile scored per trip 
 static_assert(PLANE_TILE == PLANE_THREADS, "a thread fetches one point of a tile");
 static_assert(PLANE_TILE % PLANE_UNROLL == 0 && (PLANE_UNROLL & (PLANE_UNROLL - 1)) == 0, "a tile is a whole number of groups");
 
-struct __attribute__((aligned(16))) PlaneRecord {
-    int count;    // the block's best count, 0 when no hypothesis of the block reached the bar
-    int h;        // its hypothesis, -1 when there is none
-    double sum;
-};
-static_assert(sizeof(PlaneRecord) == 16, "16 bytes per block");
-
 static __device__ __forceinline__ void plane_load3(const f32x4* __restrict__ pl, int a0, int a1, int a2, double (&X)[3][3]) {
     const f32x4 p0 = pl[a0], p1 = pl[a1], p2 = pl[a2];
 #pragma unroll
@@ -118,7 +111,7 @@ __global__ __launch_bounds__(PLANE_THREADS) void plane_points_kernel(const float
                                                                      f32x4* __restrict__ list, int* __restrict__ header,
                                                                      int* __restrict__ n_points, int N) {
     __shared__ int wtot[PLANE_WAVES];
-    const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, b = blockIdx.x;
     const float* pb = points + (size_t)b * N * 3;
     const unsigned char* mb = mask ? mask + (size_t)b * N : nullptr;
     f32x4* pl = list + (size_t)b * N;
@@ -131,18 +124,8 @@ __global__ __launch_bounds__(PLANE_THREADS) void plane_points_kernel(const float
             px = pb[3 * (size_t)i], py = pb[3 * (size_t)i + 1], pz = pb[3 * (size_t)i + 2];
             ok = cloud_finite3(px, py, pz);
         }
-        const unsigned long long m = __ballot(ok);
-        const int before = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[w] = __popcll(m);
-        __syncthreads();
-        int off = base, total = 0;
-#pragma unroll
-        for (int ww = 0; ww < PLANE_WAVES; ++ww) {
-            if (ww < w) off += wtot[ww];
-            total += wtot[ww];
-        }
-        if (ok) pl[off + before] = f32x4{px, py, pz, __int_as_float(i)};   // off + before < K <= N
-        base += total;
+        const int slot = ransac_append<PLANE_WAVES>(ok, base, wtot);
+        if (ok) pl[slot] = f32x4{px, py, pz, __int_as_float(i)};   // slot < K <= N
         __syncthreads();   // wtot is rewritten by the next chunk
     }
     if (tid == 0) {
@@ -155,16 +138,15 @@ __global__ __launch_bounds__(PLANE_THREADS) void plane_points_kernel(const float
 __global__ __launch_bounds__(PLANE_THREADS) void plane_hyp_kernel(const f32x4* __restrict__ list, const int* __restrict__ header,
                                                                   const double* __restrict__ candidates, const double* __restrict__ axis,
                                                                   double cos2, float r, int min_count, unsigned long long seed,
-                                                                  PlaneRecord* __restrict__ records, int* __restrict__ hyp_triple,
+                                                                  ConsensusRecord* __restrict__ records, int* __restrict__ hyp_triple,
                                                                   float* __restrict__ hyp_plane, int* __restrict__ hyp_count,
                                                                   double* __restrict__ hyp_sum, int H, int N, int bpc) {
     __shared__ __attribute__((aligned(16))) f32x4 tile[PLANE_TILE];
     __shared__ unsigned short surv[PLANE_BLOCK_H];   // the survivors of phase 1 as offsets into the block, in h order
     __shared__ int wtot[PLANE_WAVES];
-    __shared__ int kc[PLANE_THREADS], kh[PLANE_THREADS];
-    __shared__ double ks[PLANE_THREADS];
+    __shared__ ConsensusKeys<PLANE_THREADS> keys;
 
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const int b = (int)(blockIdx.x / (unsigned)bpc), blk = (int)(blockIdx.x % (unsigned)bpc);
     const int h0 = blk * PLANE_BLOCK_H;   // < H <= 2^24
     const int K = header[4 * b];
@@ -221,18 +203,8 @@ __global__ __launch_bounds__(PLANE_THREADS) void plane_hyp_kernel(const f32x4* _
             else
                 live = true;
         }
-        const unsigned long long m = __ballot(live);
-        const int before = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[w] = __popcll(m);
-        __syncthreads();
-        int off = nsurv, total = 0;
-#pragma unroll
-        for (int ww = 0; ww < PLANE_WAVES; ++ww) {
-            if (ww < w) off += wtot[ww];
-            total += wtot[ww];
-        }
-        if (live) surv[off + before] = (unsigned short)o;   // off + before < PLANE_BLOCK_H
-        nsurv += total;
+        const int slot = ransac_append<PLANE_WAVES>(live, nsurv, wtot);
+        if (live) surv[slot] = (unsigned short)o;   // slot < PLANE_BLOCK_H
         __syncthreads();   // wtot is rewritten by the next round; after the last one, surv is complete
     }
 
@@ -296,14 +268,8 @@ __global__ __launch_bounds__(PLANE_THREADS) void plane_hyp_kernel(const f32x4* _
     }
 
     // phase 3: the block's winner
-    kc[tid] = bc, ks[tid] = bs, kh[tid] = bh;
-    __syncthreads();
-    for (int off = PLANE_THREADS / 2; off > 0; off >>= 1) {
-        if (tid < off && ransac_better(kc[tid + off], ks[tid + off], kh[tid + off], kc[tid], ks[tid], kh[tid]))
-            kc[tid] = kc[tid + off], ks[tid] = ks[tid + off], kh[tid] = kh[tid + off];
-        __syncthreads();
-    }
-    if (tid == 0) records[(size_t)b * bpc + blk] = PlaneRecord{kc[0], kh[0], ks[0]};
+    ransac_block_best(bc, bs, bh, keys);
+    if (tid == 0) records[(size_t)b * bpc + blk] = ConsensusRecord{keys.c[0], keys.h[0], keys.s[0]};
 }
 
 constexpr int PLANE_NACC = 11;   // sum 1, sum t^2, sum d (3), sum d d^T (xx, xy, xz, yy, yz, zz) with d = p - c0
@@ -370,21 +336,19 @@ static __device__ void plane_publish(const double* n, const double* c, const flo
 
 // grid: B blocks of PLANE_SELECT_THREADS
 __global__ __launch_bounds__(PLANE_SELECT_THREADS) void plane_select_kernel(
-    const f32x4* __restrict__ list, const int* __restrict__ header, const PlaneRecord* __restrict__ records,
+    const f32x4* __restrict__ list, const int* __restrict__ header, const ConsensusRecord* __restrict__ records,
     const double* __restrict__ candidates, const float* __restrict__ viewpoint, float r, int refine_passes, unsigned long long seed,
     double* __restrict__ plane, float* __restrict__ fitness, float* __restrict__ inlier_rmse, int* __restrict__ n_inliers,
     int* __restrict__ best, int* __restrict__ status, unsigned char* __restrict__ inliers, int H, int N, int bpc) {
     constexpr int WAVES = PLANE_SELECT_THREADS / 64;
     __shared__ double part[WAVES][PLANE_NACC];
     __shared__ double Psh[6];   // the current plane in fp64: the unit normal, then the point it passes through
-    __shared__ int kc[PLANE_SELECT_THREADS], kh[PLANE_SELECT_THREADS];
-    __shared__ double ks[PLANE_SELECT_THREADS];
+    __shared__ ConsensusKeys<PLANE_SELECT_THREADS> keys;
     __shared__ int done;
 
     const int tid = threadIdx.x, b = blockIdx.x;
     const int K = header[4 * b];
     const f32x4* pl = list + (size_t)b * N;
-    const PlaneRecord* rb = records + (size_t)b * bpc;
     unsigned char* const ib = inliers ? inliers + (size_t)b * N : nullptr;
     const float* vp = viewpoint ? viewpoint + 3 * (size_t)b : nullptr;
     double* const out = plane + 4 * (size_t)b;
@@ -392,22 +356,9 @@ __global__ __launch_bounds__(PLANE_SELECT_THREADS) void plane_select_kernel(
     if (ib)
         for (int i = tid; i < N; i += PLANE_SELECT_THREADS) ib[i] = 0;
 
-    // select
-    int bc = 0, bh = -1;
-    double bs = 0.0;
-    for (int k = tid; k < bpc; k += PLANE_SELECT_THREADS) {
-        const PlaneRecord q = rb[k];
-        if (ransac_better(q.count, q.sum, q.h, bc, bs, bh)) bc = q.count, bs = q.sum, bh = q.h;
-    }
-    kc[tid] = bc, ks[tid] = bs, kh[tid] = bh;
-    __syncthreads();
-    for (int off = PLANE_SELECT_THREADS / 2; off > 0; off >>= 1) {
-        if (tid < off && ransac_better(kc[tid + off], ks[tid + off], kh[tid + off], kc[tid], ks[tid], kh[tid]))
-            kc[tid] = kc[tid + off], ks[tid] = ks[tid + off], kh[tid] = kh[tid + off];
-        __syncthreads();
-    }
+    ransac_best_record(records + (size_t)b * bpc, bpc, keys);
     if (tid == 0) {
-        const int win = K >= 3 ? kh[0] : -1;
+        const int win = K >= 3 ? keys.h[0] : -1;
         if (win < 0) {
             out[0] = 0.0, out[1] = 0.0, out[2] = 1.0, out[3] = 0.0;
             fitness[b] = 0.f;
@@ -460,22 +411,11 @@ __global__ __launch_bounds__(PLANE_SELECT_THREADS) void plane_select_kernel(
             acc[5] += dx * dx, acc[6] += dx * dy, acc[7] += dx * dz;
             acc[8] += dy * dy, acc[9] += dy * dz, acc[10] += dz * dz;
         }
-        // a fixed tree inside the wave, then the waves in order
-#pragma unroll
-        for (int e = 0; e < PLANE_NACC; ++e) {
-            double v = acc[e];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-            if ((tid & 63) == 0) part[tid >> 6][e] = v;
-        }
+        icp_wave_sums(acc, part);
         __syncthreads();
         if (tid == 0) {
             double sum[PLANE_NACC];
-            for (int e = 0; e < PLANE_NACC; ++e) {
-                double v = part[0][e];
-                for (int w = 1; w < WAVES; ++w) v += part[w][e];
-                sum[e] = v;
-            }
+            icp_block_sums(part, sum);
             const double n = sum[0];
             bool last = pass >= refine_passes || n < 3.0;
             double nn[3], cn[3];
@@ -510,7 +450,7 @@ int plane_ransac_launch(const float* points, const unsigned char* mask, float r,
     if ((long long)B * bpc > 0x7fffffffLL) return -3;
     const int min_count = min_inliers > 3 ? min_inliers : 3;
     f32x4* list = static_cast<f32x4*>(ws);
-    PlaneRecord* records = reinterpret_cast<PlaneRecord*>(list + (size_t)B * N);
+    ConsensusRecord* records = reinterpret_cast<ConsensusRecord*>(list + (size_t)B * N);
     int* header = reinterpret_cast<int*>(records + (size_t)B * bpc);
     hipLaunchKernelGGL(plane_points_kernel, dim3((unsigned)B), dim3(PLANE_THREADS), 0, st, points, mask, list, header, n_points, N);
     hipLaunchKernelGGL(plane_hyp_kernel, dim3((unsigned)((long long)B * bpc)), dim3(PLANE_THREADS), 0, st, list, header, candidates, axis, cos2,

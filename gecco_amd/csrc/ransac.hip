@@ -24,9 +24,12 @@
 //             The cloud's pairs pass through LDS tiles of RANSAC_TILE pairs that every thread of the block helps fetch (the next tile is
 //             in flight while this one is scanned) and are read as broadcasts, the loop of knn_scan_kernel / icp_match_kernel.  Every
 //             thread reaches every barrier: a thread without a survivor still stages tiles
-//   A hypothesis's result is 16 bytes of workspace (count or -code, then sum) that depend on h alone: the block geometry cannot change a bit.
+//   phase 3   the block reduces its own survivors with count >= 3 under the total order and writes ONE 16-byte record (count, h, sum) to
+//             the workspace (plane.hip's phase 3; ransac_draw.h holds what the two files share): the select kernel reads H / 1024
+//             records.  A hypothesis's count and sum depend on h alone and the order is total, so the winner does not depend on how
+//             the hypotheses fall into blocks.  Per-hypothesis stores remain only for hyp_triple, hyp_count and hyp_sum, when given
 //
-// ransac_select_kernel: one workgroup of RANSAC_SELECT_THREADS per cloud reduces the keys (a total order: any tree gives the same
+// ransac_select_kernel: one workgroup of RANSAC_SELECT_THREADS per cloud reduces the records (a total order: any tree gives the same
 // winner), refits the winner's triple with the same routine (the same bits), then runs the refine passes: thread t takes pairs t, t + T,
 // ..., the fp64 sums are reduced inside the wave by a fixed shuffle tree and across the waves in order, thread 0 solves and publishes T
 // through LDS; the last evaluation writes fitness, rmse and the inlier list.
@@ -45,13 +48,6 @@ constexpr int RANSAC_TILE = 256;             // pairs per LDS tile: two 16-byte 
 constexpr int RANSAC_SELECT_THREADS = 512;
 constexpr int RANSAC_WAVES = RANSAC_THREADS / 64;
 static_assert(RANSAC_TILE == RANSAC_THREADS, "a thread fetches one pair of a tile");
-
-struct __attribute__((aligned(16))) RansacResult {
-    int count;    // count, or -code for a rejected hypothesis
-    int pad;
-    double sum;   // +inf for a rejected hypothesis
-};
-static_assert(sizeof(RansacResult) == 16, "16 bytes per hypothesis");
 
 // checks 1 and 2 of the triple (a0, a1, a2): 0 when it passes, else the code
 static __device__ __forceinline__ int ransac_precheck(const f32x4* __restrict__ pr, int a0, int a1, int a2, double s2) {
@@ -112,7 +108,7 @@ __global__ __launch_bounds__(RANSAC_THREADS) void ransac_pairs_kernel(const floa
                                                                       const int* __restrict__ corr, f32x4* __restrict__ pairs,
                                                                       int* __restrict__ header, int* __restrict__ n_pairs, int M, int N) {
     __shared__ int wtot[RANSAC_WAVES];
-    const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, b = blockIdx.x;
     const float* sb = source + (size_t)b * M * 3;
     const float* tb = target + (size_t)b * N * 3;
     const int* cb = corr + (size_t)b * M;
@@ -131,21 +127,11 @@ __global__ __launch_bounds__(RANSAC_THREADS) void ransac_pairs_kernel(const floa
                 ok = cloud_finite3(px, py, pz) && cloud_finite3(qx, qy, qz);
             }
         }
-        const unsigned long long m = __ballot(ok);
-        const int before = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[w] = __popcll(m);
-        __syncthreads();
-        int off = base, total = 0;
-#pragma unroll
-        for (int ww = 0; ww < RANSAC_WAVES; ++ww) {
-            if (ww < w) off += wtot[ww];
-            total += wtot[ww];
+        const int slot = ransac_append<RANSAC_WAVES>(ok, base, wtot);
+        if (ok) {   // slot < K <= M
+            pr[2 * (size_t)slot] = f32x4{px, py, pz, __int_as_float(i)};
+            pr[2 * (size_t)slot + 1] = f32x4{qx, qy, qz, __int_as_float(j)};
         }
-        if (ok) {   // off + before < K <= M
-            pr[2 * (size_t)(off + before)] = f32x4{px, py, pz, __int_as_float(i)};
-            pr[2 * (size_t)(off + before) + 1] = f32x4{qx, qy, qz, __int_as_float(j)};
-        }
-        base += total;
         __syncthreads();   // wtot is rewritten by the next chunk
     }
     if (tid == 0) {
@@ -157,14 +143,15 @@ __global__ __launch_bounds__(RANSAC_THREADS) void ransac_pairs_kernel(const floa
 // grid: B * bpc blocks of RANSAC_THREADS, block (b, blk) owns hypotheses [blk * RANSAC_BLOCK_H, min(H, (blk + 1) * RANSAC_BLOCK_H))
 __global__ __launch_bounds__(RANSAC_THREADS) void ransac_hyp_kernel(const f32x4* __restrict__ pairs, const int* __restrict__ header,
                                                                     const double* __restrict__ candidates, float r2, double s2,
-                                                                    unsigned long long seed, RansacResult* __restrict__ results,
+                                                                    unsigned long long seed, ConsensusRecord* __restrict__ records,
                                                                     int* __restrict__ hyp_triple, int* __restrict__ hyp_count,
                                                                     double* __restrict__ hyp_sum, int H, int M, int bpc) {
     __shared__ __attribute__((aligned(16))) f32x4 tile[2 * RANSAC_TILE];
     __shared__ unsigned short surv[RANSAC_BLOCK_H];   // the survivors of phase 1 as offsets into the block, in h order
     __shared__ int wtot[RANSAC_WAVES];
+    __shared__ ConsensusKeys<RANSAC_THREADS> keys;
 
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const int b = (int)(blockIdx.x / (unsigned)bpc), blk = (int)(blockIdx.x % (unsigned)bpc);
     const int h0 = blk * RANSAC_BLOCK_H;   // < H <= 2^24
     const int K = header[4 * b];
@@ -173,7 +160,6 @@ __global__ __launch_bounds__(RANSAC_THREADS) void ransac_hyp_kernel(const f32x4*
     const double inf = (double)__builtin_inff();
 
     auto write = [&](int h, int count, double sum) {
-        results[hb + h] = RansacResult{count, 0, sum};
         if (hyp_count) hyp_count[hb + h] = count;
         if (hyp_sum) hyp_sum[hb + h] = sum;
     };
@@ -207,22 +193,14 @@ __global__ __launch_bounds__(RANSAC_THREADS) void ransac_hyp_kernel(const f32x4*
             else
                 live = true;
         }
-        const unsigned long long m = __ballot(live);
-        const int before = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[w] = __popcll(m);
-        __syncthreads();
-        int off = nsurv, total = 0;
-#pragma unroll
-        for (int ww = 0; ww < RANSAC_WAVES; ++ww) {
-            if (ww < w) off += wtot[ww];
-            total += wtot[ww];
-        }
-        if (live) surv[off + before] = (unsigned short)o;   // off + before < RANSAC_BLOCK_H
-        nsurv += total;
+        const int slot = ransac_append<RANSAC_WAVES>(live, nsurv, wtot);
+        if (live) surv[slot] = (unsigned short)o;   // slot < RANSAC_BLOCK_H
         __syncthreads();   // wtot is rewritten by the next round; after the last one, surv is complete
     }
 
     // phase 2
+    int bc = 0, bh = -1;   // this thread's best among its survivors
+    double bs = 0.0;
 #pragma unroll 1
     for (int s0 = 0; s0 < nsurv; s0 += RANSAC_THREADS) {
         const bool valid = s0 + tid < nsurv;
@@ -280,53 +258,44 @@ __global__ __launch_bounds__(RANSAC_THREADS) void ransac_hyp_kernel(const f32x4*
             }
         }
         if (valid) {
-            if (code)
+            if (code) {
                 write(h, -code, inf);
-            else
+            } else {
                 write(h, count, sum);
+                if (count >= 3 && ransac_better(count, sum, h, bc, bs, bh)) bc = count, bs = sum, bh = h;
+            }
         }
     }
+
+    // phase 3: the block's winner
+    ransac_block_best(bc, bs, bh, keys);
+    if (tid == 0) records[(size_t)b * bpc + blk] = ConsensusRecord{keys.c[0], keys.h[0], keys.s[0]};
 }
 
 // grid: B blocks of RANSAC_SELECT_THREADS
 __global__ __launch_bounds__(RANSAC_SELECT_THREADS) void ransac_select_kernel(
-    const f32x4* __restrict__ pairs, const int* __restrict__ header, const RansacResult* __restrict__ results,
+    const f32x4* __restrict__ pairs, const int* __restrict__ header, const ConsensusRecord* __restrict__ records,
     const double* __restrict__ candidates, float r2, int refine_passes, unsigned long long seed, double* __restrict__ transformation,
     float* __restrict__ fitness, float* __restrict__ inlier_rmse, int* __restrict__ best, int* __restrict__ status, int* __restrict__ inliers,
-    int H, int M) {
+    int H, int M, int bpc) {
     constexpr int NACC = 17;
     constexpr int WAVES = RANSAC_SELECT_THREADS / 64;
     __shared__ double part[WAVES][NACC];
     __shared__ double Tsh[16];
-    __shared__ int kc[RANSAC_SELECT_THREADS], kh[RANSAC_SELECT_THREADS];
-    __shared__ double ks[RANSAC_SELECT_THREADS];
+    __shared__ ConsensusKeys<RANSAC_SELECT_THREADS> keys;
     __shared__ int done;
 
     const int tid = threadIdx.x, b = blockIdx.x;
     const int K = header[4 * b];
     const f32x4* pr = pairs + (size_t)b * M * 2;
-    const RansacResult* rb = results + (size_t)b * H;
     int* const ib = inliers ? inliers + (size_t)b * M : nullptr;
 
     if (ib)
         for (int i = tid; i < M; i += RANSAC_SELECT_THREADS) ib[i] = -1;
 
-    // select
-    int bc = 0, bh = -1;
-    double bs = 0.0;
-    for (int h = tid; h < H; h += RANSAC_SELECT_THREADS) {
-        const RansacResult r = rb[h];
-        if (r.count >= 3 && ransac_better(r.count, r.sum, h, bc, bs, bh)) bc = r.count, bs = r.sum, bh = h;
-    }
-    kc[tid] = bc, ks[tid] = bs, kh[tid] = bh;
-    __syncthreads();
-    for (int off = RANSAC_SELECT_THREADS / 2; off > 0; off >>= 1) {
-        if (tid < off && ransac_better(kc[tid + off], ks[tid + off], kh[tid + off], kc[tid], ks[tid], kh[tid]))
-            kc[tid] = kc[tid + off], ks[tid] = ks[tid + off], kh[tid] = kh[tid + off];
-        __syncthreads();
-    }
+    ransac_best_record(records + (size_t)b * bpc, bpc, keys);
     if (tid == 0) {
-        const int win = K >= 3 ? kh[0] : -1;
+        const int win = K >= 3 ? keys.h[0] : -1;
         bool found = win >= 0;
         double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
         if (found) {
@@ -390,22 +359,11 @@ __global__ __launch_bounds__(RANSAC_SELECT_THREADS) void ransac_select_kernel(
                 for (int e = 0; e < 3; ++e) acc[8 + 3 * r + e] += p[r] * q[e];
             }
         }
-        // a fixed tree inside the wave, then the waves in order
-#pragma unroll
-        for (int e = 0; e < NACC; ++e) {
-            double v = acc[e];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-            if ((tid & 63) == 0) part[tid >> 6][e] = v;
-        }
+        icp_wave_sums(acc, part);
         __syncthreads();
         if (tid == 0) {
             double sum[NACC];
-            for (int e = 0; e < NACC; ++e) {
-                double v = part[0][e];
-                for (int w = 1; w < WAVES; ++w) v += part[w][e];
-                sum[e] = v;
-            }
+            icp_block_sums(part, sum);
             const double n = sum[0];
             bool last = pass >= refine_passes || n < 3.0;
             double dT[12];
@@ -420,12 +378,7 @@ __global__ __launch_bounds__(RANSAC_SELECT_THREADS) void ransac_select_kernel(
                 inlier_rmse[b] = n > 0.0 ? (float)sqrt(sum[1] / n) : 0.f;
                 done = 1;
             } else {
-                // T <- dT * double(Tf), dT's bottom row being (0, 0, 0, 1)
-                for (int r = 0; r < 3; ++r)
-                    for (int e = 0; e < 4; ++e)
-                        Tsh[4 * r + e] = ((dT[4 * r] * (double)tf[e] + dT[4 * r + 1] * (double)tf[4 + e]) + dT[4 * r + 2] * (double)tf[8 + e]) +
-                                         dT[4 * r + 3] * (double)tf[12 + e];
-                for (int e = 0; e < 4; ++e) Tsh[12 + e] = (double)tf[12 + e];
+                icp_compose(dT, tf, Tsh);
             }
         }
         __syncthreads();
@@ -435,8 +388,8 @@ __global__ __launch_bounds__(RANSAC_SELECT_THREADS) void ransac_select_kernel(
 
 }  // namespace
 
-// ws of GECCO_RANSAC_WORKSPACE_BYTES(B, M, H), 16-byte aligned: the results (16 B H), the pairs (32 B M), the headers (16 B).
-// -2: arguments out of range, -3: a grid would pass 2^31 - 1
+// ws of GECCO_RANSAC_WORKSPACE_BYTES(B, M, H), 16-byte aligned: the pairs (32 B M), the block records (16 B ceil(H / 1024)), the headers
+// (16 B).  -2: arguments out of range, -3: a grid would pass 2^31 - 1
 int ransac_launch(const float* source, const float* target, const int* corr, float r2, double s2, int H, int refine_passes,
                   unsigned long long seed, double* transformation, float* fitness, float* inlier_rmse, int* n_pairs, int* best, int* status,
                   int* inliers, int* hyp_triple, int* hyp_count, double* hyp_sum, const double* candidates, void* ws, int B, int M, int N,
@@ -446,13 +399,13 @@ int ransac_launch(const float* source, const float* target, const int* corr, flo
         return -2;
     const int bpc = (H + RANSAC_BLOCK_H - 1) / RANSAC_BLOCK_H;
     if ((long long)B * bpc > 0x7fffffffLL) return -3;
-    RansacResult* results = static_cast<RansacResult*>(ws);
-    f32x4* pairs = reinterpret_cast<f32x4*>(results + (size_t)B * H);
-    int* header = reinterpret_cast<int*>(pairs + (size_t)B * M * 2);
+    f32x4* pairs = static_cast<f32x4*>(ws);
+    ConsensusRecord* records = reinterpret_cast<ConsensusRecord*>(pairs + (size_t)B * M * 2);
+    int* header = reinterpret_cast<int*>(records + (size_t)B * bpc);
     hipLaunchKernelGGL(ransac_pairs_kernel, dim3((unsigned)B), dim3(RANSAC_THREADS), 0, st, source, target, corr, pairs, header, n_pairs, M, N);
     hipLaunchKernelGGL(ransac_hyp_kernel, dim3((unsigned)((long long)B * bpc)), dim3(RANSAC_THREADS), 0, st, pairs, header, candidates, r2, s2,
-                       seed, results, hyp_triple, hyp_count, hyp_sum, H, M, bpc);
-    hipLaunchKernelGGL(ransac_select_kernel, dim3((unsigned)B), dim3(RANSAC_SELECT_THREADS), 0, st, pairs, header, results, candidates, r2,
-                       refine_passes, seed, transformation, fitness, inlier_rmse, best, status, inliers, H, M);
+                       seed, records, hyp_triple, hyp_count, hyp_sum, H, M, bpc);
+    hipLaunchKernelGGL(ransac_select_kernel, dim3((unsigned)B), dim3(RANSAC_SELECT_THREADS), 0, st, pairs, header, records, candidates, r2,
+                       refine_passes, seed, transformation, fitness, inlier_rmse, best, status, inliers, H, M, bpc);
     return (int)hipGetLastError();
 }

@@ -1,7 +1,8 @@
-// What the RANSAC kernels share (ransac.hip, plane.hip): the counter-based draw of three distinct indices, the squared length and the
-// degenerate-triangle test in fp64 without a division or a root, and the total order of the scores.  One implementation, so that a
-// hypothesis h of seed s names the same triple in gecco_ransac_f32 and gecco_plane_ransac_f32 (include/gecco_hip.h: the definitions;
-// tests/_ransac_ref.py restates the draw).  Device code is static __device__ __forceinline__.
+// What the consensus kernels share (ransac.hip, plane.hip): the counter-based draw of three distinct indices, the squared length and the
+// degenerate-triangle test in fp64 without a division or a root, the ordered append of the compactions and of phase 1, the total order
+// of the scores, the 16-byte record a workgroup leaves and the reductions under that order.  One implementation, so that a hypothesis h
+// of seed s names the same triple and the same winner in gecco_ransac_f32 and gecco_plane_ransac_f32 (include/gecco_hip.h: the
+// definitions; tests/_ransac_ref.py restates the draw).  Device code is static __device__ __forceinline__.
 #pragma once
 #include "common.h"
 
@@ -54,4 +55,66 @@ static __device__ __forceinline__ bool ransac_better(int c, double s, int h, int
     if (c != bc) return c > bc;
     if (s != bs) return s < bs;
     return h < bh;
+}
+
+// Ordered append: the slot of a kept item in a list that holds the kept items of all earlier calls and of the lower threads of this
+// one (a ballot, the rank inside the wave, the waves' totals in wtot[WAVES] of LDS), and base advanced by this call's total (uniform).
+// Every thread of the block calls it.  wtot is read after the barrier inside: the caller stores its item and then places the second
+// barrier itself (__syncthreads()) before the next call rewrites wtot, which is also where an LDS list becomes readable.
+template <int WAVES>
+static __device__ __forceinline__ int ransac_append(bool keep, int& base, int* wtot) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(keep);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wtot[w] = __popcll(m);
+    __syncthreads();
+    int off = base, total = 0;
+#pragma unroll
+    for (int ww = 0; ww < WAVES; ++ww) {
+        if (ww < w) off += wtot[ww];
+        total += wtot[ww];
+    }
+    base += total;
+    return off + before;
+}
+
+// What a workgroup of a hypothesis kernel leaves in the workspace: the best of its hypotheses that reached the bar, under ransac_better
+struct __attribute__((aligned(16))) ConsensusRecord {
+    int count;    // 0 when no hypothesis of the block reached the bar
+    int h;        // its hypothesis, -1 when there is none
+    double sum;
+};
+static_assert(sizeof(ConsensusRecord) == 16, "16 bytes per block");
+
+// The LDS of a reduction under ransac_better by THREADS threads
+template <int THREADS>
+struct ConsensusKeys {
+    int c[THREADS], h[THREADS];
+    double s[THREADS];
+};
+
+// Block best: every thread brings its own best (bc, bs, bh); afterwards the workgroup's best is in slot 0 of k, readable by every thread.
+// The order is total, so the shape of the tree cannot change the winner.
+template <int THREADS>
+static __device__ __forceinline__ void ransac_block_best(int bc, double bs, int bh, ConsensusKeys<THREADS>& k) {
+    const int tid = threadIdx.x;
+    k.c[tid] = bc, k.s[tid] = bs, k.h[tid] = bh;
+    __syncthreads();
+    for (int off = THREADS / 2; off > 0; off >>= 1) {
+        if (tid < off && ransac_better(k.c[tid + off], k.s[tid + off], k.h[tid + off], k.c[tid], k.s[tid], k.h[tid]))
+            k.c[tid] = k.c[tid + off], k.s[tid] = k.s[tid + off], k.h[tid] = k.h[tid + off];
+        __syncthreads();
+    }
+}
+
+// The first step of a select kernel: the best of a cloud's n records, strided over the threads, then the tree
+template <int THREADS>
+static __device__ __forceinline__ void ransac_best_record(const ConsensusRecord* __restrict__ records, int n, ConsensusKeys<THREADS>& k) {
+    int bc = 0, bh = -1;
+    double bs = 0.0;
+    for (int i = threadIdx.x; i < n; i += THREADS) {
+        const ConsensusRecord q = records[i];
+        if (ransac_better(q.count, q.sum, q.h, bc, bs, bh)) bc = q.count, bs = q.sum, bh = q.h;
+    }
+    ransac_block_best(bc, bs, bh, k);
 }

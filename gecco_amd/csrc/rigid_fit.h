@@ -1,6 +1,7 @@
 // The rigid fit icp.hip and ransac.hip share: the fp32 transform of a point, Horn's quaternion from fp64 moments of point pairs about an
-// anchor, its 4 x 4 symmetric eigenproblem by a fixed number of cyclic Jacobi sweeps, and the finite test.  One implementation, so that a fit of the same sums is
-// the same bits wherever it runs; the steps are part of the definitions of gecco_icp_f32 and gecco_ransac_f32 (include/gecco_hip.h).
+// anchor, its 4 x 4 symmetric eigenproblem by a fixed number of cyclic Jacobi sweeps, the finite test, the fixed-order reduction of the
+// fp64 sums that feed it (plane.hip's refit reduces the same way) and the compose step.  One implementation, so that a fit of the same
+// sums is the same bits wherever it runs; the steps are part of the definitions of gecco_icp_f32 and gecco_ransac_f32 (include/gecco_hip.h).
 // Device code is static __device__; icp_solve_point stays __noinline__ (one copy per kernel, its arrays in scratch once).
 #pragma once
 #include "common.h"
@@ -46,6 +47,40 @@ static __device__ __forceinline__ void icp_rotate(double (&a)[4][4], double (&v)
         v[r][p] = c * vp - s * vq;
         v[r][q] = s * vp + c * vq;
     }
+}
+
+// Fixed-order sums of a workgroup's fp64 accumulators, the order the definitions name: a fixed tree inside the wave, then the waves in
+// order.  icp_wave_sums: every thread brings acc[NACC]; the shuffle tree 32, 16, .., 1 leaves each wave's sums in part[wave].  After
+// the caller's barrier, icp_block_sums (one thread) adds wave 0 + wave 1 + .. into sum[NACC].
+template <int NACC, int WAVES>
+static __device__ __forceinline__ void icp_wave_sums(const double (&acc)[NACC], double (&part)[WAVES][NACC]) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int e = 0; e < NACC; ++e) {
+        double v = acc[e];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if ((tid & 63) == 0) part[tid >> 6][e] = v;
+    }
+}
+
+template <int NACC, int WAVES>
+static __device__ __forceinline__ void icp_block_sums(const double (&part)[WAVES][NACC], double (&sum)[NACC]) {
+    for (int e = 0; e < NACC; ++e) {
+        double v = part[0][e];
+        for (int w = 1; w < WAVES; ++w) v += part[w][e];
+        sum[e] = v;
+    }
+}
+
+// step 5's compose: T <- dT * double(Tf), dT (3 x 4) having the bottom row (0, 0, 0, 1); tf holds all 16 entries of Tf.  It stands
+// outside any fp contract(off) region, so this is the one place where the compiler decides how its products and sums fuse.
+static __device__ __forceinline__ void icp_compose(const double* dT, const float* tf, double* T) {
+    for (int r = 0; r < 3; ++r)
+        for (int e = 0; e < 4; ++e)
+            T[4 * r + e] = ((dT[4 * r] * (double)tf[e] + dT[4 * r + 1] * (double)tf[4 + e]) + dT[4 * r + 2] * (double)tf[8 + e]) +
+                           dT[4 * r + 3] * (double)tf[12 + e];
+    for (int e = 0; e < 4; ++e) T[12 + e] = (double)tf[12 + e];
 }
 
 // Point-to-point step from the reduced sums: acc[2..4] = sum (P - c), acc[5..7] = sum (Q - c), acc[8 + 3 a + e] = sum (P - c)_a (Q - c)_e.

@@ -291,6 +291,7 @@ FPFH_BINS = 33                   # GECCO_FPFH_BINS
 FEATURE_MAX_DIM = 64             # GECCO_FEATURE_MAX_DIM
 RANSAC_MAX_HYPOTHESES = 1 << 24  # GECCO_RANSAC_MAX_HYPOTHESES
 RANSAC_MAX_REFINE = 8            # GECCO_RANSAC_MAX_REFINE
+_RANSAC_BLOCK_HYPOTHESES = 1024  # GECCO_RANSAC_BLOCK_HYPOTHESES
 DBSCAN_MAX_ROUNDS = 64            # GECCO_DBSCAN_MAX_ROUNDS
 PLANE_MAX_HYPOTHESES = 1 << 24   # GECCO_PLANE_RANSAC_MAX_HYPOTHESES
 PLANE_MAX_REFINE = 8             # GECCO_PLANE_RANSAC_MAX_REFINE
@@ -351,6 +352,39 @@ def _integer(value, name: str) -> int:
         return operator.index(value)
     except TypeError as e:
         raise ValueError(f"{name} = {value!r} is not an integer") from e
+
+
+def _refits_and_seed(refine_passes, seed, max_refine: int, slots: int = 1):
+    """refine_passes in 0 .. max_refine and a seed that `slots` consecutive calls can count up from, as Python ints"""
+    refine_passes = _integer(refine_passes, "refine_passes")
+    if not 0 <= refine_passes <= max_refine:
+        raise ValueError(f"refine_passes = {refine_passes} is not in 0 .. {max_refine}")
+    seed = _integer(seed, "seed")
+    if not 0 <= seed <= (1 << 64) - slots:
+        raise ValueError(f"seed = {seed} is not in 0 .. 2^64 - {slots}")
+    return refine_passes, seed
+
+
+def _candidates_or_count(candidates, hypotheses, trailing: tuple, default: int, limit: int, B: int, single: bool):
+    """`candidates` (numbers or a tensor, (H, *trailing) or (B, H, *trailing)) or `hypotheses`, never both: the candidates as a tensor
+    (or None) and H in 1 .. limit (`default` when neither is given)"""
+    if candidates is None:
+        H = default if hypotheses is None else _integer(hypotheses, "hypotheses")
+    else:
+        if hypotheses is not None:
+            raise ValueError("candidates set the number of hypotheses: pass one of `hypotheses` and `candidates`")
+        shape, d = ", ".join(str(n) for n in trailing), len(trailing)
+        try:
+            candidates = candidates if isinstance(candidates, Tensor) else torch.as_tensor(candidates, dtype=torch.float64)
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise ValueError(f"candidates must be (H, {shape}) or ({B}, H, {shape})") from e
+        if candidates.is_complex() or candidates.dtype == torch.bool or candidates.dim() not in (d + 1, d + 2) or \
+                tuple(candidates.shape[-d:]) != trailing or (candidates.dim() == d + 2 and (single or candidates.shape[0] != B)):
+            raise ValueError(f"candidates must be (H, {shape}){'' if single else f' or ({B}, H, {shape})'}")
+        H = int(candidates.shape[-d - 1])
+    if not 1 <= H <= limit:
+        raise ValueError(f"hypotheses = {H} is not in 1 .. {limit}")
+    return candidates, H
 
 
 def _per_cloud_vector(value, name: str, B: int, refuse_bool: bool):
@@ -909,7 +943,7 @@ class RANSACResult(NamedTuple):
 
 def _ransac_workspace_bytes(B: int, M: int, H: int) -> int:
     """GECCO_RANSAC_WORKSPACE_BYTES(B, M, H)"""
-    return 16 * B * H + 32 * B * M + 16 * B
+    return 32 * B * M + 16 * B * ((H + _RANSAC_BLOCK_HYPOTHESES - 1) // _RANSAC_BLOCK_HYPOTHESES) + 16 * B
 
 
 def ransac_registration(source: Tensor, target: Tensor, correspondences: Tensor, max_correspondence_distance: float,
@@ -946,28 +980,8 @@ def ransac_registration(source: Tensor, target: Tensor, correspondences: Tensor,
         raise ValueError(f"edge_similarity = {edge_similarity!r} is not a number") from e
     if not 0.0 <= edge_similarity <= 1.0:
         raise ValueError(f"edge_similarity = {edge_similarity!r} is not in 0 .. 1")
-    refine_passes = _integer(refine_passes, "refine_passes")
-    if not 0 <= refine_passes <= RANSAC_MAX_REFINE:
-        raise ValueError(f"refine_passes = {refine_passes} is not in 0 .. {RANSAC_MAX_REFINE}")
-    seed = _integer(seed, "seed")
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed = {seed} is not in 0 .. 2^64 - 1")
-    cand = None
-    if candidates is not None:
-        if hypotheses is not None:
-            raise ValueError("candidates set the number of hypotheses: pass one of `hypotheses` and `candidates`")
-        try:
-            cand = candidates if isinstance(candidates, Tensor) else torch.as_tensor(candidates, dtype=torch.float64)
-        except (TypeError, ValueError, RuntimeError) as e:
-            raise ValueError(f"candidates must be (H, 4, 4) or ({B}, H, 4, 4)") from e
-        if cand.is_complex() or cand.dtype == torch.bool or cand.dim() not in (3, 4) or tuple(cand.shape[-2:]) != (4, 4) or \
-                (cand.dim() == 4 and (single or cand.shape[0] != B)):
-            raise ValueError(f"candidates must be (H, 4, 4){'' if single else f' or ({B}, H, 4, 4)'}")
-        H = int(cand.shape[-3])
-    else:
-        H = 100_000 if hypotheses is None else _integer(hypotheses, "hypotheses")
-    if not 1 <= H <= RANSAC_MAX_HYPOTHESES:
-        raise ValueError(f"hypotheses = {H} is not in 1 .. {RANSAC_MAX_HYPOTHESES}")
+    refine_passes, seed = _refits_and_seed(refine_passes, seed, RANSAC_MAX_REFINE)
+    cand, H = _candidates_or_count(candidates, hypotheses, (4, 4), 100_000, RANSAC_MAX_HYPOTHESES, B, single)
     x, px = _f32(s)
     y, py = _f32(t)
     dev = x.device
@@ -1034,12 +1048,7 @@ def _plane_arguments(points, distance_threshold, hypotheses, refine_passes, seed
     if B < 1 or N < 1:
         raise ValueError("empty batch or cloud")
     r = _positive_f32(distance_threshold, "distance_threshold", (TypeError, ValueError, OverflowError))
-    refine_passes = _integer(refine_passes, "refine_passes")
-    if not 0 <= refine_passes <= PLANE_MAX_REFINE:
-        raise ValueError(f"refine_passes = {refine_passes} is not in 0 .. {PLANE_MAX_REFINE}")
-    seed = _integer(seed, "seed")
-    if not 0 <= seed <= (1 << 64) - slots:
-        raise ValueError(f"seed = {seed} is not in 0 .. 2^64 - {slots}")
+    refine_passes, seed = _refits_and_seed(refine_passes, seed, PLANE_MAX_REFINE, slots)
     min_inliers = _integer(min_inliers, "min_inliers")
     if not 0 <= min_inliers < 1 << 31:
         raise ValueError(f"min_inliers = {min_inliers} is not in 0 .. 2^31 - 1")
@@ -1062,21 +1071,7 @@ def _plane_arguments(points, distance_threshold, hypotheses, refine_passes, seed
         cos2 = math.cos(max_angle) ** 2   # in double, on the host: part of the definition
     if viewpoint is not None:
         viewpoint = _per_cloud_vector(viewpoint, "viewpoint", B, refuse_bool=True)
-    if candidates is not None:
-        if hypotheses is not None:
-            raise ValueError("candidates set the number of hypotheses: pass one of `hypotheses` and `candidates`")
-        try:
-            candidates = candidates if isinstance(candidates, Tensor) else torch.as_tensor(candidates, dtype=torch.float64)
-        except (TypeError, ValueError, RuntimeError) as e:
-            raise ValueError(f"candidates must be (H, 4) or ({B}, H, 4)") from e
-        if candidates.is_complex() or candidates.dtype == torch.bool or candidates.dim() not in (2, 3) or candidates.shape[-1] != 4 or \
-                (candidates.dim() == 3 and (single or candidates.shape[0] != B)):
-            raise ValueError(f"candidates must be (H, 4){'' if single else f' or ({B}, H, 4)'}")
-        H = int(candidates.shape[-2])
-    else:
-        H = 1024 if hypotheses is None else _integer(hypotheses, "hypotheses")
-    if not 1 <= H <= PLANE_MAX_HYPOTHESES:
-        raise ValueError(f"hypotheses = {H} is not in 1 .. {PLANE_MAX_HYPOTHESES}")
+    candidates, H = _candidates_or_count(candidates, hypotheses, (4,), 1024, PLANE_MAX_HYPOTHESES, B, single)
     return p, single, dict(r=r, H=H, refine_passes=refine_passes, seed=seed, mask=mask, axis=axis, cos2=cos2, min_inliers=min_inliers,
                            viewpoint=viewpoint, candidates=candidates)
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GECCO_ABI_VERSION 14
+#define GECCO_ABI_VERSION 15
 
 int gecco_abi_version(void);
 const char* gecco_build_arch(void);   /* "gfx950" */
@@ -1167,7 +1167,8 @@ size_t gecco_feature_nn_workspace_bytes(int B, int M, int N);
  * Three launches whatever the data: a compaction of the pairs (one workgroup per cloud, an ordered scan, each pair as two 16-byte
  * entries (P, i), (Q, j)); the hypothesis kernel (a workgroup of 256 threads per 1024 consecutive hypotheses of a cloud: draw and
  * checks 1 - 2 for four hypotheses per thread, the survivors compacted in h order in LDS, then one thread per survivor fits and
- * scores against the pairs streamed through LDS tiles; 16 bytes of result per hypothesis); select + refine (one workgroup per cloud).
+ * scores against the pairs streamed through LDS tiles; the workgroup leaves one 16-byte record, its best survivor with count >= 3
+ * under the total order); select + refine (one workgroup per cloud, reading one record per GECCO_RANSAC_BLOCK_HYPOTHESES hypotheses).
  * No atomics, no workgroup waits on another, no allocation and no host synchronisation: the call can be captured in a graph.  The
  * outputs are the same bits run to run, in any batch position and however H is split across workgroups.
  * ws: gecco_ransac_workspace_bytes(B, M, hypotheses) = GECCO_RANSAC_WORKSPACE_BYTES(B, M, H) bytes, 16-byte aligned; required; never
@@ -1178,8 +1179,10 @@ size_t gecco_feature_nn_workspace_bytes(int B, int M, int N);
 #define GECCO_RANSAC_MAX_HYPOTHESES (1 << 24)
 #define GECCO_RANSAC_MAX_REFINE 8
 #define GECCO_RANSAC_BLOCK_HYPOTHESES 1024
-#define GECCO_RANSAC_WORKSPACE_BYTES(B, M, H) \
-    ((size_t)16 * (size_t)(B) * (size_t)(H) + (size_t)32 * (size_t)(B) * (size_t)(M) + (size_t)16 * (size_t)(B))
+#define GECCO_RANSAC_WORKSPACE_BYTES(B, M, H)                                                                                 \
+    ((size_t)32 * (size_t)(B) * (size_t)(M) +                                                                                 \
+     (size_t)16 * (size_t)(B) * (((size_t)(H) + GECCO_RANSAC_BLOCK_HYPOTHESES - 1) / GECCO_RANSAC_BLOCK_HYPOTHESES) +     \
+     (size_t)16 * (size_t)(B))
 int gecco_ransac_f32(const float* source, const float* target, const int32_t* corr, float r, double edge_similarity, int hypotheses,
                      int refine_passes, uint64_t seed, double* transformation, float* fitness, float* inlier_rmse, int32_t* n_pairs,
                      int32_t* best, int32_t* status, int32_t* inliers, int32_t* hyp_triple, int32_t* hyp_count, double* hyp_sum,

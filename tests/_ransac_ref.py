@@ -273,7 +273,7 @@ def holes():
 # name -> (inputs, H, seed of the draw).  The three scenes of the issue, the tiny ones, H across the wave and block edges of the hypothesis
 # kernel, K across the edges of its 256-pair LDS tile (257 is the second scene), the holes
 SCENES = {"s300": (300, 600, 4096, 0.3), "s257": (257, 4097, 1000, 0.5), "s1025": (1025, 1100, 2048, 0.3)}
-H_EDGES = [1, 63, 65, 1023, 1025]
+H_EDGES = [1, 63, 65, 1023, 1024, 1025, 2049]   # 1024: exactly one full block; 2049: two blocks and one hypothesis
 K_EDGES = [255, 256, 513]
 CASES = list(SCENES) + ["tiny3", "tiny4", "holes"] + [f"h{H}" for H in H_EDGES] + [f"k{K}" for K in K_EDGES]
 
@@ -302,6 +302,40 @@ def solved(name, refine_passes=1):
     (src, tgt, corr, _), H, seed = case(name)
     hyp = None if refine_passes == 1 else solved(name)["hyp"]
     return ransac(src, tgt, corr, R, EDGE, H, refine_passes, seed, hyp=hyp)
+
+
+# ---- candidates for the per-block winner ---------------------------------------------------------------------------------------------
+
+TYING = ([1500, 2047, 2048, 3000, 4095], [2048, 4095], [4095], [1023, 1024])   # where the good pose stands among 4096 candidates
+SCATTER_H, SCATTER_SHIFT = 2500, 517
+
+
+def hopeless():
+    """the identity moved by 100 along x: under it no pair of s300 is within r"""
+    T = np.eye(4)
+    T[0, 3] = 100.0
+    return T
+
+
+def tying_candidates(tying, H=4096):
+    """(H, 4, 4): ground_truth() at the positions `tying`, hopeless() elsewhere.  Identical poses have identical count and sum: h decides"""
+    cand = np.tile(hopeless(), (H, 1, 1))
+    cand[list(tying)] = ground_truth()
+    return cand
+
+
+@functools.lru_cache(maxsize=None)
+def scattered_candidates():
+    """(SCATTER_H, 4, 4), read-only: the restatement's T of every scored hypothesis of case s300 at fixed pseudo-random positions (three
+    blocks of hypotheses), hopeless() elsewhere; and those positions"""
+    hyp = solved("s300")["hyp"]
+    live = np.nonzero(hyp["count"] >= 0)[0]
+    pos = np.random.default_rng(2500).permutation(SCATTER_H)[:len(live)]
+    cand = np.tile(hopeless(), (SCATTER_H, 1, 1))
+    cand[pos] = hyp["T"][live]
+    cand.setflags(write=False)
+    pos.setflags(write=False)
+    return cand, pos
 
 
 # ---- the whole registration chain ---------------------------------------------------------------------------------------------------

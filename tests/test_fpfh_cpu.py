@@ -45,7 +45,7 @@ def test_symbols_declared_exported_and_bound(lib):
     assert gecco_amd.fpfh is pointops.fpfh and gecco_amd.match_features is pointops.match_features
     assert gecco_amd.FPFH_BINS == pointops.FPFH_BINS == 33 and gecco_amd.FEATURE_MAX_DIM == pointops.FEATURE_MAX_DIM == 64
     assert "#define GECCO_FPFH_BINS 33" in header and "#define GECCO_FEATURE_MAX_DIM 64" in header
-    assert lib.gecco_abi_version() == 14
+    assert lib.gecco_abi_version() == 15
 
 
 def test_workspace_query_runs_without_gpu(lib):

@@ -45,7 +45,7 @@ def test_entry_point_declared_exported_and_bound(lib):
     fn = getattr(lib, NAME)
     assert fn is not None and len(fn.argtypes) == 10
     assert "fps.hip" in __import__("__graft_entry__").SOURCES
-    assert lib.gecco_abi_version() == 14 and _lib.ABI_VERSION == 14
+    assert lib.gecco_abi_version() == 15 and _lib.ABI_VERSION == 15
 
 
 def test_header_states_the_definition_and_the_limit():

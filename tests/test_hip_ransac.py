@@ -1,6 +1,7 @@
 """RANSAC registration on the GPU (csrc/ransac.hip, gecco_ransac_f32) against the numpy restatement of its definition
 (tests/_ransac_ref.py): the draw and the fit-free checks index for index, the score teacher-forced through `candidates` bit for bit,
-free runs (tests/test_ransac_cpu.py holds the margins that make their comparison exact), every status, NaN and batch containment,
+free runs (tests/test_ransac_cpu.py holds the margins that make their comparison exact), ties across blocks and the block geometry
+(the per-block winner), every status, NaN and batch containment,
 reproducibility, poisoned memory, streams, graphs, input handling and the whole chain fpfh -> match_features -> ransac -> icp."""
 import numpy as np
 import pytest
@@ -181,6 +182,51 @@ def test_reproducibility(ops):
         long_ = ops.ransac_registration(ts, tt, tc, ref.R, **{**kw, "hypotheses": H2})
         for x, y in zip(short.hypotheses, long_.hypotheses):
             assert torch.equal(x.view(torch.int64) if x.is_floating_point() else x, (y.view(torch.int64) if y.is_floating_point() else y)[:, :H1])
+
+
+def test_ties_across_blocks(ops):
+    """4096 candidates on s300, all hopeless but the ground-truth pose at the positions `tying`: identical poses have identical count
+    and sum, so h alone decides, also when the tie begins in a later block or straddles a block edge
+    (tests/test_ransac_cpu.py::test_conditions_of_the_per_block_winner_tests holds the conditions)"""
+    (src, tgt, corr, _), _, _ = ref.case("s300")
+    ts, tt, tc = _cuda(src), _cuda(tgt), _cuda(corr)
+    _, _, P, Q = ref.pairs(src, tgt, corr)
+    good = ref.score(ref.ground_truth(), P, Q, ref.r2_of(ref.R))[0]
+    assert good >= 3
+    for tying in ref.TYING:
+        cand = ref.tying_candidates(tying)
+        res = ops.ransac_registration(ts, tt, tc, ref.R, candidates=_cuda(cand), refine_passes=0, return_hypotheses=True)
+        assert int(res.best_hypothesis) == tying[0] and int(res.status) == 0, tying
+        assert np.array_equal(res.transformation.cpu().numpy().view(np.int64), cand[tying[0]].view(np.int64)), tying   # the candidate itself
+        assert np.array_equal(res.hypotheses[1].cpu().numpy(), np.where(np.isin(np.arange(4096), tying), good, 0)), tying
+
+
+def test_block_geometry_cannot_change_the_answer(ops):
+    """the same set of poses falling into the workgroups differently (rotated, reversed): every pose keeps its score bit for bit and the
+    same pose wins with the same outputs; and a free run's winner is the reduction of its per-hypothesis results by a routine that knows
+    nothing of blocks"""
+    (src, tgt, corr, _), _, _ = ref.case("s300")
+    ts, tt, tc = _cuda(src), _cuda(tgt), _cuda(corr)
+    cand, pos = ref.scattered_candidates()
+    Hc = len(cand)
+    kw = dict(return_inliers=True, return_hypotheses=True)
+    straight = ops.ransac_registration(ts, tt, tc, ref.R, candidates=_cuda(cand), **kw)
+    _, c0, s0 = (t.cpu().numpy() for t in straight.hypotheses)
+    assert sorted(np.nonzero(c0 > 0)[0].tolist()) == sorted(pos.tolist()) and len(set((pos // ref.BLOCK_HYPOTHESES).tolist())) == 3
+    top = np.nonzero(c0 == c0.max())[0]
+    assert c0.max() >= 3 and len(np.unique(s0[top])) == len(top)   # no tie at the top: the winner is one pose, wherever it sits
+    assert int(straight.status) == 0 and int(straight.best_hypothesis) == ref.select(c0, s0)
+    for name, perm in [("rotated", np.roll(np.arange(Hc), ref.SCATTER_SHIFT)), ("reversed", np.arange(Hc)[::-1].copy())]:
+        moved = ops.ransac_registration(ts, tt, tc, ref.R, candidates=_cuda(cand[perm]), **kw)
+        _, c1, s1 = (t.cpu().numpy() for t in moved.hypotheses)
+        assert np.array_equal(c1, c0[perm]) and np.array_equal(s1.view(np.int64), s0[perm].view(np.int64)), name
+        assert perm[int(moved.best_hypothesis)] == int(straight.best_hypothesis), name
+        for f in ("transformation", "fitness", "inlier_rmse"):
+            _poison.assert_same_bits(getattr(moved, f), getattr(straight, f), f"{name} {f}")
+        assert torch.equal(moved.inliers, straight.inliers), name
+    free = _run(ops, "s300", return_hypotheses=True)
+    _, counts, sums = (t.cpu().numpy() for t in free.hypotheses)
+    assert len(counts) == 4096 and int(free.best_hypothesis) == ref.select(counts, sums)
 
 
 def test_stream_and_graph(ops):

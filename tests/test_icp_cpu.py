@@ -34,7 +34,7 @@ def test_symbols_declared_exported_and_bound(lib):
     assert gecco_amd.ICPResult is pointops.ICPResult and gecco_amd.ICP_MAX_ITERATIONS == pointops.ICP_MAX_ITERATIONS == 1000
     assert pointops.ICPResult._fields == ("transformation", "fitness", "inlier_rmse", "iterations", "status", "correspondence")
     assert "#define GECCO_ICP_MAX_ITERATIONS 1000" in header and "#define GECCO_ICP_STATE_BYTES %d" % pointops._ICP_STATE_BYTES in header
-    assert lib.gecco_abi_version() == 14
+    assert lib.gecco_abi_version() == 15
 
 
 def test_workspace_query_runs_without_gpu(lib):

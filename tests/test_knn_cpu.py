@@ -51,7 +51,7 @@ def test_entry_points_declared_exported_and_bound(lib):
     assert len(_lib.SIGNATURES[NAME][1]) == 12 and len(_lib.SIGNATURES[WS_NAME][1]) == 4
     assert len(getattr(lib, NAME).argtypes) == 12 and len(getattr(lib, WS_NAME).argtypes) == 4
     assert "knn.hip" in __import__("__graft_entry__").SOURCES
-    assert lib.gecco_abi_version() == 14 and _lib.ABI_VERSION == 14
+    assert lib.gecco_abi_version() == 15 and _lib.ABI_VERSION == 15
 
 
 def test_header_states_the_definition_and_the_limits():

@@ -42,7 +42,7 @@ def test_entry_points_declared_exported_and_bound(lib):
         head = src[:src.index("int " + name)]
         comment = head[head.rindex("/*"):]
         assert re.search(r"metrics\.py:\d+-\d+", comment), f"{name}: no reference citation"
-    assert lib.gecco_abi_version() == 14
+    assert lib.gecco_abi_version() == 15
 
 
 def test_header_states_the_zero_distance_rule_and_the_gather():

@@ -41,7 +41,7 @@ def test_entry_point_declared_exported_and_bound(lib):
     assert len(_lib.SIGNATURES[NAME][1]) == 15
     assert len(getattr(lib, NAME).argtypes) == 15
     assert "normals.hip" in __import__("__graft_entry__").SOURCES
-    assert lib.gecco_abi_version() == 14 and _lib.ABI_VERSION == 14
+    assert lib.gecco_abi_version() == 15 and _lib.ABI_VERSION == 15
 
 
 def test_header_states_the_definition():

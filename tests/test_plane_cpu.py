@@ -293,7 +293,7 @@ def test_symbols_and_workspace(ops):
                  "size_t gecco_plane_ransac_workspace_bytes(int B, int N, int hypotheses);", "#define GECCO_PLANE_RANSAC_WORKSPACE_BYTES(B, N, H)",
                  "void* ws, int B, int N, void* stream);", "tests/_plane_ref.py"):
         assert text in header, text
-    assert lib.gecco_abi_version() == 14
+    assert lib.gecco_abi_version() == 15
     for B, N, H in [(1, 1, 1), (3, 600, 1024), (3, 600, 1025), (16, 2048, 4096), (1, 100_000, 16_384), (2, 7, 1 << 24)]:
         want = ops._plane_workspace_bytes(B, N, H)
         assert lib.gecco_plane_ransac_workspace_bytes(B, N, H) == want == ref.workspace_bytes(B, N, H)

@@ -171,6 +171,28 @@ def test_margin_conditions(name):
     assert (total[tied] > total[best] * (1 + 1e-6)).all()
 
 
+def test_conditions_of_the_per_block_winner_tests():
+    """What test_hip_ransac.py's test_ties_across_blocks and test_block_geometry_cannot_change_the_answer rely on, by the restatement:
+    on s300 the ground-truth pose scores count >= 3 and the hopeless pose 0; the scattered candidates span three blocks and those
+    that hold the top count all differ in sum, so one pose wins wherever it stands."""
+    (src, tgt, corr, _), _, _ = ref.case("s300")
+    _, _, P, Q = ref.pairs(src, tgt, corr)
+    r2 = ref.r2_of(ref.R)
+    assert ref.score(ref.ground_truth(), P, Q, r2)[0] >= 3 and ref.score(ref.hopeless(), P, Q, r2)[0] == 0
+    for tying in ref.TYING:
+        cand = ref.tying_candidates(tying)
+        assert cand.shape == (4096, 4, 4) and [h for h in range(4096) if np.array_equal(cand[h], ref.ground_truth())] == list(tying)
+    cand, pos = ref.scattered_candidates()
+    hyp = ref.solved("s300")["hyp"]
+    live = np.nonzero(hyp["count"] >= 0)[0]
+    assert len(pos) == len(live) == len(set(pos.tolist())) and 0.02 * 4096 < len(live) < 0.04 * 4096
+    assert sorted(set((pos // ref.BLOCK_HYPOTHESES).tolist())) == [0, 1, 2]
+    assert np.array_equal(cand[pos], hyp["T"][live]) and (np.delete(cand, pos, axis=0) == ref.hopeless()).all()
+    count, total = hyp["count"][live], hyp["sum"][live]
+    top = np.nonzero(count == count.max())[0]
+    assert count.max() >= 3 and len(np.unique(total[top])) == len(top)   # no tie at the top
+
+
 def test_pipeline_restatement_registers_where_icp_alone_fails():
     out = ref.pipeline_solved()
     perm = ref.pipeline_scene()[2]
@@ -193,13 +215,13 @@ def test_abi_constants_and_exports(lib):
     assert len(_lib.SIGNATURES["gecco_ransac_f32"][1]) == 24
     assert pointops.RANSACResult._fields == ("transformation", "fitness", "inlier_rmse", "n_pairs", "best_hypothesis", "status", "inliers",
                                              "hypotheses")
-    assert lib.gecco_abi_version() == 14
+    assert lib.gecco_abi_version() == 15
 
 
 def test_workspace_query_runs_without_gpu(lib):
     from gecco_amd import pointops
     for B, M, H in [(1, 1, 1), (3, 257, 1000), (16, 2048, 100000), (1, 2 ** 20, 1 << 24)]:
-        want = 16 * B * H + 32 * B * M + 16 * B
+        want = 32 * B * M + 16 * B * -(-H // ref.BLOCK_HYPOTHESES) + 16 * B   # one record per block of 1024 hypotheses: not O(B H)
         assert lib.gecco_ransac_workspace_bytes(B, M, H) == want == pointops._ransac_workspace_bytes(B, M, H)
     for bad in [(0, 1, 1), (1, 0, 1), (1, 1, 0), (-1, 5, 5), (1, 5, (1 << 24) + 1)]:
         assert lib.gecco_ransac_workspace_bytes(*bad) == 0

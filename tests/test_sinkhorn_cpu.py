@@ -47,7 +47,7 @@ def test_entry_points_declared_exported_and_bound(lib):
         assert "metrics.py:144-156" in comment, f"{name}: no reference citation"
         assert "no float atomics" in comment and "constant of the gradient" in comment, name
     assert "benchmark.py:21-39" in _comment_above(src, "gecco_set_sinkhorn_f32")
-    assert lib.gecco_abi_version() == 14
+    assert lib.gecco_abi_version() == 15
 
 
 def test_header_states_the_definition_and_the_limit():

@@ -34,7 +34,7 @@ def test_symbols_exported_and_bound(lib):
     with open(os.path.join(ROOT, "include", "gecco_hip.h")) as f:
         src = f.read()
     assert "int " + NAME + "(" in src and "size_t " + WS_NAME + "(int B, int N);" in src and "#define GECCO_VOXEL_WORKSPACE_BYTES(B, N)" in src
-    assert lib.gecco_abi_version() == 14
+    assert lib.gecco_abi_version() == 15
     assert gecco_amd.voxel_downsample is gecco_amd.pointops.voxel_downsample and gecco_amd.voxel_pool is gecco_amd.pointops.voxel_pool
     sig = inspect.signature(gecco_amd.voxel_downsample)
     assert list(sig.parameters) == ["points", "voxel_size", "origin", "max_voxels", "return_index", "return_counts", "return_inverse"]
