@@ -1,5 +1,5 @@
 // C ABI of libgecco_hip.so, part 4 of 4: point-cloud operators and metrics (distance matrix, Chamfer, set metrics, EMD,
-// Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, RANSAC registration, voxel grid, DBSCAN).
+// Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, RANSAC registration, voxel grid, DBSCAN, radius search).
 #include "api_common.h"
 
 using namespace gecco_api;
@@ -359,6 +359,38 @@ int gecco_dbscan_f32(const float* points, int32_t* labels, int32_t* n_clusters, 
     const int rc = dbscan_launch(points, labels, n_clusters, count, rounds, status, ws, B, N, eps2, min_points, max_rounds, (hipStream_t)stream);
     if (rc == -3) return fail(-2, "dbscan: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
     TRY(rc, "dbscan");
+    return 0;
+}
+
+// fixed-radius neighbour search (radius.hip).  radius2 = fp32(r * r) from the caller.  Every refusal is -2, null pointers included
+static int radius_common(const char* who, int B, int M, int N, float radius2, int exclude_self) {
+    if (B < 1 || M < 1 || N < 1) return fail(-2, "%s: B = %d, M = %d, N = %d must all be >= 1", who, B, M, N);
+    if (!finite_positive(radius2)) return fail(-2, "%s: radius2 = %g must be a finite number > 0", who, (double)radius2);
+    if (exclude_self && M != N)
+        return fail(-2, "%s: exclude_self needs the query cloud to be the reference cloud (M = %d, N = %d)", who, M, N);
+    return 0;
+}
+int gecco_radius_count_f32(const float* query, const float* ref, int32_t* count, int B, int M, int N, float radius2, int exclude_self,
+                           void* stream) {
+    if (!query || !ref || !count) return fail(-2, "radius_count: null argument");
+    if (const int bad = radius_common("radius_count", B, M, N, radius2, exclude_self)) return bad;
+    const int rc = radius_launch(query, ref, nullptr, nullptr, nullptr, count, B, M, N, radius2, exclude_self ? 1 : 0, 0, (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "radius_count: the grid for B = %d, M = %d, N = %d passes 2^31 - 1 workgroups", B, M, N);
+    TRY(rc, "radius_count");
+    return 0;
+}
+int gecco_radius_search_f32(const float* query, const float* ref, const int64_t* row_start, int32_t* idx, float* d2, int32_t* count, int B, int M,
+                            int N, float radius2, int exclude_self, int max_neighbors, void* stream) {
+    if (!query || !ref || !idx) return fail(-2, "radius_search: null argument");
+    if (const int bad = radius_common("radius_search", B, M, N, radius2, exclude_self)) return bad;
+    if (row_start ? max_neighbors != 0 : max_neighbors < 1)
+        return fail(-2, "radius_search: max_neighbors = %d must be 0 with row_start (the CSR form) and >= 1 without (the fixed-width form)",
+                    max_neighbors);
+    static_assert(sizeof(long long) == sizeof(int64_t), "row_start is read as long long");
+    const int rc = radius_launch(query, ref, reinterpret_cast<const long long*>(row_start), idx, d2, row_start ? nullptr : count, B, M, N,
+                                 radius2, exclude_self ? 1 : 0, max_neighbors, (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "radius_search: the grid for B = %d, M = %d, N = %d passes 2^31 - 1 workgroups", B, M, N);
+    TRY(rc, "radius_search");
     return 0;
 }
 

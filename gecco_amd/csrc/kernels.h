@@ -545,6 +545,12 @@ int voxel_launch(const float* points, const float* origin, float voxel_size, flo
 // 2^31 - 1 workgroups
 int dbscan_launch(const float* points, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
                   int min_points, int R, hipStream_t st);
+// radius.hip — fixed-radius neighbour search (definition: gecco_radius_search_f32): one launch.  r2 = fp32(r * r).  idx null: the counts
+// alone (count required).  row_start (the int64 exclusive prefix sum of the counts) given: the CSR fill, K = 0, d2 nullable.  Otherwise
+// the fixed-width fill, K >= 1 slots per row, d2 and count nullable.  -2: arguments out of range, -3: the grid would pass 2^31 - 1
+// workgroups
+int radius_launch(const float* query, const float* ref, const long long* row_start, int* idx, float* d2, int* count, int B, int M, int N,
+                  float r2, int exclude_self, int K, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

@@ -4,7 +4,8 @@ lists (csrc/normals.hip, gecco_normals_f32), voxel-grid downsampling with attrib
 gecco_voxel_downsample_f32), rigid ICP registration, point-to-point and point-to-plane (csrc/icp.hip, gecco_icp_f32), FPFH
 descriptors with nearest-neighbour matching in feature space (csrc/fpfh.hip, gecco_fpfh_f32, gecco_feature_nn_f32), and RANSAC
 registration from correspondences (csrc/ransac.hip, gecco_ransac_f32), RANSAC plane segmentation (csrc/plane.hip,
-gecco_plane_ransac_f32) and DBSCAN clustering (csrc/dbscan.hip, gecco_dbscan_f32).
+gecco_plane_ransac_f32), DBSCAN clustering (csrc/dbscan.hip, gecco_dbscan_f32) and fixed-radius neighbour search (csrc/radius.hip,
+gecco_radius_count_f32, gecco_radius_search_f32) with the radius outlier filter built on it.
 
 The reference reduces a dense cloud to a fixed size by random permutation (gecco-jax data/torch_shapenet.py:20-21, data/taskonomy.py:84),
 which keeps density clumps and loses thin structure.  `farthest_point_sample` is the well-spread cut: from a start point, each next point
@@ -263,6 +264,35 @@ found the fixed point (`rounds` counts it, `status` 0) and the cloud's later wor
 ceil(log2 max(N, 2)) + 2 cannot be exceeded; a cloud that runs out of an explicit limit has status 1 and labels that refine the true
 clusters.  In every launch what is read is written by no thread of that launch, so labels, rounds and status are the same bits run to
 run and in any batch position, also at the limit; no float atomics, no host synchronisation.
+
+Fixed-radius neighbour search (`radius_count`, `radius_search`, `radius_outlier_mask`).  "Every point within r": the query Open3D and
+PCL pair with `knn` (`search_radius_vector_3d`, `search_hybrid_vector_3d`, `remove_radius_outlier` / `RadiusOutlierRemoval`) and
+PointNet++'s `ball_query`.  The route without it is `metrics.distance_matrix(...) <= r` and `nonzero`: an M x N matrix (40 GB at
+100 000 points against themselves) whose aa + bb - 2ab rounding puts pairs at the bound on the wrong side.  Definition
+(include/gecco_hip.h; tests/_radius_ref.py restates it in numpy float32).  Per batch element, for queries q_i (i < M) and reference
+points p_j (j < N):
+    r2         fp32(radius * radius): the fp32 value of the radius squared in double and rounded once, `cluster_dbscan`'s eps2.  The
+               radius must be a finite fp32 number > 0 and so must its square
+    dist2      the spelling of `knn`: (dx dx + dy dy) + dz dz, every operation rounded to fp32, none contracted, NaN -> +inf
+    neighbour  j is a neighbour of i iff dist2(q_i, p_j) <= r2, inclusive, compared on the bits as unsigned integers.  The bound is
+               defined on r2 because r and r2 disagree at it: radius = sqrt(2) excludes a pair at dist2 = 2, for
+               fp32(fp32(sqrt 2)^2) = 1.99999988.  A non-finite query has no neighbours and a non-finite reference point is nobody's
+               neighbour; neither disturbs another row or cloud
+    self mode  the query cloud is the reference cloud and exclude_self is set: the pair j == i is skipped by index, not by distance,
+               so exact duplicates remain neighbours
+    count      count[i] = the number of neighbours of i, never clamped
+    order      "index" (the default): a row's neighbours in ascending j.  "distance": by (dist2, j) ascending, the lowest index among
+               equal distances, which is `knn`'s order
+On the 6 x 6 x 6 integer grid of `knn` above in self mode, radius 1.5: query 0 gets [1, 6, 7, 36, 37, 42] with dist2 [1, 1, 2, 1, 2, 2]
+in index order and [1, 6, 36, 7, 37, 42] in distance order (`knn`'s first six; 43 lies at dist2 3 > 2.25), query 215 gets [173, 178,
+179, 208, 209, 214], an interior point has 18 neighbours, and without self exclusion every count is one higher.  Radius 1: query 0
+gets [1, 6, 36], the bound being inclusive; radius sqrt(2) gives the same three.  Ten identical points, query 3: self mode gives
+[0, 1, 2, 4, ..., 9], count 9; without exclusion all ten.
+One scan kernel (`knn`'s direct loop: one thread per query, the reference cloud streamed through LDS) in three modes: the counts; the
+CSR fill, which is handed the exclusive prefix sum of the counts and recounts each row by the same predicate, so it writes exactly
+count[r] entries; the fixed-width fill, which writes the first K neighbours, pads with -1 / +inf and reports the unclamped count from
+the same pass.  A thread writes its own words only: no atomics, no workspace, the same bits run to run and in any batch position.
+There is no split form: few queries against many points (2048 against 100 000: 32 workgroups) leave most of the device idle.
 HIP tensors only: there is no CPU fallback (`voxel_pool`, `cluster_sizes` and `point_plane_distance`, plain torch, run on any device)."""
 from __future__ import annotations
 
@@ -1269,3 +1299,144 @@ def cluster_sizes(labels: Tensor, n_clusters) -> Tensor:
     rows = torch.where((lab >= 0) & (lab < Cn), lab, Cn) + (Cn + 1) * torch.arange(B, device=lab.device)[:, None]   # column C: skipped
     out = torch.bincount(rows.reshape(-1), minlength=B * (Cn + 1)).view(B, Cn + 1)[:, :Cn]
     return out[0] if single else out
+
+
+class RadiusNeighbors(NamedTuple):
+    """What `radius_search` returns without max_neighbors (module docstring: the definition): the neighbour lists of every query in
+    CSR form.  Row r = b * M + i, query i of cloud b, owns the entries [row_splits[r], row_splits[r + 1])."""
+    indices: Tensor            # int64 (nnz,): j in [0, N) of the row's own cloud
+    row_splits: Tensor         # int64 (B * M + 1,)
+    distances: Tensor | None   # fp32 (nnz,): sqrt(dist2)
+    counts: Tensor             # int64 (B, M): row_splits[r + 1] - row_splits[r]
+
+
+def _radius_arguments(query: Tensor, ref: Tensor | None, radius, exclude_self):
+    """What the three radius operators check before any device call -> q (B, M, 3), r (B, N, 3) or None (= q), single, N,
+    r2 = fp32(radius * radius) and exclude_self as a bool"""
+    q, single = _cloud(query)
+    r = None
+    if ref is not None:
+        r, rsingle = _cloud(ref)
+        _same_batching(q, single, r, rsingle, "query", "ref")
+    B, M, _ = q.shape
+    N = M if r is None else r.shape[1]
+    if B < 1 or M < 1 or N < 1:
+        raise ValueError("empty batch or cloud")
+    exclude_self = (ref is None) if exclude_self is None else bool(exclude_self)
+    if exclude_self and M != N:
+        raise ValueError(f"exclude_self needs the query cloud to be the reference cloud (M = {M}, N = {N})")
+    rad = _positive_f32(radius, "radius", (TypeError, ValueError, OverflowError))
+    r2 = C.c_float(rad * rad).value   # exact in double, rounded to fp32 once
+    if not (math.isfinite(r2) and r2 > 0):
+        raise ValueError(f"radius = {radius!r}: its square must be a finite fp32 number > 0")
+    return q, r, single, N, r2, exclude_self
+
+
+def _radius_inputs(q: Tensor, r: Tensor | None):
+    """the fp32 contiguous copies of both clouds (one copy when they are the same cloud) and their pointers"""
+    x, px = _f32(q)
+    y, py = (x, px) if r is None or r is q else _f32(r)
+    return x, px, y, py
+
+
+def _radius_counts(x: Tensor, px, py, N: int, r2: float, exclude_self: bool) -> Tensor:
+    """the count launch: int32 (B, M)"""
+    B, M, _ = x.shape
+    cnt = torch.empty(B, M, device=x.device, dtype=torch.int32)
+    _lib.check(_lib.load().gecco_radius_count_f32(px, py, _vp(cnt), B, M, N, r2, int(exclude_self), _stream()), "gecco_radius_count_f32")
+    return cnt
+
+
+def radius_count(query: Tensor, ref: Tensor | None = None, radius: float | None = None, exclude_self: bool | None = None) -> Tensor:
+    """The number of points of `ref` within `radius` of every point of `query` (module docstring: the definition; the bound
+    dist2 <= fp32(radius * radius) is inclusive).  query (B, M, 3) or (M, 3), ref (B, N, 3) or (N, 3) on the HIP device, any float dtype
+    and strides (computed on fp32 contiguous copies).  ref=None: the query cloud itself, and exclude_self then defaults to True (a point
+    does not count itself); with a ref it defaults to False.  Returns int64 (B, M), (M,) for a single cloud, never clamped.  One launch,
+    no synchronisation: the call can be captured in a hipGraph.  ValueError, before any device call, for bad shapes, mixed batching, a
+    radius that is not a finite fp32 number > 0 with a finite square > 0, exclude_self with M != N; GeccoHipError for CPU tensors.  No
+    gradient: counts."""
+    q, r, single, N, r2, exclude_self = _radius_arguments(query, ref, radius, exclude_self)
+    x, px, _, py = _radius_inputs(q, r)
+    cnt = _radius_counts(x, px, py, N, r2, exclude_self).long()
+    return cnt[0] if single else cnt
+
+
+def radius_search(query: Tensor, ref: Tensor | None = None, radius: float | None = None, exclude_self: bool | None = None,
+                  max_neighbors: int | None = None, order: str = "index", return_distances: bool = True):
+    """Every point of `ref` within `radius` of every point of `query` (module docstring: the definition).  Clouds, radius and
+    exclude_self as in `radius_count`.  order "index": a row's neighbours in ascending j; "distance": by (dist2, j) ascending, `knn`'s
+    order.
+
+    max_neighbors=None (Open3D's search_radius_vector_3d): a RadiusNeighbors in CSR form, indices int64 (nnz,), row_splits int64
+    (B * M + 1,), distances = sqrt(dist2) fp32 (nnz,) (None without return_distances) and counts int64 (B, M), (M,) for a single cloud.
+    A count launch, an int64 cumsum on the device, ONE host read of the total to size the outputs (the call's only synchronisation)
+    and a fill launch, none when nothing is within the radius.  The distance order is a stable sort of the index-ordered entries by
+    (row, dist2's bits), in torch.
+
+    max_neighbors=K: (idx int64 (B, M, K) padded with -1, dist fp32 padded with +inf or None without return_distances, counts int64
+    (B, M), unclamped); the batch dimension is dropped for single clouds.  No synchronisation: the call can be captured in a hipGraph.
+    order "index", 1 <= K <= N: the FIRST K neighbours by index, one launch (PointNet++'s ball query).  order "distance", 1 <= K <=
+    min(KNN_MAX_K, candidates of a query): the K NEAREST, cut at the radius (Open3D's search_hybrid_vector_3d): `knn`, the count
+    launch and a mask on dist2 <= r2.
+
+    ValueError, before any device call, for what `radius_count` refuses, an unknown order, max_neighbors that is not an integer or out
+    of range; GeccoHipError for CPU tensors.  No gradient: indices (and the distances are detached)."""
+    q, r, single, N, r2, exclude_self = _radius_arguments(query, ref, radius, exclude_self)
+    if order not in ("index", "distance"):
+        raise ValueError("order must be 'index' or 'distance'")
+    B, M, _ = q.shape
+    K = None
+    if max_neighbors is not None:
+        K = _integer(max_neighbors, "max_neighbors")
+        limit = N if order == "index" else min(KNN_MAX_K, N - int(exclude_self))
+        if not 1 <= K <= limit:
+            raise ValueError(f"max_neighbors = {K} is not in 1 .. {limit}" + (" (order 'distance': KNN_MAX_K and the candidates of a query)"
+                                                                             if order == "distance" else " (N)"))
+    x, px, y, py = _radius_inputs(q, r)
+    dev, lib, null = x.device, _lib.load(), C.c_void_p(0)
+    want_d2 = return_distances or (K is None and order == "distance")
+
+    if K is not None and order == "distance":   # the hybrid search: the k nearest, cut at the radius
+        idx, d2 = _knn(x, None if y is x else y, K, exclude_self, True, None)
+        cnt = _radius_counts(x, px, py, N, r2, exclude_self)
+        inside = d2 <= r2   # (dist2 >= 0 or +inf: the float order is the order of the bits)
+        out = [idx.long().masked_fill(~inside, -1), d2.sqrt().masked_fill(~inside, math.inf) if return_distances else None, cnt.long()]
+        return tuple(_unbatch(out, single))
+
+    if K is not None:   # the first K by index: one launch
+        idx = torch.empty(B, M, K, device=dev, dtype=torch.int32)
+        d2 = torch.empty(B, M, K, device=dev, dtype=torch.float32) if want_d2 else None
+        cnt = torch.empty(B, M, device=dev, dtype=torch.int32)
+        _lib.check(lib.gecco_radius_search_f32(px, py, null, _vp(idx), _ptr(d2), _vp(cnt), B, M, N, r2, int(exclude_self), K, _stream()),
+                   "gecco_radius_search_f32")
+        return tuple(_unbatch([idx.long(), d2.sqrt() if return_distances else None, cnt.long()], single))
+
+    cnt = _radius_counts(x, px, py, N, r2, exclude_self)
+    rows = B * M
+    splits = torch.zeros(rows + 1, device=dev, dtype=torch.int64)
+    torch.cumsum(cnt.view(-1), 0, dtype=torch.int64, out=splits[1:])   # exact; splits[:rows] is the exclusive prefix sum
+    nnz = int(splits[-1])   # the one synchronisation
+    idx = torch.empty(nnz, device=dev, dtype=torch.int32)
+    d2 = torch.empty(nnz, device=dev, dtype=torch.float32) if want_d2 else None
+    if nnz:
+        _lib.check(lib.gecco_radius_search_f32(px, py, _vp(splits), _vp(idx), _ptr(d2), null, B, M, N, r2, int(exclude_self), 0, _stream()),
+                   "gecco_radius_search_f32")
+        if order == "distance":   # stable: equal (row, dist2) keep their ascending j
+            row = torch.repeat_interleave(torch.arange(rows, device=dev), cnt.view(-1).long(), output_size=nnz)
+            perm = torch.sort((row << 32) | d2.view(torch.int32).long(), stable=True).indices
+            idx, d2 = idx[perm], d2[perm]
+    counts = cnt.long()
+    return RadiusNeighbors(idx.long(), splits, d2.sqrt() if return_distances else None, counts[0] if single else counts)
+
+
+def radius_outlier_mask(points: Tensor, radius: float, min_neighbors: int, return_counts: bool = False):
+    """The radius outlier filter of Open3D (`remove_radius_outlier`) and PCL (`RadiusOutlierRemoval`) on `radius_count`: keep_i =
+    count_i >= min_neighbors with count_i the points within `radius` of point i, itself excluded (Open3D's `indices.size() > nb_points`
+    counts the point among its own results).  points (B, N, 3) or (N, 3) -> a bool mask (B, N) or (N,), True for the points to keep;
+    with return_counts also the int64 counts of the same shape.  min_neighbors: an integer >= 0.  One launch, no synchronisation."""
+    min_neighbors = _integer(min_neighbors, "min_neighbors")
+    if min_neighbors < 0:
+        raise ValueError(f"min_neighbors = {min_neighbors} must be >= 0")
+    counts = radius_count(points, None, radius, True)
+    keep = counts >= min_neighbors
+    return (keep, counts) if return_counts else keep

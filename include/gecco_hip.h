@@ -1355,6 +1355,49 @@ size_t gecco_voxel_workspace_bytes(int B, int N);
 int gecco_dbscan_f32(const float* points, int32_t* labels, int32_t* n_clusters, int32_t* count, int32_t* rounds, int32_t* status, void* ws,
                      int B, int N, float eps2, int min_points, int max_rounds, void* stream);
 size_t gecco_dbscan_workspace_bytes(int B, int N, int max_rounds);
+/* Fixed-radius neighbour search between 3-D clouds (csrc/radius.hip): for every query of query (B, M, 3) EVERY point of ref (B, N, 3)
+ * of the same batch element within r of it; the second neighbourhood query of Open3D and PCL beside gecco_knn_f32
+ * (search_radius_vector_3d, search_hybrid_vector_3d, remove_radius_outlier / RadiusOutlierRemoval, PointNet++'s ball_query).  The
+ * reference has nothing of the kind and these entries replace nothing in it; without them the route is an M x N distance matrix
+ * (cdist <= r: 40 GB at 100 000 points against themselves) and nonzero over it, with aa + bb - 2ab roundings that put pairs at the
+ * bound on the wrong side.  tests/_radius_ref.py restates the definition in numpy float32.  Per batch element, for queries q_i
+ * (i < M) and reference points p_j (j < N), with radius2 a finite fp32 number > 0 (the caller's fp32(r * r), the product taken in
+ * double and rounded once: the eps2 of gecco_dbscan_f32):
+ *     dist2(q, p)  (dx dx + dy dy) + dz dz on the coordinate differences, every operation rounded to fp32 and none contracted into an
+ *                  FMA, a NaN replaced by +inf: the spelling of gecco_knn_f32
+ *     neighbour    j is a neighbour of i when dist2(q_i, p_j) <= radius2, the bound INCLUSIVE, compared on the bits as unsigned
+ *                  integers (dist2 >= 0 or +inf).  The bound is defined on radius2 and not on r because the two disagree:
+ *                  fp32(fp32(sqrt 2)^2) = 1.99999988, so r = fp32(sqrt 2) excludes a pair at dist2 = 2 although sqrt(2) rounds to r
+ *     non-finite   a query with a non-finite coordinate has no neighbours; a reference point with one is nobody's neighbour; neither
+ *                  disturbs another row or cloud
+ *     self mode    exclude_self (M == N, the query cloud is the reference cloud) skips the pair j == i by index, not by distance:
+ *                  exact duplicates of a point remain its neighbours
+ *     count        count[i] = the number of neighbours of i, never clamped
+ *     order        a row lists its neighbours in ascending j
+ * Worked example: the 6 x 6 x 6 integer grid (x slowest), self mode, radius2 = 2.25: query 0 gets 1, 6, 7, 36, 37, 42 with dist2 1, 1,
+ * 2, 1, 2, 2 (43 lies at dist2 3), query 215 gets 173, 178, 179, 208, 209, 214, an interior point has 18 neighbours, and without
+ * exclude_self every count is one higher; radius2 = 1: query 0 gets 1, 6, 36.  Ten identical points, query 3: self mode 0, 1, 2, 4,
+ * .., 9 (count 9), without it all ten.
+ * gecco_radius_count_f32: count (B, M) int32.  gecco_radius_search_f32 has two forms, one launch each:
+ *     CSR          row_start given (int64, B M entries: the exclusive prefix sum of the counts over the rows r = b M + i of the whole
+ *                  batch; the total may pass 2^31) and max_neighbors = 0: neighbour t of row r goes to idx[row_start[r] + t] (int32,
+ *                  an index into the row's own cloud) and, when d2 is given, its dist2 to d2[row_start[r] + t].  The row is
+ *                  recounted by the same predicate on the same bits: exactly count[r] entries are written, nothing else of idx and
+ *                  d2 is touched, and count is neither read nor written
+ *     fixed width  row_start NULL and max_neighbors = K >= 1: the first K neighbours of row r go to idx[r, 0 .. K) (d2 likewise), the
+ *                  remaining slots are padded with -1 (d2: +inf), every element of idx (B, M, K) and d2 (B, M, K) is written, and
+ *                  count (B, M), when given, takes the unclamped counts from the same pass.  K is not bounded by N
+ * One thread per query, the reference cloud streamed through LDS (the scan of gecco_knn_f32's direct form; there is no split form, so
+ * few queries against many points leave compute units idle).  A thread writes its own words only: no atomics, no workspace, no
+ * allocation, no host synchronisation (a call can be captured in a graph), and the outputs are the same bits run to run and in any
+ * batch position.  ref == query is allowed.  Returns before anything is enqueued (and sets gecco_last_error) with -2 for: null query /
+ * ref / count (count form) or query / ref / idx (search form), B, M or N < 1, a radius2 that is not a finite number > 0,
+ * exclude_self with M != N, row_start together with max_neighbors != 0 or neither of them (max_neighbors < 1 without row_start); with
+ * -3 for a grid above 2^31 - 1 workgroups.  Asynchronous on `stream`. */
+int gecco_radius_count_f32(const float* query, const float* ref, int32_t* count, int B, int M, int N, float radius2, int exclude_self,
+                           void* stream);
+int gecco_radius_search_f32(const float* query, const float* ref, const int64_t* row_start, int32_t* idx, float* d2, int32_t* count, int B,
+                            int M, int N, float radius2, int exclude_self, int max_neighbors, void* stream);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
