@@ -250,6 +250,10 @@ SIGNATURES = {
     "gecco_dbscan_workspace_bytes": (sz, [i, i, i]),
     "gecco_radius_count_f32": (i, [vp, vp, vp, i, i, i, fl, i, vp]),
     "gecco_radius_search_f32": (i, [vp, vp, vp, vp, vp, vp, i, i, i, fl, i, i, vp]),
+    "gecco_grid_keys_f32": (i, [vp, vp, fl, vp, i, i, vp]),
+    "gecco_grid_build_f32": (i, [vp] * 7 + [i, i, vp]),
+    "gecco_grid_radius_count_f32": (i, [vp] * 7 + [fl, vp, i, i, i, fl, i, vp]),
+    "gecco_grid_radius_search_f32": (i, [vp] * 7 + [fl, vp, vp, vp, i, i, i, fl, i, vp]),
     "gecco_convnext_stem_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),
     "gecco_convnext_dwconv_ln_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),
     "gecco_convnext_ln_patch2_f32": (i, [vp] * 4 + [i, i, i, i, fl, vp]),

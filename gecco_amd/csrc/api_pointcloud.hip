@@ -1,5 +1,6 @@
 // C ABI of libgecco_hip.so, part 4 of 4: point-cloud operators and metrics (distance matrix, Chamfer, set metrics, EMD,
-// Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, RANSAC registration, voxel grid, DBSCAN, radius search).
+// Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, RANSAC registration, voxel grid, DBSCAN, radius search
+// and its grid index).
 #include "api_common.h"
 
 using namespace gecco_api;
@@ -391,6 +392,71 @@ int gecco_radius_search_f32(const float* query, const float* ref, const int64_t*
                                  radius2, exclude_self ? 1 : 0, max_neighbors, (hipStream_t)stream);
     if (rc == -3) return fail(-3, "radius_search: the grid for B = %d, M = %d, N = %d passes 2^31 - 1 workgroups", B, M, N);
     TRY(rc, "radius_search");
+    return 0;
+}
+
+// the uniform-grid index of the fixed-radius search (grid.hip).  Every refusal is -2, null pointers included
+static int grid_cell_size(const char* who, float cell_size) {
+    if (!finite_positive(cell_size) || !finite_positive(1.0f / cell_size))
+        return fail(-2, "%s: cell_size = %g must be a finite number > 0 with a finite reciprocal", who, (double)cell_size);
+    return 0;
+}
+static int grid_points(const char* who, int B, int N) {
+    if (B < 1 || N < 1) return fail(-2, "%s: B = %d, N = %d must both be >= 1", who, B, N);
+    if (N > GECCO_VOXEL_MAX_POINTS) return fail(-2, "%s: N = %d above %d", who, N, GECCO_VOXEL_MAX_POINTS);
+    return 0;
+}
+int gecco_grid_keys_f32(const float* points, const float* origin, float cell_size, int64_t* keys, int B, int N, void* stream) {
+    if (!points || !keys) return fail(-2, "grid_keys: null argument");
+    if (const int bad = grid_points("grid_keys", B, N)) return bad;
+    if (const int bad = grid_cell_size("grid_keys", cell_size)) return bad;
+    static_assert(sizeof(long long) == sizeof(int64_t), "keys are written as long long");
+    const int rc = grid_keys_launch(points, origin, cell_size, reinterpret_cast<long long*>(keys), B, N, (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "grid_keys: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
+    TRY(rc, "grid_keys");
+    return 0;
+}
+int gecco_grid_build_f32(const float* points, const int64_t* sorted_keys, const int32_t* perm, float* sorted, int64_t* table_keys,
+                         int32_t* table_range, int32_t* n_in_grid, int B, int N, void* stream) {
+    if (!points || !sorted_keys || !perm || !sorted || !table_keys || !table_range || !n_in_grid) return fail(-2, "grid_build: null argument");
+    if (const int bad = grid_points("grid_build", B, N)) return bad;
+    const int rc = grid_build_launch(points, reinterpret_cast<const long long*>(sorted_keys), perm, sorted,
+                                     reinterpret_cast<long long*>(table_keys), table_range, n_in_grid, B, N, (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "grid_build: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
+    TRY(rc, "grid_build");
+    return 0;
+}
+static int grid_radius_common(const char* who, int B, int M, int N, float cell_size, float radius2, int exclude_self) {
+    if (const int bad = radius_common(who, B, M, N, radius2, exclude_self)) return bad;
+    if (N > GECCO_VOXEL_MAX_POINTS) return fail(-2, "%s: N = %d above %d", who, N, GECCO_VOXEL_MAX_POINTS);
+    if (const int bad = grid_cell_size(who, cell_size)) return bad;
+    if (!(radius2 <= cell_size * cell_size))
+        return fail(-2, "%s: radius2 = %g is above cell_size^2 = %g: build an index with a larger cell", who, (double)radius2,
+                    (double)(cell_size * cell_size));
+    return 0;
+}
+int gecco_grid_radius_count_f32(const float* query, const int32_t* qorder, const float* sorted, const int64_t* table_keys,
+                                const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size, int32_t* count,
+                                int B, int M, int N, float radius2, int exclude_self, void* stream) {
+    if (!query || !sorted || !table_keys || !table_range || !n_in_grid || !count) return fail(-2, "grid_radius_count: null argument");
+    if (const int bad = grid_radius_common("grid_radius_count", B, M, N, cell_size, radius2, exclude_self)) return bad;
+    const int rc = grid_radius_launch(query, qorder, sorted, reinterpret_cast<const long long*>(table_keys), table_range, n_in_grid, origin,
+                                      cell_size, nullptr, nullptr, nullptr, count, B, M, N, radius2, exclude_self ? 1 : 0, (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "grid_radius_count: the grid for B = %d, M = %d passes 2^31 - 1 workgroups", B, M);
+    TRY(rc, "grid_radius_count");
+    return 0;
+}
+int gecco_grid_radius_search_f32(const float* query, const int32_t* qorder, const float* sorted, const int64_t* table_keys,
+                                 const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size,
+                                 const int64_t* row_start, int32_t* idx, float* d2, int B, int M, int N, float radius2, int exclude_self,
+                                 void* stream) {
+    if (!query || !sorted || !table_keys || !table_range || !n_in_grid || !row_start || !idx) return fail(-2, "grid_radius_search: null argument");
+    if (const int bad = grid_radius_common("grid_radius_search", B, M, N, cell_size, radius2, exclude_self)) return bad;
+    const int rc = grid_radius_launch(query, qorder, sorted, reinterpret_cast<const long long*>(table_keys), table_range, n_in_grid, origin,
+                                      cell_size, reinterpret_cast<const long long*>(row_start), idx, d2, nullptr, B, M, N, radius2,
+                                      exclude_self ? 1 : 0, (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "grid_radius_search: the grid for B = %d, M = %d passes 2^31 - 1 workgroups", B, M);
+    TRY(rc, "grid_radius_search");
     return 0;
 }
 

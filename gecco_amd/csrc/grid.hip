@@ -1,0 +1,269 @@
+// A uniform-grid index for the fixed-radius neighbour search (gfx950): radius.hip answers "every point within r" by walking the whole
+// reference cloud for every query (100 000 candidates per query at 100 000 points); with the cloud sorted into cells of edge >= r a
+// query looks at the few cells its ball can reach (about 250 candidates at DESIGN.md's shape) and at nothing else.  The results are
+// radius.hip's, element for element and bit for bit: the cells only choose which candidates are tested, the test itself is unchanged.
+//
+// Definition (gecco_grid_keys_f32 / gecco_grid_build_f32 / gecco_grid_radius_count_f32 / gecco_grid_radius_search_f32,
+// include/gecco_hip.h; tests/_grid_ref.py restates it in numpy float32).
+//   cell     voxel.hip's, for voxel_size = cell_size (voxel_cell.h): per axis t = fp32(p - o), u = fp32(t * inv), c = floor(u), with
+//            inv = fp32(1 / cell_size) from the host; key = (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20).  A point with a
+//            non-finite u or a c outside [-2^20, 2^20) is OFF-GRID: its key is GRID_OFF = 2^63 (no real key has bit 63)
+//   order    the caller sorts the keys of a cloud as UNSIGNED integers, stably: cells ascend in key, a cell's points in original index,
+//            the off-grid points come last (the tail), also in original index.  perm[s] = the original index at sorted position s
+//   build    from position s: sorted[s] = (x, y, z, bits of perm[s]) as one 16-byte store; at a run's first position (key[s] != key[s-1])
+//            and at its last (key[s] != key[s+1]) the key is found or inserted in the cloud's open-addressing table of cap =
+//            GECCO_GRID_CAPACITY(N) slots (the power of two >= 2 N: load <= 0.5) by atomicCAS on the key word, voxel_insert_kernel's
+//            loop, idempotent for a key that is there, and range[slot] takes the run's start or end; n_in_grid = where the tail starts.
+//            No thread waits on another; the probe loop ends at an empty slot or at its own key and is bounded by cap all the same
+//   query    one thread per query q.  With R the host's fp32 reach (below), per axis the cells lo = cell(fp32(q - R)) .. hi =
+//            cell(fp32(q + R)), same u and floor, clamped to the grid; the box is walked with x outermost and z innermost, which is
+//            ascending key order; every occupied cell's run sorted[start .. end) is scanned, then the tail sorted[n_in_grid .. N).
+//            j is a neighbour when cloud_dist2_bits(q, p_j) <= r2_bits (radius.hip's predicate on radius.hip's bits); self mode skips
+//            j == i by the original index carried in .w.  COUNT writes count[b, i]; FILL_CSR writes neighbour t of row r to
+//            idx[row_start[r] + t] (d2 likewise) in scan order: ascending position in the sorted order
+// A thread writes its own words only: no atomics in the query, no workspace, no thread reads what another writes; the outputs are the
+// same bits run to run and in any batch position (which slot a key takes in the table may differ from run to run; what a query finds
+// there does not).  With qorder (a permutation of the queries, by cell) thread t answers query qorder[t] and writes THAT query's row:
+// the lanes of a wave probe the same cells and read the same runs, which the L2 then serves once.
+//
+// Why no neighbour is missed.  Let dist2(q, p) <= r2 and take one axis, d = fp32(q - p).  Rounding and adding non-negative numbers are
+// monotone, so fp32(d d) <= dist2 <= r2, hence the real d d <= r2 (1 + 2^-24) + 2^-150 (half a unit above r2, the second term when r2
+// is subnormal), and the real |q - p| <= |d| (1 + 2^-24).  grid_reach forms, in double and rounded UP to fp32,
+//     R >= sqrt(r2 (1 + 2^-23) + 2^-149) (1 + 2^-16),
+// which is above that bound (and above r (1 + 2^-16), since r2 >= r r (1 - 2^-24)).  So p >= q - R in the reals, and p being an fp32
+// number, p >= fp32(q - R): rounding to nearest never crosses a representable number.  Subtracting o, multiplying by inv > 0 and
+// floor are each monotone in fp32 as well, so cell(p) >= cell(fp32(q - R)) = lo, and symmetrically cell(p) <= hi.  An on-grid p has its
+// cell inside the grid, so clamping lo and hi to the grid loses nothing; an off-grid p is in the tail, which every query scans.  Extra
+// cells cost time, never correctness: the cells are a filter, membership is dist2 <= r2 alone.
+//
+// How wide the box can be.  The entry points refuse radius2 > fp32(cell_size^2), so for a normal r2 R <= cell_size (1 + 2^-15) and
+// 2 R inv <= 2.0001.  fp32(q + R) - fp32(q - R) <= 2 R + (the spacing of fp32 numbers at |q| + R), and inside the grid (|u| < 2^20)
+// the two roundings of t add at most 1/8 cell and the two of u at most 1/8.  So where fp32 resolves the coordinates to better than 0.7
+// of a cell, every cloud a grid makes sense for, u(q + R) - u(q - R) < 3 and the box touches AT MOST GRID_BOX = 4 CELLS PER AXIS, 64
+// in all (tests/test_grid_cpu.py asserts it on its inputs, coordinates near 1000 at r = 0.01 and cells at +-2^20 among them).  The
+// three loops are bounded by that constant.  Where the arithmetic gives a wider box all the same (coordinates fp32 resolves more
+// coarsely than a cell, a subnormal r2, a non-finite origin) the thread scans the whole sorted cloud instead, sorted[0 .. N): the
+// scan of radius.hip in another order, the same neighbours, rows still ascending in sorted position.  No input makes a thread walk
+// an unbounded box and none loses a neighbour to the bound.
+//
+// The radius may not exceed the cell edge; an index serves every smaller radius (at r = cell_size / 2 the 27 to 64 cells hold 8 times
+// the candidates that cells of edge r would: build another index when that matters).  The fixed-width forms stay on radius.hip.
+#include <cmath>
+
+#include "cloud_nn.h"
+#include "kernels.h"
+#include "launch_state.h"
+#include "voxel_cell.h"
+
+namespace {
+
+constexpr u64 GRID_OFF = 1ull << 63;   // the key of an off-grid point: above every real key as an unsigned integer
+constexpr int GRID_THREADS = 256;      // keys, build, fill
+constexpr int GRID_BOX = 4;            // cells per axis a query walks; a wider box is answered by a scan of the whole cloud
+constexpr int GRID_HALF = 1 << 20;
+
+enum { GRID_COUNT = 0, GRID_FILL_CSR = 1 };
+
+// grid: B * chunks blocks of GRID_THREADS points
+__global__ __launch_bounds__(GRID_THREADS) void grid_keys_kernel(const float* __restrict__ points, const float* __restrict__ origin, float inv,
+                                                                 u64* __restrict__ keys, int N, int chunks) {
+    const int b = (int)(blockIdx.x / (unsigned)chunks);
+    const int i = (int)(blockIdx.x % (unsigned)chunks) * GRID_THREADS + (int)threadIdx.x;
+    if (i >= N) return;
+    const float ox = origin ? origin[3 * b] : 0.f, oy = origin ? origin[3 * b + 1] : 0.f, oz = origin ? origin[3 * b + 2] : 0.f;
+    const VoxelCell v = voxel_cell(points + ((size_t)b * N + i) * 3, ox, oy, oz, inv);
+    keys[(size_t)b * N + i] = v.kept ? voxel_key(v) : GRID_OFF;
+}
+
+__global__ __launch_bounds__(GRID_THREADS) void grid_fill_kernel(u64* __restrict__ table_keys, size_t slots) {
+    const size_t step = (size_t)gridDim.x * GRID_THREADS;
+    for (size_t w = (size_t)blockIdx.x * GRID_THREADS + threadIdx.x; w < slots; w += step) table_keys[w] = VOXEL_EMPTY;
+}
+
+// grid: B * chunks blocks of GRID_THREADS sorted positions
+__global__ __launch_bounds__(GRID_THREADS) void grid_build_kernel(const float* __restrict__ points, const u64* __restrict__ keys,
+                                                                  const int* __restrict__ perm, f32x4* __restrict__ sorted,
+                                                                  u64* __restrict__ table_keys, int* __restrict__ table_range,
+                                                                  int* __restrict__ n_in_grid, int N, unsigned cap, int chunks) {
+    const int b = (int)(blockIdx.x / (unsigned)chunks);
+    const int s = (int)(blockIdx.x % (unsigned)chunks) * GRID_THREADS + (int)threadIdx.x;
+    if (s >= N) return;   // (no barrier below)
+    const u64* kb = keys + (size_t)b * N;
+    const u64 key = kb[s];
+    const int given = perm[(size_t)b * N + s];
+    const int j = (unsigned)given < (unsigned)N ? given : 0;   // a perm that is none reads inside the cloud all the same
+    const float* p = points + ((size_t)b * N + j) * 3;
+    sorted[(size_t)b * N + s] = f32x4{p[0], p[1], p[2], __int_as_float(j)};
+    if (key >> 63) {   // the tail
+        if (s == 0) n_in_grid[b] = 0;
+        return;
+    }
+    const u64 next = s + 1 < N ? kb[s + 1] : GRID_OFF;
+    if (next >> 63) n_in_grid[b] = s + 1;   // exactly one position of a sorted cloud is the last before the tail (or s = 0 above)
+    const bool head = s == 0 || kb[s - 1] != key, last = next != key;
+    if (!head && !last) return;
+    u64* tk = table_keys + (size_t)b * cap;
+    const unsigned mask = cap - 1;
+    unsigned h = voxel_hash(key, mask);
+    for (unsigned probe = 0; probe < cap; ++probe) {   // ends at an empty slot or at this key: at most N of the >= 2 N slots are taken
+        const u64 seen = atomicCAS(tk + h, VOXEL_EMPTY, key);
+        if (seen == VOXEL_EMPTY || seen == key) {
+            int* range = table_range + ((size_t)b * cap + h) * 2;
+            if (head) range[0] = s;
+            if (last) range[1] = s + 1;
+            break;
+        }
+        h = (h + 1) & mask;
+    }
+}
+
+// floor(u) of the fp32 coordinate x on one axis: voxel_cell's roundings
+static __device__ __forceinline__ float grid_u(float x, float o, float inv) {
+#pragma clang fp contract(off)
+    const float t = x - o;
+    return floorf(t * inv);
+}
+
+// grid: B * tiles blocks of T queries.  COUNT: count.  FILL_CSR: row_start, idx, d2 (nullable)
+template <int T, int MODE>
+__global__ __launch_bounds__(T) void grid_query_kernel(const float* __restrict__ query, const int* __restrict__ qorder,
+                                                       const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,
+                                                       const int2* __restrict__ table_range, const int* __restrict__ n_in_grid,
+                                                       const float* __restrict__ origin, float inv, float R,
+                                                       const long long* __restrict__ row_start, int* __restrict__ idx, float* __restrict__ d2,
+                                                       int* __restrict__ count, unsigned r2_bits, int M, int N, unsigned cap, int exclude_self,
+                                                       int tiles) {
+#pragma clang fp contract(off)
+    const int b = (int)(blockIdx.x / (unsigned)tiles);
+    const int t = (int)(blockIdx.x % (unsigned)tiles) * T + (int)threadIdx.x;
+    if (t >= M) return;   // (no barrier below)
+    const int i = qorder ? qorder[(size_t)b * M + t] : t;
+    if ((unsigned)i >= (unsigned)M) return;   // a qorder that is no permutation writes nothing outside the outputs
+    const size_t row = (size_t)b * M + i;
+    const float q[3] = {query[row * 3], query[row * 3 + 1], query[row * 3 + 2]};
+    const unsigned self = exclude_self ? (unsigned)i : 0xffffffffu;   // no j reaches 2^32 - 1
+    const size_t o = MODE == GRID_FILL_CSR ? (size_t)row_start[row] : 0;
+    const f32x4* sb = sorted + (size_t)b * N;
+    int n = 0;   // neighbours so far (n <= N)
+
+    auto scan = [&](int from, int to) {
+        for (int s = from; s < to; ++s) {
+            const f32x4 p = sb[s];   // one 16-byte load
+            const unsigned u = cloud_dist2_bits(q[0], q[1], q[2], p), j = __float_as_uint(p[3]);
+            if (u <= r2_bits && j != self) {
+                if (MODE == GRID_FILL_CSR) {
+                    idx[o + (size_t)n] = (int)j;
+                    if (d2) d2[o + (size_t)n] = __uint_as_float(u);
+                }
+                ++n;
+            }
+        }
+    };
+
+    if (cloud_finite3(q[0], q[1], q[2])) {   // (a non-finite query has dist2 = +inf to everything)
+        int lo[3], hi[3];
+        bool wide = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float org = origin ? origin[3 * b + a] : 0.f;
+            const float below = q[a] - R, above = q[a] + R;   // rounded to fp32 before the cell arithmetic
+            const float fl = grid_u(below, org, inv), fh = grid_u(above, org, inv);
+            // clamped to the grid: a bound beyond it on the far side leaves an empty box, a NaN (a non-finite origin) the widest one
+            lo[a] = fl >= -VOXEL_HALF ? (fl < VOXEL_HALF ? (int)fl : GRID_HALF) : -GRID_HALF;
+            hi[a] = fh < VOXEL_HALF ? (fh >= -VOXEL_HALF ? (int)fh : -GRID_HALF - 1) : GRID_HALF - 1;
+            wide = wide || hi[a] - lo[a] >= GRID_BOX;
+        }
+        if (wide) {   // header comment: never for coordinates that fp32 resolves inside a cell
+            scan(0, N);
+            lo[0] = 1, hi[0] = 0;
+        }
+        const u64* tk = table_keys + (size_t)b * cap;
+        const int2* tr = table_range + (size_t)b * cap;
+        const unsigned mask = cap - 1;
+        for (int cx = lo[0]; cx < lo[0] + GRID_BOX && cx <= hi[0]; ++cx)
+            for (int cy = lo[1]; cy < lo[1] + GRID_BOX && cy <= hi[1]; ++cy)
+                for (int cz = lo[2]; cz < lo[2] + GRID_BOX && cz <= hi[2]; ++cz) {   // ascending key
+                    const u64 key = voxel_key(cx, cy, cz);
+                    unsigned h = voxel_hash(key, mask);
+                    for (unsigned probe = 0; probe < cap; ++probe) {   // ends at the key or at an empty slot (load <= 0.5)
+                        const u64 seen = tk[h];
+                        if (seen == key) {
+                            const int2 r = tr[h];
+                            scan(max(r.x, 0), min(r.y, N));
+                            break;
+                        }
+                        if (seen == VOXEL_EMPTY) break;
+                        h = (h + 1) & mask;
+                    }
+                }
+        if (!wide) scan(min(max(n_in_grid[b], 0), N), N);   // the off-grid tail
+    }
+    if (MODE == GRID_COUNT) count[row] = n;
+}
+
+// The reach R of a query's box (header comment): the least fp32 number >= sqrt(r2 (1 + 2^-23) + 2^-149) (1 + 2^-16), formed in double
+float grid_reach(float r2) {
+    const double bound = std::sqrt((double)r2 * (1.0 + 0x1p-23) + 0x1p-149) * (1.0 + 0x1p-16);
+    float R = (float)bound;
+    if ((double)R < bound) R = std::nextafterf(R, INFINITY);
+    return R;
+}
+
+}  // namespace
+
+// key[b, i] of every point.  -2: arguments out of range, -3: the grid would pass 2^31 - 1 workgroups
+int grid_keys_launch(const float* points, const float* origin, float cell_size, long long* keys, int B, int N, hipStream_t st) {
+    if (!points || !keys || B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return -2;
+    const int chunks = (N + GRID_THREADS - 1) / GRID_THREADS;
+    if ((long long)B * chunks > 0x7fffffffLL) return -3;
+    const float inv = 1.0f / cell_size;   // fp32, once, on the host
+    hipLaunchKernelGGL(grid_keys_kernel, dim3((unsigned)(B * chunks)), dim3(GRID_THREADS), 0, st, points, origin, inv,
+                       reinterpret_cast<u64*>(keys), N, chunks);
+    return (int)hipGetLastError();
+}
+
+// Two launches: the table filled with the empty key, then the build.  -2: arguments out of range, -3: a grid would pass 2^31 - 1 workgroups
+int grid_build_launch(const float* points, const long long* keys, const int* perm, float* sorted, long long* table_keys, int* table_range,
+                      int* n_in_grid, int B, int N, hipStream_t st) {
+    if (!points || !keys || !perm || !sorted || !table_keys || !table_range || !n_in_grid || B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS)
+        return -2;
+    const int chunks = (N + GRID_THREADS - 1) / GRID_THREADS;
+    if ((long long)B * chunks > 0x7fffffffLL) return -3;
+    const size_t cap = GECCO_GRID_CAPACITY(N), slots = (size_t)B * cap;
+    const size_t fill_blocks = (slots + GRID_THREADS - 1) / GRID_THREADS, fill_cap = (size_t)device_cus() * 8;
+    hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)(fill_blocks < fill_cap ? fill_blocks : fill_cap)), dim3(GRID_THREADS), 0, st,
+                       reinterpret_cast<u64*>(table_keys), slots);
+    hipLaunchKernelGGL(grid_build_kernel, dim3((unsigned)(B * chunks)), dim3(GRID_THREADS), 0, st, points, reinterpret_cast<const u64*>(keys),
+                       perm, reinterpret_cast<f32x4*>(sorted), reinterpret_cast<u64*>(table_keys), table_range, n_in_grid, N, (unsigned)cap,
+                       chunks);
+    return (int)hipGetLastError();
+}
+
+// One launch.  idx null: COUNT (count required, row_start and d2 null).  Otherwise FILL_CSR (row_start required, d2 nullable, count not
+// written).  -2: arguments out of range (radius2 above fp32(cell_size^2) among them), -3: the grid would pass 2^31 - 1 workgroups
+int grid_radius_launch(const float* query, const int* qorder, const float* sorted, const long long* table_keys, const int* table_range,
+                       const int* n_in_grid, const float* origin, float cell_size, const long long* row_start, int* idx, float* d2, int* count,
+                       int B, int M, int N, float r2, int exclude_self, hipStream_t st) {
+    if (!query || !sorted || !table_keys || !table_range || !n_in_grid || B < 1 || M < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return -2;
+    if (!(r2 > 0.f) || !(r2 <= 3.402823466e38f) || !(r2 <= cell_size * cell_size) || (exclude_self && M != N)) return -2;
+    if (idx ? !row_start : !count || row_start || d2) return -2;
+    const CloudPlan p = cloud_plan(B, M, N, 1, false, 256, device_cus());
+    if (!p.fits()) return -3;
+    const unsigned r2_bits = __builtin_bit_cast(unsigned, r2), cap = (unsigned)GECCO_GRID_CAPACITY(N);
+    const float inv = 1.0f / cell_size, R = grid_reach(r2);
+    const int self = exclude_self ? 1 : 0;
+    const u64* tk = reinterpret_cast<const u64*>(table_keys);
+    const int2* tr = reinterpret_cast<const int2*>(table_range);
+    const f32x4* sp = reinterpret_cast<const f32x4*>(sorted);
+    return dispatch_T(p.T, [&](auto t) -> int {
+        constexpr int T = decltype(t)::value;
+        const dim3 grid((unsigned)p.blocks), block(T);
+        if (!idx)
+            hipLaunchKernelGGL((grid_query_kernel<T, GRID_COUNT>), grid, block, 0, st, query, qorder, sp, tk, tr, n_in_grid, origin, inv, R,
+                               row_start, idx, d2, count, r2_bits, M, N, cap, self, p.tiles);
+        else
+            hipLaunchKernelGGL((grid_query_kernel<T, GRID_FILL_CSR>), grid, block, 0, st, query, qorder, sp, tk, tr, n_in_grid, origin, inv, R,
+                               row_start, idx, d2, count, r2_bits, M, N, cap, self, p.tiles);
+        return (int)hipGetLastError();
+    });
+}

@@ -551,6 +551,16 @@ int dbscan_launch(const float* points, int* labels, int* n_clusters, int* count,
 // workgroups
 int radius_launch(const float* query, const float* ref, const long long* row_start, int* idx, float* d2, int* count, int B, int M, int N,
                   float r2, int exclude_self, int K, hipStream_t st);
+// grid.hip — the uniform-grid index of the fixed-radius search (definition: gecco_grid_build_f32).  keys: one launch, origin nullable.
+// build: the table fill and one launch over the sorted positions.  radius: one launch over the index; qorder, origin, d2 nullable; idx
+// null: the counts alone (count required), otherwise the CSR fill (row_start required).  -2: arguments out of range (a radius2 above
+// fp32(cell_size^2) among them), -3: the grid would pass 2^31 - 1 workgroups
+int grid_keys_launch(const float* points, const float* origin, float cell_size, long long* keys, int B, int N, hipStream_t st);
+int grid_build_launch(const float* points, const long long* keys, const int* perm, float* sorted, long long* table_keys, int* table_range,
+                      int* n_in_grid, int B, int N, hipStream_t st);
+int grid_radius_launch(const float* query, const int* qorder, const float* sorted, const long long* table_keys, const int* table_range,
+                       const int* n_in_grid, const float* origin, float cell_size, const long long* row_start, int* idx, float* d2, int* count,
+                       int B, int M, int N, float r2, int exclude_self, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

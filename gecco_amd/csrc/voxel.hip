@@ -6,8 +6,8 @@
 // u = fp32(t * inv) with inv = fp32(1 / s) from the host, c = floor(u); a point with a non-finite u or a c outside [-2^20, 2^20) is
 // dropped.  key = (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20).  Voxels are the distinct keys, numbered by first occurrence.
 // frac = fp32(u - c), q = (uint64) trunc(frac * 2^32), S = the integer sum of q over the voxel, centroid = fp32(double(o) + (double(c) +
-// double(S) / (double(count) * 2^32)) * double(s)).  voxel_cell spells the fp32 roundings out, voxel_finalise_kernel the fp64 ones; both
-// with contraction off (u - c would otherwise fuse with the product that made u).
+// double(S) / (double(count) * 2^32)) * double(s)).  voxel_cell (voxel_cell.h, shared with grid.hip) spells the fp32 roundings out,
+// voxel_finalise_kernel the fp64 ones; both with contraction off (u - c would otherwise fuse with the product that made u).
 //
 // Why a table and integer sums, not a sort.  A sort of N 64-bit keys costs several passes over the cloud and gives an order (by key)
 // that nobody asked for; the first-occurrence order wanted here is a scan over the POINT index, which needs no sort at all once every
@@ -30,56 +30,13 @@
 #include "common.h"
 #include "kernels.h"
 #include "launch_state.h"
+#include "voxel_cell.h"
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr u64 VOXEL_EMPTY = ~0ull;
 constexpr int VOXEL_THREADS = 256;        // insert, accumulate, finalise, fill
 constexpr int VOXEL_RANK_THREADS = 1024;  // rank: one workgroup per cloud
 constexpr int VOXEL_RANK_ITEMS = 4;       // consecutive points per thread and scan step: chunks of 4096 points
-constexpr float VOXEL_HALF = 1048576.f;   // 2^20
-
-struct VoxelCell {
-    int c[3];
-    u64 q[3];
-    bool kept;
-};
-
-// the fp32 roundings of the definition: t = p - o, u = t * inv, c = floor(u), frac = u - c, q = trunc(frac * 2^32)
-static __device__ __forceinline__ VoxelCell voxel_cell(const float* __restrict__ p, float ox, float oy, float oz, float inv) {
-#pragma clang fp contract(off)
-    VoxelCell r;
-    const float o[3] = {ox, oy, oz};
-    r.kept = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float t = p[a] - o[a];
-        const float u = t * inv;
-        const float c = floorf(u);
-        const bool ok = __builtin_isfinite(u) && c >= -VOXEL_HALF && c < VOXEL_HALF;
-        r.kept = r.kept && ok;
-        const float frac = u - c;                                   // in [0, 1]; 1.0 for a tiny negative u
-        r.c[a] = ok ? (int)c : 0;
-        r.q[a] = ok ? (u64)(frac * 4294967296.0f) : 0ull;           // exact scaling, truncation
-    }
-    return r;
-}
-
-static __device__ __forceinline__ u64 voxel_key(const VoxelCell& v) {
-    return ((u64)(unsigned)(v.c[0] + (1 << 20)) << 42) | ((u64)(unsigned)(v.c[1] + (1 << 20)) << 21) | (u64)(unsigned)(v.c[2] + (1 << 20));
-}
-
-// murmur3's 64-bit finaliser: every bit of the key reaches every bit of the slot index, so cells along one axis, or a power-of-two
-// stride apart, spread over the table instead of piling into one probe run
-static __device__ __forceinline__ unsigned voxel_hash(u64 k, unsigned mask) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return (unsigned)k & mask;
-}
 
 // words [0, ones) = ~0, words [ones, ones + zeros) = 0
 __global__ __launch_bounds__(VOXEL_THREADS) void voxel_fill_kernel(unsigned* __restrict__ ws, size_t ones, size_t zeros) {

@@ -1398,6 +1398,57 @@ int gecco_radius_count_f32(const float* query, const float* ref, int32_t* count,
                            void* stream);
 int gecco_radius_search_f32(const float* query, const float* ref, const int64_t* row_start, int32_t* idx, float* d2, int32_t* count, int B,
                             int M, int N, float radius2, int exclude_self, int max_neighbors, void* stream);
+/* A uniform-grid index for the fixed-radius search (csrc/grid.hip): the two entries above walk the whole reference cloud for every
+ * query; with the cloud sorted into cells of edge cell_size >= r a query tests the points of the cells its ball can reach and no
+ * others.  The neighbours, their counts and the bits of dist2 are those of gecco_radius_count_f32 / gecco_radius_search_f32; only the
+ * order of a CSR row differs (below).  tests/_grid_ref.py restates the definition in numpy float32.  Per batch element:
+ *     cell        that of gecco_voxel_downsample_f32 for voxel_size = cell_size (a finite fp32 number > 0 with a finite fp32(1 /
+ *                 cell_size)): per axis t = fp32(p - o), u = fp32(t * inv), c = floor(u), key = (cx + 2^20) << 42 | (cy + 2^20) << 21 |
+ *                 (cz + 2^20).  A point that the voxel filter would drop (a non-finite u, a c outside [-2^20, 2^20)) is OFF-GRID: its
+ *                 key is 2^63, the sign bit alone (no real key has bit 63).  gecco_grid_keys_f32 writes key (B, N) int64
+ *     order       the CALLER sorts every cloud's keys as UNSIGNED integers, stably (a signed sort of key ^ 2^63 is that order): cells
+ *                 ascend in key, a cell's points in original index, the off-grid points come last (the tail) in original index.
+ *                 perm (B, N) int32: the original index at each sorted position
+ *     build       gecco_grid_build_f32, from the sorted keys and perm: sorted (B, N, 4) fp32 = (x, y, z, the bits of perm) per
+ *                 position; table_keys (B, cap) int64 and table_range (B, cap, 2) int32 with cap = GECCO_GRID_CAPACITY(N), the power
+ *                 of two >= 2 N: an open-addressing table (linear probing from the hash of gecco_voxel_downsample_f32; an empty slot
+ *                 holds -1) that maps a key to its run [start, end) of sorted positions (range words of empty slots are not
+ *                 written); n_in_grid (B) int32: where the tail starts.  Which slot a key takes may differ from run to run, what a
+ *                 lookup finds does not.  Two launches (the table fill and the build); compare-and-swap on the key word, no thread
+ *                 waits on another, every probe loop is bounded by cap
+ *     query       with R the least fp32 number >= sqrt(radius2 (1 + 2^-23) + 2^-149) (1 + 2^-16), formed in double by the library, a
+ *                 query q looks, per axis, at the cells cell(fp32(q - R)) .. cell(fp32(q + R)) (same u and floor, clamped to the
+ *                 grid), x outermost and z innermost (ascending key), then at the tail.  A box wider than 4 cells on an axis (never
+ *                 where fp32 resolves the coordinates inside a cell) is answered by a scan of all N sorted positions instead.  Among
+ *                 those candidates j is a neighbour exactly when gecco_radius_search_f32 says so: dist2(q, p_j) <= radius2 on the
+ *                 bits, exclude_self skipping j == i by index.  csrc/grid.hip proves that no neighbour lies outside the box
+ *     rows        gecco_grid_radius_search_f32 is the CSR form of gecco_radius_search_f32 (row_start required, no max_neighbors):
+ *                 a row lists its neighbours in ascending SORTED POSITION, that is by (key, j) with the tail last; sort a row by j
+ *                 for the order of gecco_radius_search_f32
+ *     qorder      (B, M) int32 or NULL: thread t answers query qorder[b, t] and writes that query's row, so that neighbouring threads
+ *                 read the same cells.  A permutation of 0 .. M - 1 per cloud (perm itself in self mode); entries outside 0 .. M - 1
+ *                 are skipped, their rows are not written
+ * Worked example: the 6 x 6 x 6 integer grid (x slowest) of the radius block, cell_size 1.5, origin 0: coordinates {0, 1 | 2 | 3, 4 | 5}
+ * share a cell per axis, 64 cells.  Self mode, radius2 = 2.25: query 0 gets 1, 6, 7, 36, 37, 42, all six in its own cell (0, 0, 0), so
+ * the row is also ascending in j; query 43 = (1, 1, 1) has 18 neighbours in 7 cells and its row is 1, 6, 7, 36, 37, 42 (cell (0, 0,
+ * 0)), 8, 38, 44 (cell (0, 0, 1)), 13, 48, 49 (cell (0, 1, 0)), 50, then 73, 78, 79, 80, 85 from the cells with cx = 1: by cell
+ * first, by j inside a cell.
+ * Every entry is asynchronous on `stream`, allocates nothing and does not synchronise; the query writes with no atomics and no
+ * workspace, the same bits run to run and in any batch position.  origin (B, 3) may be NULL (zeros); d2 may be NULL.  Return -2 before
+ * anything is enqueued (and gecco_last_error) for: a null required pointer, B, M or N < 1, N above GECCO_VOXEL_MAX_POINTS, a cell_size
+ * that is not a finite number > 0 with a finite reciprocal, a radius2 that is not a finite number > 0 or is above fp32(cell_size *
+ * cell_size) (build an index with a larger cell), exclude_self with M != N; -3 for a grid above 2^31 - 1 workgroups. */
+#define GECCO_GRID_CAPACITY(N) GECCO_VOXEL_CAPACITY(N)
+int gecco_grid_keys_f32(const float* points, const float* origin, float cell_size, int64_t* keys, int B, int N, void* stream);
+int gecco_grid_build_f32(const float* points, const int64_t* sorted_keys, const int32_t* perm, float* sorted, int64_t* table_keys,
+                         int32_t* table_range, int32_t* n_in_grid, int B, int N, void* stream);
+int gecco_grid_radius_count_f32(const float* query, const int32_t* qorder, const float* sorted, const int64_t* table_keys,
+                                const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size, int32_t* count,
+                                int B, int M, int N, float radius2, int exclude_self, void* stream);
+int gecco_grid_radius_search_f32(const float* query, const int32_t* qorder, const float* sorted, const int64_t* table_keys,
+                                 const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size,
+                                 const int64_t* row_start, int32_t* idx, float* d2, int B, int M, int N, float radius2, int exclude_self,
+                                 void* stream);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
