@@ -1,6 +1,6 @@
 // C ABI of libgecco_hip.so, part 4 of 4: point-cloud operators and metrics (distance matrix, Chamfer, set metrics, EMD,
 // Sinkhorn, farthest-point sampling, kNN, normals, ICP, FPFH and feature matching, RANSAC registration, voxel grid, DBSCAN, radius search
-// and its grid index).
+// and its grid index, ISS keypoints).
 #include "api_common.h"
 
 using namespace gecco_api;
@@ -457,6 +457,34 @@ int gecco_grid_radius_search_f32(const float* query, const int32_t* qorder, cons
                                       exclude_self ? 1 : 0, (hipStream_t)stream);
     if (rc == -3) return fail(-3, "grid_radius_search: the grid for B = %d, M = %d passes 2^31 - 1 workgroups", B, M);
     TRY(rc, "grid_radius_search");
+    return 0;
+}
+
+// ISS keypoints on the grid index (iss.hip).  Every refusal is -2, null pointers included; eigenvalues, counts and origin nullable
+static int iss_radius2(const char* name, float cell_size, float radius2) {
+    if (!finite_positive(radius2)) return fail(-2, "iss_keypoints: %s = %g must be a finite number > 0", name, (double)radius2);
+    if (!(radius2 <= cell_size * cell_size))
+        return fail(-2, "iss_keypoints: %s = %g is above cell_size^2 = %g: build an index with a larger cell", name, (double)radius2,
+                    (double)(cell_size * cell_size));
+    return 0;
+}
+int gecco_iss_keypoints_f32(const float* sorted, const int64_t* table_keys, const int32_t* table_range, const int32_t* n_in_grid,
+                            const float* origin, float cell_size, double* saliency, double* eigenvalues, int32_t* counts, uint8_t* mask, int B,
+                            int N, float salient_radius2, float non_max_radius2, double gamma_21, double gamma_32, int min_neighbors,
+                            void* stream) {
+    if (!sorted || !table_keys || !table_range || !n_in_grid || !saliency || !mask) return fail(-2, "iss_keypoints: null argument");
+    if (const int bad = grid_points("iss_keypoints", B, N)) return bad;
+    if (const int bad = grid_cell_size("iss_keypoints", cell_size)) return bad;
+    if (const int bad = iss_radius2("salient_radius2", cell_size, salient_radius2)) return bad;
+    if (const int bad = iss_radius2("non_max_radius2", cell_size, non_max_radius2)) return bad;
+    if (!(gamma_21 > 0.0) || !(gamma_21 <= 1.7976931348623157e308) || !(gamma_32 > 0.0) || !(gamma_32 <= 1.7976931348623157e308))
+        return fail(-2, "iss_keypoints: gamma_21 = %g and gamma_32 = %g must be finite numbers > 0", gamma_21, gamma_32);
+    if (min_neighbors < 1) return fail(-2, "iss_keypoints: min_neighbors = %d must be >= 1", min_neighbors);
+    const int rc = iss_launch(sorted, reinterpret_cast<const long long*>(table_keys), table_range, n_in_grid, origin, cell_size, saliency,
+                              eigenvalues, counts, mask, B, N, salient_radius2, non_max_radius2, gamma_21, gamma_32, min_neighbors,
+                              (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "iss_keypoints: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
+    TRY(rc, "iss_keypoints");
     return 0;
 }
 

@@ -124,7 +124,8 @@ static __device__ __forceinline__ float grid_u(float x, float o, float inv) {
     return floorf(t * inv);
 }
 
-// grid: B * tiles blocks of T queries.  COUNT: count.  FILL_CSR: row_start, idx, d2 (nullable)
+// grid: B * tiles blocks of T queries.  COUNT: count.  FILL_CSR: row_start, idx, d2 (nullable).  iss.hip's iss_walk is this kernel's
+// walk (the reach, the box, the probe, the runs, the tail, the wide scan) written out again for a visitor: THE TWO CHANGE TOGETHER
 template <int T, int MODE>
 __global__ __launch_bounds__(T) void grid_query_kernel(const float* __restrict__ query, const int* __restrict__ qorder,
                                                        const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,

@@ -1,0 +1,266 @@
+// ISS keypoints (Intrinsic Shape Signatures, Zhong 2009; Open3D's compute_iss_keypoints, PCL's ISSKeypoint3D) on the grid index of
+// grid.hip (gfx950): the points whose neighbourhood is not flat, not a line and not isotropic, thinned by non-maximum suppression.  Both
+// steps pool over "every point within a radius", the unbounded neighbourhood the grid index serves; nothing here writes a neighbour
+// list: a thread walks the cells its ball can reach and accumulates in registers.
+//
+// Definition (gecco_iss_keypoints_f32, include/gecco_hip.h; tests/_iss_ref.py restates it in numpy).  Per cloud, with r2s =
+// fp32(salient_radius^2) and r2n = fp32(non_max_radius^2) from the caller:
+//   ball       B_r(i) = the j with cloud_dist2_bits(p_i, p_j) <= r2 bits: radius.hip's predicate, the point itself INCLUDED by index
+//              (Open3D's radius search returns the query).  A non-finite point is in nobody's ball, not even its own.  The ball is
+//              visited in ascending sorted position of the index (by (cell key, j), the off-grid tail last): grid.hip's scan order,
+//              and part of the definition as it is of the grid-ordered rows there
+//   count      m_i = |B_r2s(i)|
+//   moments    in fp64 on the fp32 coordinates, about the point itself, every operation rounded and none contracted:
+//              d = double(p_j) - double(p_i) per axis;  S1 = sum d (3 sums), S2 = sum d d^T (xx, xy, xz, yy, yz, zz), each from 0 in
+//              ball order;  inv = 1 / m;  mu = S1 inv;  C_ab = S2_ab inv - mu_a mu_b.  |d| <= the radius, so the raw moments cancel
+//              against the radius and not against the cloud's distance from the origin
+//   eigen      big = max |C_ab|;  A = C sc with sc = 1 / big;  ISS_JACOBI_SWEEPS = 8 cyclic Jacobi sweeps over (0,1), (0,2), (1,2) with
+//              the guarded rotation of rigid_fit.h (icp_rotate: a non-finite theta gives t = 0, a theta whose square would overflow
+//              t = 1 / (2 theta)), a fixed count;  lambda = diag big, negative roundings clamped to 0, sorted lambda0 <= lambda1 <= lambda2
+//   candidate  m_i >= min_neighbors, big a positive finite number (all of the ball identical: not a candidate, Open3D's
+//              cov.isZero()), lambda1 < gamma_21 lambda2, lambda0 < gamma_32 lambda1 (fp64 products, no division) and lambda0 > 0.
+//              saliency_i = lambda0 for a candidate, 0 otherwise;  eigenvalues_i = 0 where m_i < min_neighbors or big is not a
+//              positive finite number
+//   keypoint   i is a candidate, |B_r2n(i)| >= min_neighbors, and no j in B_r2n(i) has saliency_j > saliency_i (fp64 compare).  Equal
+//              saliencies keep each other, as Open3D's IsLocalMaxima does: two exact duplicates of a keypoint are both kept
+// A point's result depends on the cloud and on the index's cell_size and origin, which fix the order of the sums, and on nothing else:
+// the same bits run to run, in any batch position and at any workgroup size.  Two indices with different cells may differ in the last
+// bits of the eigenvalues (another order of the same sums); counts do not.
+//
+// Two launches, one thread per SORTED POSITION in both: thread t of a cloud owns the point at sorted[t], whose 16-byte load gives the
+// coordinates and, in .w, the original index i its outputs go to.  The lanes of a wave are neighbours in the sorted order, so they
+// probe the same cells and read the same runs.  iss_saliency_kernel walks the box of r2s, adds the count and the nine fp64 sums in
+// registers, solves the 3 x 3 problem in registers (the matrix and the rotations are scalars: no indexed local array, no scratch;
+// plane.hip's refit keeps arrays in scratch because one thread per cloud runs it, here every thread does) and writes saliency,
+// eigenvalues and counts at i.  iss_select_kernel starts from saliency[i] > 0 (other threads write false and return), walks the box of
+// r2n, counts the ball and compares saliency[j], a gather by the index carried in .w, and writes the mask byte.  A thread writes its own
+// words only: no atomics, no LDS, no workspace, no thread waits on another, every loop is bounded by a constant, by cap or by N.
+//
+// The walk (grid_reach, the clamped per-axis cells, at most GRID_BOX cells per axis, the table probe, the runs, the tail, the scan of
+// all N sorted positions for a wide box) is grid_query_kernel's, written out again in iss_walk below; grid.hip's header proves that it
+// misses no neighbour and bounds every loop.  THE TWO CHANGE TOGETHER.  It is a copy and not a shared header because the query
+// kernel's registers (38 and 42 VGPRs, no scratch) and its time at 100 000 points were not re-measured with the loop moved behind a
+// visitor template; cloud_nn.h records the same decision, measured, for the kNN loop.
+#include <cmath>
+
+#include "cloud_nn.h"
+#include "kernels.h"
+#include "launch_state.h"
+#include "voxel_cell.h"
+
+namespace {
+
+constexpr int ISS_BOX = 4;             // grid.hip's GRID_BOX: cells per axis a thread walks; a wider box scans the whole cloud
+constexpr int ISS_HALF = 1 << 20;      // grid.hip's GRID_HALF
+constexpr int ISS_JACOBI_SWEEPS = 8;   // rigid_fit.h's count: quadratic convergence, fp64 by the fifth
+
+// floor(u) of the fp32 coordinate x on one axis: voxel_cell's roundings (grid.hip's grid_u)
+static __device__ __forceinline__ float iss_u(float x, float o, float inv) {
+#pragma clang fp contract(off)
+    const float t = x - o;
+    return floorf(t * inv);
+}
+
+// grid_query_kernel's walk for the finite point (qx, qy, qz) of cloud b: visit(p) for every sorted entry p of the ball, in ascending
+// sorted position.  sb, tk, tr: the cloud's own sorted points and table
+template <class Visit>
+static __device__ __forceinline__ void iss_walk(float qx, float qy, float qz, const f32x4* __restrict__ sb, const u64* __restrict__ tk,
+                                                const int2* __restrict__ tr, int tail, const float* __restrict__ origin, int b, float inv,
+                                                float R, unsigned r2_bits, int N, unsigned cap, Visit visit) {
+#pragma clang fp contract(off)
+    auto scan = [&](int from, int to) {
+        for (int s = from; s < to; ++s) {
+            const f32x4 p = sb[s];   // one 16-byte load
+            if (cloud_dist2_bits(qx, qy, qz, p) <= r2_bits) visit(p);
+        }
+    };
+    const float q[3] = {qx, qy, qz};
+    int lo[3], hi[3];
+    bool wide = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float org = origin ? origin[3 * b + a] : 0.f;
+        const float below = q[a] - R, above = q[a] + R;   // rounded to fp32 before the cell arithmetic
+        const float fl = iss_u(below, org, inv), fh = iss_u(above, org, inv);
+        // clamped to the grid: a bound beyond it on the far side leaves an empty box, a NaN (a non-finite origin) the widest one
+        lo[a] = fl >= -VOXEL_HALF ? (fl < VOXEL_HALF ? (int)fl : ISS_HALF) : -ISS_HALF;
+        hi[a] = fh < VOXEL_HALF ? (fh >= -VOXEL_HALF ? (int)fh : -ISS_HALF - 1) : ISS_HALF - 1;
+        wide = wide || hi[a] - lo[a] >= ISS_BOX;
+    }
+    if (wide) {   // grid.hip's header: never for coordinates that fp32 resolves inside a cell
+        scan(0, N);
+        return;
+    }
+    const unsigned mask = cap - 1;
+    for (int cx = lo[0]; cx < lo[0] + ISS_BOX && cx <= hi[0]; ++cx)
+        for (int cy = lo[1]; cy < lo[1] + ISS_BOX && cy <= hi[1]; ++cy)
+            for (int cz = lo[2]; cz < lo[2] + ISS_BOX && cz <= hi[2]; ++cz) {   // ascending key
+                const u64 key = voxel_key(cx, cy, cz);
+                unsigned h = voxel_hash(key, mask);
+                for (unsigned probe = 0; probe < cap; ++probe) {   // ends at the key or at an empty slot (load <= 0.5)
+                    const u64 seen = tk[h];
+                    if (seen == key) {
+                        const int2 r = tr[h];
+                        scan(max(r.x, 0), min(r.y, N));
+                        break;
+                    }
+                    if (seen == VOXEL_EMPTY) break;
+                    h = (h + 1) & mask;
+                }
+            }
+    scan(min(max(tail, 0), N), N);   // the off-grid tail
+}
+
+static __device__ __forceinline__ bool iss_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and inf
+
+// icp_rotate (rigid_fit.h) for a symmetric 3 x 3 matrix held in scalars, eigenvalues only: the rotation that annihilates a_pq; arp, arq
+// are the entries of the third row r against p and q.  Same guard, same order of operations, none contracted
+static __device__ __forceinline__ void iss_rotate(double& app, double& aqq, double& apq, double& arp, double& arq) {
+#pragma clang fp contract(off)
+    double t = 0.0;
+    if (apq != 0.0) {
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double at = fabs(theta);
+        if (at <= 1e150)
+            t = copysign(1.0, theta) / (at + sqrt(theta * theta + 1.0));
+        else if (iss_finite(at))
+            t = 0.5 / theta;
+    }
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    const double shift = t * apq;
+    app -= shift;
+    aqq += shift;
+    apq = 0.0;
+    const double rp = arp, rq = arq;
+    arp = c * rp - s * rq;
+    arq = s * rp + c * rq;
+}
+
+// grid: B * tiles blocks of T sorted positions.  eigenvalues, counts nullable
+template <int T>
+__global__ __launch_bounds__(T) void iss_saliency_kernel(const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,
+                                                         const int2* __restrict__ table_range, const int* __restrict__ n_in_grid,
+                                                         const float* __restrict__ origin, float inv, float R, unsigned r2_bits,
+                                                         double gamma_21, double gamma_32, int min_neighbors,
+                                                         double* __restrict__ saliency, double* __restrict__ eigenvalues,
+                                                         int* __restrict__ counts, int N, unsigned cap, int tiles) {
+#pragma clang fp contract(off)
+    const int b = (int)(blockIdx.x / (unsigned)tiles);
+    const int t = (int)(blockIdx.x % (unsigned)tiles) * T + (int)threadIdx.x;
+    if (t >= N) return;   // (no barrier below)
+    const f32x4* sb = sorted + (size_t)b * N;
+    const f32x4 own = sb[t];
+    const unsigned i = __float_as_uint(own[3]);
+    if (i >= (unsigned)N) return;   // a sorted array no build wrote: nothing outside the outputs is written
+    const float qx = own[0], qy = own[1], qz = own[2];
+    const double cx = (double)qx, cy = (double)qy, cz = (double)qz;
+    int m = 0;
+    double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+    if (cloud_finite3(qx, qy, qz))   // (a non-finite point has dist2 = +inf to everything)
+        iss_walk(qx, qy, qz, sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, R, r2_bits, N, cap,
+                 [&](const f32x4 p) {
+                     const double dx = (double)p[0] - cx, dy = (double)p[1] - cy, dz = (double)p[2] - cz;
+                     ++m;
+                     sx += dx, sy += dy, sz += dz;
+                     sxx += dx * dx, sxy += dx * dy, sxz += dx * dz;
+                     syy += dy * dy, syz += dy * dz, szz += dz * dz;
+                 });
+    double l0 = 0.0, l1 = 0.0, l2 = 0.0, sal = 0.0;
+    if (m >= min_neighbors) {
+        const double im = 1.0 / (double)m;
+        const double mx = sx * im, my = sy * im, mz = sz * im;
+        double a00 = sxx * im - mx * mx, a01 = sxy * im - mx * my, a02 = sxz * im - mx * mz;
+        double a11 = syy * im - my * my, a12 = syz * im - my * mz, a22 = szz * im - mz * mz;
+        const double big = fmax(fmax(fmax(fabs(a00), fabs(a01)), fmax(fabs(a02), fabs(a11))), fmax(fabs(a12), fabs(a22)));
+        if (big > 0.0 && iss_finite(big)) {
+            const double sc = 1.0 / big;
+            a00 *= sc, a01 *= sc, a02 *= sc, a11 *= sc, a12 *= sc, a22 *= sc;
+            for (int sweep = 0; sweep < ISS_JACOBI_SWEEPS; ++sweep) {
+                iss_rotate(a00, a11, a01, a02, a12);   // (0, 1): the third row is 2
+                iss_rotate(a00, a22, a02, a01, a12);   // (0, 2): the third row is 1
+                iss_rotate(a11, a22, a12, a01, a02);   // (1, 2): the third row is 0
+            }
+            l0 = fmax(a00 * big, 0.0), l1 = fmax(a11 * big, 0.0), l2 = fmax(a22 * big, 0.0);
+            double lo = fmin(l0, l1), hi = fmax(l0, l1);   // three compare-exchanges
+            l0 = lo, l1 = hi;
+            lo = fmin(l1, l2), hi = fmax(l1, l2);
+            l1 = lo, l2 = hi;
+            lo = fmin(l0, l1), hi = fmax(l0, l1);
+            l0 = lo, l1 = hi;
+            if (l1 < gamma_21 * l2 && l0 < gamma_32 * l1 && l0 > 0.0) sal = l0;
+        }
+    }
+    const size_t row = (size_t)b * N + i;
+    saliency[row] = sal;
+    if (eigenvalues) eigenvalues[row * 3] = l0, eigenvalues[row * 3 + 1] = l1, eigenvalues[row * 3 + 2] = l2;
+    if (counts) counts[row] = m;
+}
+
+// grid: B * tiles blocks of T sorted positions
+template <int T>
+__global__ __launch_bounds__(T) void iss_select_kernel(const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,
+                                                       const int2* __restrict__ table_range, const int* __restrict__ n_in_grid,
+                                                       const float* __restrict__ origin, float inv, float R, unsigned r2_bits,
+                                                       int min_neighbors, const double* __restrict__ saliency,
+                                                       unsigned char* __restrict__ mask, int N, unsigned cap, int tiles) {
+    const int b = (int)(blockIdx.x / (unsigned)tiles);
+    const int t = (int)(blockIdx.x % (unsigned)tiles) * T + (int)threadIdx.x;
+    if (t >= N) return;   // (no barrier below)
+    const f32x4* sb = sorted + (size_t)b * N;
+    const f32x4 own = sb[t];
+    const unsigned i = __float_as_uint(own[3]);
+    if (i >= (unsigned)N) return;
+    const double* sal = saliency + (size_t)b * N;
+    const double mine = sal[i];
+    bool keep = false;
+    if (mine > 0.0) {   // a candidate: its point is finite
+        int n = 0;
+        bool beaten = false;
+        iss_walk(own[0], own[1], own[2], sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, R,
+                 r2_bits, N, cap, [&](const f32x4 p) {
+                     const unsigned j = __float_as_uint(p[3]);
+                     ++n;
+                     beaten = beaten || (j < (unsigned)N && sal[j] > mine);
+                 });
+        keep = n >= min_neighbors && !beaten;
+    }
+    mask[(size_t)b * N + i] = keep ? 1 : 0;
+}
+
+// grid.hip's grid_reach: the least fp32 number >= sqrt(r2 (1 + 2^-23) + 2^-149) (1 + 2^-16), formed in double
+float iss_reach(float r2) {
+    const double bound = std::sqrt((double)r2 * (1.0 + 0x1p-23) + 0x1p-149) * (1.0 + 0x1p-16);
+    float R = (float)bound;
+    if ((double)R < bound) R = std::nextafterf(R, INFINITY);
+    return R;
+}
+
+bool iss_radius2_ok(float r2, float cell_size) { return r2 > 0.f && r2 <= 3.402823466e38f && r2 <= cell_size * cell_size; }
+
+}  // namespace
+
+// Two launches: the saliency of every point, then the selection.  eigenvalues, counts nullable.  -2: arguments out of range (a radius2
+// above fp32(cell_size^2) among them), -3: the grid would pass 2^31 - 1 workgroups
+int iss_launch(const float* sorted, const long long* table_keys, const int* table_range, const int* n_in_grid, const float* origin,
+               float cell_size, double* saliency, double* eigenvalues, int* counts, unsigned char* mask, int B, int N, float r2s, float r2n,
+               double gamma_21, double gamma_32, int min_neighbors, hipStream_t st) {
+    if (!sorted || !table_keys || !table_range || !n_in_grid || !saliency || !mask || B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return -2;
+    if (!iss_radius2_ok(r2s, cell_size) || !iss_radius2_ok(r2n, cell_size) || min_neighbors < 1) return -2;
+    if (!(gamma_21 > 0.0) || !(gamma_21 <= 1.7976931348623157e308) || !(gamma_32 > 0.0) || !(gamma_32 <= 1.7976931348623157e308)) return -2;
+    const CloudPlan p = cloud_plan(B, N, N, 1, false, 256, device_cus());
+    if (!p.fits()) return -3;
+    const unsigned cap = (unsigned)GECCO_GRID_CAPACITY(N);
+    const float inv = 1.0f / cell_size;
+    const u64* tk = reinterpret_cast<const u64*>(table_keys);
+    const int2* tr = reinterpret_cast<const int2*>(table_range);
+    const f32x4* sp = reinterpret_cast<const f32x4*>(sorted);
+    return dispatch_T(p.T, [&](auto t) -> int {
+        constexpr int T = decltype(t)::value;
+        const dim3 grid((unsigned)p.blocks), block(T);
+        hipLaunchKernelGGL((iss_saliency_kernel<T>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, iss_reach(r2s),
+                           __builtin_bit_cast(unsigned, r2s), gamma_21, gamma_32, min_neighbors, saliency, eigenvalues, counts, N, cap, p.tiles);
+        hipLaunchKernelGGL((iss_select_kernel<T>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, iss_reach(r2n),
+                           __builtin_bit_cast(unsigned, r2n), min_neighbors, saliency, mask, N, cap, p.tiles);
+        return (int)hipGetLastError();
+    });
+}

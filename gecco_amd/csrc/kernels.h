@@ -561,6 +561,13 @@ int grid_build_launch(const float* points, const long long* keys, const int* per
 int grid_radius_launch(const float* query, const int* qorder, const float* sorted, const long long* table_keys, const int* table_range,
                        const int* n_in_grid, const float* origin, float cell_size, const long long* row_start, int* idx, float* d2, int* count,
                        int B, int M, int N, float r2, int exclude_self, hipStream_t st);
+// iss.hip — ISS keypoints on the grid index (definition: gecco_iss_keypoints_f32): two launches over the sorted positions, the
+// saliency of every point and the selection.  r2s, r2n = fp32(radius^2) of the salient and the non-maximum radius; origin,
+// eigenvalues, counts nullable.  -2: arguments out of range (a radius2 above fp32(cell_size^2) among them), -3: the grid would pass
+// 2^31 - 1 workgroups
+int iss_launch(const float* sorted, const long long* table_keys, const int* table_range, const int* n_in_grid, const float* origin,
+               float cell_size, double* saliency, double* eigenvalues, int* counts, unsigned char* mask, int B, int N, float r2s, float r2n,
+               double gamma_21, double gamma_32, int min_neighbors, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

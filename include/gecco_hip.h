@@ -1449,6 +1449,51 @@ int gecco_grid_radius_search_f32(const float* query, const int32_t* qorder, cons
                                  const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size,
                                  const int64_t* row_start, int32_t* idx, float* d2, int B, int M, int N, float radius2, int exclude_self,
                                  void* stream);
+/* ISS keypoints (Intrinsic Shape Signatures, Zhong 2009; Open3D's compute_iss_keypoints, PCL's ISSKeypoint3D) on the grid index above
+ * (csrc/iss.hip): the points whose neighbourhood is not flat, not a line and not isotropic, thinned by non-maximum suppression.  The
+ * cloud is the one the index was built over; sorted, table_keys, table_range, n_in_grid, origin and cell_size are that index.
+ * tests/_iss_ref.py restates the definition in numpy.  Per batch element, with r2s = salient_radius2 = fp32(salient_radius^2) and
+ * r2n = non_max_radius2 = fp32(non_max_radius^2) from the caller:
+ *     ball        B_r(i) = the j with dist2(p_i, p_j) <= r2 on the bits, gecco_radius_count_f32's predicate, the point itself INCLUDED
+ *                 by index (Open3D's radius search returns the query).  A non-finite point is in nobody's ball, not even its own.  The
+ *                 ball is visited in ascending sorted position of the index (by (cell key, j), the off-grid tail last), the order of
+ *                 a row of gecco_grid_radius_search_f32: that order is part of the definition
+ *     count       m_i = |B_r2s(i)|
+ *     moments     in fp64 on the fp32 coordinates, about the point itself, every operation rounded and none contracted:
+ *                 d = double(p_j) - double(p_i) per axis;  S1 = sum d (3 sums), S2 = sum d d^T (xx, xy, xz, yy, yz, zz), each from 0
+ *                 in ball order;  inv = 1 / m;  mu = S1 inv;  C_ab = S2_ab inv - mu_a mu_b.  |d| <= the radius, so the raw moments
+ *                 cancel against the radius and not against the cloud's distance from the origin
+ *     eigen       big = max |C_ab|;  A = C sc with sc = 1 / big;  8 cyclic Jacobi sweeps over (0,1), (0,2), (1,2) with the guarded
+ *                 rotation of gecco_icp_f32 (a non-finite theta gives t = 0, a theta whose square would overflow t = 1 / (2 theta)),
+ *                 a fixed count, none of its operations contracted;  lambda = diag big, negative roundings clamped to 0, sorted
+ *                 lambda0 <= lambda1 <= lambda2
+ *     candidate   m_i >= min_neighbors, big a positive finite number (all of the ball identical: not a candidate, Open3D's
+ *                 cov.isZero()), lambda1 < gamma_21 lambda2, lambda0 < gamma_32 lambda1 (fp64 products, no division) and
+ *                 lambda0 > 0.  saliency_i = lambda0 for a candidate, 0 otherwise;  eigenvalues_i = 0 where m_i < min_neighbors or
+ *                 big is not a positive finite number
+ *     keypoint    i is a candidate, |B_r2n(i)| >= min_neighbors, and no j in B_r2n(i) has saliency_j > saliency_i (fp64 compare).
+ *                 Equal saliencies keep each other, as Open3D's IsLocalMaxima does: two exact duplicates of a keypoint are both kept
+ * Outputs, at the ORIGINAL index of a point: saliency (B, N) fp64, eigenvalues (B, N, 3) fp64 ascending (may be NULL), counts (B, N)
+ * int32 = m_i (may be NULL), mask (B, N) one byte per point, 1 for a keypoint and 0 otherwise.  A point's result depends on the cloud
+ * and on the index's cell_size and origin, which fix the order of the sums, and on nothing else: the same bits run to run, in any
+ * batch position and at any workgroup size.  Two indices with different cells may differ in the last bits of the eigenvalues.
+ * Worked example: the 6 x 6 x 6 integer grid (x slowest) of the radius block, cell_size 1.5, origin 0, both radii 1.5 (radius2 2.25),
+ * gammas 0.975, min_neighbors 5.  Point 0, a corner: m = 7, S1 = (3, 3, 3), S2 = 3 on the diagonal and 1 off it, C = 12/49 on the
+ * diagonal and -2/49 off it, lambda = (8/49, 2/7, 2/7): lambda1 = lambda2, not a candidate.  Point 1 = (0, 0, 1), on an edge: m = 10,
+ * lambda = (0.18, 0.3, 0.6), saliency 0.18.  Point 7 = (0, 1, 1), on a face: m = 14, lambda1 = lambda2 = 4/7; point 43 = (1, 1, 1): m =
+ * 19, lambda = 10/19 three times.  The candidates are the 48 points inside the 12 edges, all with saliency 0.18 up to rounding in
+ * the last place; every one is a keypoint (a non-maximum ball holds 10 points and no larger saliency), and nothing else is.
+ * Two launches, one thread per sorted position in both: the saliency of every point (a walk over the cells its ball can reach, the
+ * count and the nine sums in registers, the 3 x 3 problem in registers), then the selection (the same walk at r2n, a gather of
+ * saliency by index).  A thread writes its own words only: no atomics, no workspace, no allocation, no synchronisation, asynchronous
+ * on `stream`.  Return -2 before anything is enqueued (and gecco_last_error) for: a null required pointer, B or N < 1, N above
+ * GECCO_VOXEL_MAX_POINTS, a cell_size that is not a finite number > 0 with a finite reciprocal, a radius2 that is not a finite
+ * number > 0 or is above fp32(cell_size * cell_size) (build an index with a larger cell), a gamma that is not a finite number > 0,
+ * min_neighbors < 1; -3 for a grid above 2^31 - 1 workgroups. */
+int gecco_iss_keypoints_f32(const float* sorted, const int64_t* table_keys, const int32_t* table_range, const int32_t* n_in_grid,
+                            const float* origin, float cell_size, double* saliency, double* eigenvalues, int32_t* counts, uint8_t* mask, int B,
+                            int N, float salient_radius2, float non_max_radius2, double gamma_21, double gamma_32, int min_neighbors,
+                            void* stream);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through
