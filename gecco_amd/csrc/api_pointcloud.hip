@@ -426,14 +426,18 @@ int gecco_grid_build_f32(const float* points, const int64_t* sorted_keys, const 
     TRY(rc, "grid_build");
     return 0;
 }
+// a radius2 (finite and > 0: checked by the caller) the index's cells serve: not above fp32(cell_size^2), grid_walk.h's grid_radius2_ok
+static int grid_radius2_fits(const char* who, const char* name, float cell_size, float radius2) {
+    if (!(radius2 <= cell_size * cell_size))
+        return fail(-2, "%s: %s = %g is above cell_size^2 = %g: build an index with a larger cell", who, name, (double)radius2,
+                    (double)(cell_size * cell_size));
+    return 0;
+}
 static int grid_radius_common(const char* who, int B, int M, int N, float cell_size, float radius2, int exclude_self) {
     if (const int bad = radius_common(who, B, M, N, radius2, exclude_self)) return bad;
     if (N > GECCO_VOXEL_MAX_POINTS) return fail(-2, "%s: N = %d above %d", who, N, GECCO_VOXEL_MAX_POINTS);
     if (const int bad = grid_cell_size(who, cell_size)) return bad;
-    if (!(radius2 <= cell_size * cell_size))
-        return fail(-2, "%s: radius2 = %g is above cell_size^2 = %g: build an index with a larger cell", who, (double)radius2,
-                    (double)(cell_size * cell_size));
-    return 0;
+    return grid_radius2_fits(who, "radius2", cell_size, radius2);
 }
 int gecco_grid_radius_count_f32(const float* query, const int32_t* qorder, const float* sorted, const int64_t* table_keys,
                                 const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size, int32_t* count,
@@ -463,10 +467,7 @@ int gecco_grid_radius_search_f32(const float* query, const int32_t* qorder, cons
 // ISS keypoints on the grid index (iss.hip).  Every refusal is -2, null pointers included; eigenvalues, counts and origin nullable
 static int iss_radius2(const char* name, float cell_size, float radius2) {
     if (!finite_positive(radius2)) return fail(-2, "iss_keypoints: %s = %g must be a finite number > 0", name, (double)radius2);
-    if (!(radius2 <= cell_size * cell_size))
-        return fail(-2, "iss_keypoints: %s = %g is above cell_size^2 = %g: build an index with a larger cell", name, (double)radius2,
-                    (double)(cell_size * cell_size));
-    return 0;
+    return grid_radius2_fits("iss_keypoints", name, cell_size, radius2);
 }
 int gecco_iss_keypoints_f32(const float* sorted, const int64_t* table_keys, const int32_t* table_range, const int32_t* n_in_grid,
                             const float* origin, float cell_size, double* saliency, double* eigenvalues, int32_t* counts, uint8_t* mask, int B,

@@ -26,31 +26,16 @@
 // there does not).  With qorder (a permutation of the queries, by cell) thread t answers query qorder[t] and writes THAT query's row:
 // the lanes of a wave probe the same cells and read the same runs, which the L2 then serves once.
 //
-// Why no neighbour is missed.  Let dist2(q, p) <= r2 and take one axis, d = fp32(q - p).  Rounding and adding non-negative numbers are
-// monotone, so fp32(d d) <= dist2 <= r2, hence the real d d <= r2 (1 + 2^-24) + 2^-150 (half a unit above r2, the second term when r2
-// is subnormal), and the real |q - p| <= |d| (1 + 2^-24).  grid_reach forms, in double and rounded UP to fp32,
-//     R >= sqrt(r2 (1 + 2^-23) + 2^-149) (1 + 2^-16),
-// which is above that bound (and above r (1 + 2^-16), since r2 >= r r (1 - 2^-24)).  So p >= q - R in the reals, and p being an fp32
-// number, p >= fp32(q - R): rounding to nearest never crosses a representable number.  Subtracting o, multiplying by inv > 0 and
-// floor are each monotone in fp32 as well, so cell(p) >= cell(fp32(q - R)) = lo, and symmetrically cell(p) <= hi.  An on-grid p has its
-// cell inside the grid, so clamping lo and hi to the grid loses nothing; an off-grid p is in the tail, which every query scans.  Extra
-// cells cost time, never correctness: the cells are a filter, membership is dist2 <= r2 alone.
-//
-// How wide the box can be.  The entry points refuse radius2 > fp32(cell_size^2), so for a normal r2 R <= cell_size (1 + 2^-15) and
-// 2 R inv <= 2.0001.  fp32(q + R) - fp32(q - R) <= 2 R + (the spacing of fp32 numbers at |q| + R), and inside the grid (|u| < 2^20)
-// the two roundings of t add at most 1/8 cell and the two of u at most 1/8.  So where fp32 resolves the coordinates to better than 0.7
-// of a cell, every cloud a grid makes sense for, u(q + R) - u(q - R) < 3 and the box touches AT MOST GRID_BOX = 4 CELLS PER AXIS, 64
-// in all (tests/test_grid_cpu.py asserts it on its inputs, coordinates near 1000 at r = 0.01 and cells at +-2^20 among them).  The
-// three loops are bounded by that constant.  Where the arithmetic gives a wider box all the same (coordinates fp32 resolves more
-// coarsely than a cell, a subnormal r2, a non-finite origin) the thread scans the whole sorted cloud instead, sorted[0 .. N): the
-// scan of radius.hip in another order, the same neighbours, rows still ascending in sorted position.  No input makes a thread walk
-// an unbounded box and none loses a neighbour to the bound.
+// The walk itself (the reach, the box, the probe, the runs, the tail, the scan of the whole cloud for a box wider than GRID_BOX cells) is
+// grid_walk of grid_walk.h, which iss.hip's kernels call as well; that header proves that the walk misses no neighbour and bounds
+// every loop.
 //
 // The radius may not exceed the cell edge; an index serves every smaller radius (at r = cell_size / 2 the 27 to 64 cells hold 8 times
 // the candidates that cells of edge r would: build another index when that matters).  The fixed-width forms stay on radius.hip.
 #include <cmath>
 
 #include "cloud_nn.h"
+#include "grid_walk.h"
 #include "kernels.h"
 #include "launch_state.h"
 #include "voxel_cell.h"
@@ -59,8 +44,6 @@ namespace {
 
 constexpr u64 GRID_OFF = 1ull << 63;   // the key of an off-grid point: above every real key as an unsigned integer
 constexpr int GRID_THREADS = 256;      // keys, build, fill
-constexpr int GRID_BOX = 4;            // cells per axis a query walks; a wider box is answered by a scan of the whole cloud
-constexpr int GRID_HALF = 1 << 20;
 
 enum { GRID_COUNT = 0, GRID_FILL_CSR = 1 };
 
@@ -117,15 +100,8 @@ __global__ __launch_bounds__(GRID_THREADS) void grid_build_kernel(const float* _
     }
 }
 
-// floor(u) of the fp32 coordinate x on one axis: voxel_cell's roundings
-static __device__ __forceinline__ float grid_u(float x, float o, float inv) {
-#pragma clang fp contract(off)
-    const float t = x - o;
-    return floorf(t * inv);
-}
-
-// grid: B * tiles blocks of T queries.  COUNT: count.  FILL_CSR: row_start, idx, d2 (nullable).  iss.hip's iss_walk is this kernel's
-// walk (the reach, the box, the probe, the runs, the tail, the wide scan) written out again for a visitor: THE TWO CHANGE TOGETHER
+// grid: B * tiles blocks of T queries.  COUNT: count.  FILL_CSR: row_start, idx, d2 (nullable).  The walk is grid_walk (grid_walk.h); what
+// is this kernel's own is the visitor: self exclusion by the index in .w, the stores, the counter
 template <int T, int MODE>
 __global__ __launch_bounds__(T) void grid_query_kernel(const float* __restrict__ query, const int* __restrict__ qorder,
                                                        const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,
@@ -134,80 +110,29 @@ __global__ __launch_bounds__(T) void grid_query_kernel(const float* __restrict__
                                                        const long long* __restrict__ row_start, int* __restrict__ idx, float* __restrict__ d2,
                                                        int* __restrict__ count, unsigned r2_bits, int M, int N, unsigned cap, int exclude_self,
                                                        int tiles) {
-#pragma clang fp contract(off)
     const int b = (int)(blockIdx.x / (unsigned)tiles);
     const int t = (int)(blockIdx.x % (unsigned)tiles) * T + (int)threadIdx.x;
     if (t >= M) return;   // (no barrier below)
     const int i = qorder ? qorder[(size_t)b * M + t] : t;
     if ((unsigned)i >= (unsigned)M) return;   // a qorder that is no permutation writes nothing outside the outputs
     const size_t row = (size_t)b * M + i;
-    const float q[3] = {query[row * 3], query[row * 3 + 1], query[row * 3 + 2]};
+    const float qx = query[row * 3], qy = query[row * 3 + 1], qz = query[row * 3 + 2];
     const unsigned self = exclude_self ? (unsigned)i : 0xffffffffu;   // no j reaches 2^32 - 1
     const size_t o = MODE == GRID_FILL_CSR ? (size_t)row_start[row] : 0;
-    const f32x4* sb = sorted + (size_t)b * N;
     int n = 0;   // neighbours so far (n <= N)
-
-    auto scan = [&](int from, int to) {
-        for (int s = from; s < to; ++s) {
-            const f32x4 p = sb[s];   // one 16-byte load
-            const unsigned u = cloud_dist2_bits(q[0], q[1], q[2], p), j = __float_as_uint(p[3]);
-            if (u <= r2_bits && j != self) {
-                if (MODE == GRID_FILL_CSR) {
-                    idx[o + (size_t)n] = (int)j;
-                    if (d2) d2[o + (size_t)n] = __uint_as_float(u);
-                }
-                ++n;
-            }
-        }
-    };
-
-    if (cloud_finite3(q[0], q[1], q[2])) {   // (a non-finite query has dist2 = +inf to everything)
-        int lo[3], hi[3];
-        bool wide = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float org = origin ? origin[3 * b + a] : 0.f;
-            const float below = q[a] - R, above = q[a] + R;   // rounded to fp32 before the cell arithmetic
-            const float fl = grid_u(below, org, inv), fh = grid_u(above, org, inv);
-            // clamped to the grid: a bound beyond it on the far side leaves an empty box, a NaN (a non-finite origin) the widest one
-            lo[a] = fl >= -VOXEL_HALF ? (fl < VOXEL_HALF ? (int)fl : GRID_HALF) : -GRID_HALF;
-            hi[a] = fh < VOXEL_HALF ? (fh >= -VOXEL_HALF ? (int)fh : -GRID_HALF - 1) : GRID_HALF - 1;
-            wide = wide || hi[a] - lo[a] >= GRID_BOX;
-        }
-        if (wide) {   // header comment: never for coordinates that fp32 resolves inside a cell
-            scan(0, N);
-            lo[0] = 1, hi[0] = 0;
-        }
-        const u64* tk = table_keys + (size_t)b * cap;
-        const int2* tr = table_range + (size_t)b * cap;
-        const unsigned mask = cap - 1;
-        for (int cx = lo[0]; cx < lo[0] + GRID_BOX && cx <= hi[0]; ++cx)
-            for (int cy = lo[1]; cy < lo[1] + GRID_BOX && cy <= hi[1]; ++cy)
-                for (int cz = lo[2]; cz < lo[2] + GRID_BOX && cz <= hi[2]; ++cz) {   // ascending key
-                    const u64 key = voxel_key(cx, cy, cz);
-                    unsigned h = voxel_hash(key, mask);
-                    for (unsigned probe = 0; probe < cap; ++probe) {   // ends at the key or at an empty slot (load <= 0.5)
-                        const u64 seen = tk[h];
-                        if (seen == key) {
-                            const int2 r = tr[h];
-                            scan(max(r.x, 0), min(r.y, N));
-                            break;
-                        }
-                        if (seen == VOXEL_EMPTY) break;
-                        h = (h + 1) & mask;
-                    }
-                }
-        if (!wide) scan(min(max(n_in_grid[b], 0), N), N);   // the off-grid tail
-    }
+    if (cloud_finite3(qx, qy, qz))   // (a non-finite query has dist2 = +inf to everything)
+        grid_walk(qx, qy, qz, sorted + (size_t)b * N, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv,
+                  R, r2_bits, N, cap, [&](const f32x4 p, unsigned u) {
+                      const unsigned j = __float_as_uint(p[3]);
+                      if (j != self) {
+                          if (MODE == GRID_FILL_CSR) {
+                              idx[o + (size_t)n] = (int)j;
+                              if (d2) d2[o + (size_t)n] = __uint_as_float(u);
+                          }
+                          ++n;
+                      }
+                  });
     if (MODE == GRID_COUNT) count[row] = n;
-}
-
-// The reach R of a query's box (header comment): the least fp32 number >= sqrt(r2 (1 + 2^-23) + 2^-149) (1 + 2^-16), formed in double
-float grid_reach(float r2) {
-    const double bound = std::sqrt((double)r2 * (1.0 + 0x1p-23) + 0x1p-149) * (1.0 + 0x1p-16);
-    float R = (float)bound;
-    if ((double)R < bound) R = std::nextafterf(R, INFINITY);
-    return R;
 }
 
 }  // namespace
@@ -246,7 +171,7 @@ int grid_radius_launch(const float* query, const int* qorder, const float* sorte
                        const int* n_in_grid, const float* origin, float cell_size, const long long* row_start, int* idx, float* d2, int* count,
                        int B, int M, int N, float r2, int exclude_self, hipStream_t st) {
     if (!query || !sorted || !table_keys || !table_range || !n_in_grid || B < 1 || M < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return -2;
-    if (!(r2 > 0.f) || !(r2 <= 3.402823466e38f) || !(r2 <= cell_size * cell_size) || (exclude_self && M != N)) return -2;
+    if (!grid_radius2_ok(r2, cell_size) || (exclude_self && M != N)) return -2;
     if (idx ? !row_start : !count || row_start || d2) return -2;
     const CloudPlan p = cloud_plan(B, M, N, 1, false, 256, device_cus());
     if (!p.fits()) return -3;

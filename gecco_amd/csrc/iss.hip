@@ -36,80 +36,19 @@
 // r2n, counts the ball and compares saliency[j], a gather by the index carried in .w, and writes the mask byte.  A thread writes its own
 // words only: no atomics, no LDS, no workspace, no thread waits on another, every loop is bounded by a constant, by cap or by N.
 //
-// The walk (grid_reach, the clamped per-axis cells, at most GRID_BOX cells per axis, the table probe, the runs, the tail, the scan of
-// all N sorted positions for a wide box) is grid_query_kernel's, written out again in iss_walk below; grid.hip's header proves that it
-// misses no neighbour and bounds every loop.  THE TWO CHANGE TOGETHER.  It is a copy and not a shared header because the query
-// kernel's registers (38 and 42 VGPRs, no scratch) and its time at 100 000 points were not re-measured with the loop moved behind a
-// visitor template; cloud_nn.h records the same decision, measured, for the kNN loop.
+// The walk (the reach, the clamped cells, the table probe, the runs, the tail, the scan of all N positions for a wide box) is grid_walk of
+// grid_walk.h, the one grid_query_kernel calls, where it is proved to miss no neighbour and every loop is bounded.
 #include <cmath>
 
 #include "cloud_nn.h"
+#include "grid_walk.h"
 #include "kernels.h"
 #include "launch_state.h"
 #include "voxel_cell.h"
 
 namespace {
 
-constexpr int ISS_BOX = 4;             // grid.hip's GRID_BOX: cells per axis a thread walks; a wider box scans the whole cloud
-constexpr int ISS_HALF = 1 << 20;      // grid.hip's GRID_HALF
 constexpr int ISS_JACOBI_SWEEPS = 8;   // rigid_fit.h's count: quadratic convergence, fp64 by the fifth
-
-// floor(u) of the fp32 coordinate x on one axis: voxel_cell's roundings (grid.hip's grid_u)
-static __device__ __forceinline__ float iss_u(float x, float o, float inv) {
-#pragma clang fp contract(off)
-    const float t = x - o;
-    return floorf(t * inv);
-}
-
-// grid_query_kernel's walk for the finite point (qx, qy, qz) of cloud b: visit(p) for every sorted entry p of the ball, in ascending
-// sorted position.  sb, tk, tr: the cloud's own sorted points and table
-template <class Visit>
-static __device__ __forceinline__ void iss_walk(float qx, float qy, float qz, const f32x4* __restrict__ sb, const u64* __restrict__ tk,
-                                                const int2* __restrict__ tr, int tail, const float* __restrict__ origin, int b, float inv,
-                                                float R, unsigned r2_bits, int N, unsigned cap, Visit visit) {
-#pragma clang fp contract(off)
-    auto scan = [&](int from, int to) {
-        for (int s = from; s < to; ++s) {
-            const f32x4 p = sb[s];   // one 16-byte load
-            if (cloud_dist2_bits(qx, qy, qz, p) <= r2_bits) visit(p);
-        }
-    };
-    const float q[3] = {qx, qy, qz};
-    int lo[3], hi[3];
-    bool wide = false;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float org = origin ? origin[3 * b + a] : 0.f;
-        const float below = q[a] - R, above = q[a] + R;   // rounded to fp32 before the cell arithmetic
-        const float fl = iss_u(below, org, inv), fh = iss_u(above, org, inv);
-        // clamped to the grid: a bound beyond it on the far side leaves an empty box, a NaN (a non-finite origin) the widest one
-        lo[a] = fl >= -VOXEL_HALF ? (fl < VOXEL_HALF ? (int)fl : ISS_HALF) : -ISS_HALF;
-        hi[a] = fh < VOXEL_HALF ? (fh >= -VOXEL_HALF ? (int)fh : -ISS_HALF - 1) : ISS_HALF - 1;
-        wide = wide || hi[a] - lo[a] >= ISS_BOX;
-    }
-    if (wide) {   // grid.hip's header: never for coordinates that fp32 resolves inside a cell
-        scan(0, N);
-        return;
-    }
-    const unsigned mask = cap - 1;
-    for (int cx = lo[0]; cx < lo[0] + ISS_BOX && cx <= hi[0]; ++cx)
-        for (int cy = lo[1]; cy < lo[1] + ISS_BOX && cy <= hi[1]; ++cy)
-            for (int cz = lo[2]; cz < lo[2] + ISS_BOX && cz <= hi[2]; ++cz) {   // ascending key
-                const u64 key = voxel_key(cx, cy, cz);
-                unsigned h = voxel_hash(key, mask);
-                for (unsigned probe = 0; probe < cap; ++probe) {   // ends at the key or at an empty slot (load <= 0.5)
-                    const u64 seen = tk[h];
-                    if (seen == key) {
-                        const int2 r = tr[h];
-                        scan(max(r.x, 0), min(r.y, N));
-                        break;
-                    }
-                    if (seen == VOXEL_EMPTY) break;
-                    h = (h + 1) & mask;
-                }
-            }
-    scan(min(max(tail, 0), N), N);   // the off-grid tail
-}
 
 static __device__ __forceinline__ bool iss_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and inf
 
@@ -157,14 +96,14 @@ __global__ __launch_bounds__(T) void iss_saliency_kernel(const f32x4* __restrict
     int m = 0;
     double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
     if (cloud_finite3(qx, qy, qz))   // (a non-finite point has dist2 = +inf to everything)
-        iss_walk(qx, qy, qz, sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, R, r2_bits, N, cap,
-                 [&](const f32x4 p) {
-                     const double dx = (double)p[0] - cx, dy = (double)p[1] - cy, dz = (double)p[2] - cz;
-                     ++m;
-                     sx += dx, sy += dy, sz += dz;
-                     sxx += dx * dx, sxy += dx * dy, sxz += dx * dz;
-                     syy += dy * dy, syz += dy * dz, szz += dz * dz;
-                 });
+        grid_walk(qx, qy, qz, sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, R, r2_bits, N, cap,
+                  [&](const f32x4 p, unsigned) {
+                      const double dx = (double)p[0] - cx, dy = (double)p[1] - cy, dz = (double)p[2] - cz;
+                      ++m;
+                      sx += dx, sy += dy, sz += dz;
+                      sxx += dx * dx, sxy += dx * dy, sxz += dx * dz;
+                      syy += dy * dy, syz += dy * dz, szz += dz * dz;
+                  });
     double l0 = 0.0, l1 = 0.0, l2 = 0.0, sal = 0.0;
     if (m >= min_neighbors) {
         const double im = 1.0 / (double)m;
@@ -216,26 +155,16 @@ __global__ __launch_bounds__(T) void iss_select_kernel(const f32x4* __restrict__
     if (mine > 0.0) {   // a candidate: its point is finite
         int n = 0;
         bool beaten = false;
-        iss_walk(own[0], own[1], own[2], sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, R,
-                 r2_bits, N, cap, [&](const f32x4 p) {
-                     const unsigned j = __float_as_uint(p[3]);
-                     ++n;
-                     beaten = beaten || (j < (unsigned)N && sal[j] > mine);
-                 });
+        grid_walk(own[0], own[1], own[2], sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, R,
+                  r2_bits, N, cap, [&](const f32x4 p, unsigned) {
+                      const unsigned j = __float_as_uint(p[3]);
+                      ++n;
+                      beaten = beaten || (j < (unsigned)N && sal[j] > mine);
+                  });
         keep = n >= min_neighbors && !beaten;
     }
     mask[(size_t)b * N + i] = keep ? 1 : 0;
 }
-
-// grid.hip's grid_reach: the least fp32 number >= sqrt(r2 (1 + 2^-23) + 2^-149) (1 + 2^-16), formed in double
-float iss_reach(float r2) {
-    const double bound = std::sqrt((double)r2 * (1.0 + 0x1p-23) + 0x1p-149) * (1.0 + 0x1p-16);
-    float R = (float)bound;
-    if ((double)R < bound) R = std::nextafterf(R, INFINITY);
-    return R;
-}
-
-bool iss_radius2_ok(float r2, float cell_size) { return r2 > 0.f && r2 <= 3.402823466e38f && r2 <= cell_size * cell_size; }
 
 }  // namespace
 
@@ -245,7 +174,7 @@ int iss_launch(const float* sorted, const long long* table_keys, const int* tabl
                float cell_size, double* saliency, double* eigenvalues, int* counts, unsigned char* mask, int B, int N, float r2s, float r2n,
                double gamma_21, double gamma_32, int min_neighbors, hipStream_t st) {
     if (!sorted || !table_keys || !table_range || !n_in_grid || !saliency || !mask || B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return -2;
-    if (!iss_radius2_ok(r2s, cell_size) || !iss_radius2_ok(r2n, cell_size) || min_neighbors < 1) return -2;
+    if (!grid_radius2_ok(r2s, cell_size) || !grid_radius2_ok(r2n, cell_size) || min_neighbors < 1) return -2;
     if (!(gamma_21 > 0.0) || !(gamma_21 <= 1.7976931348623157e308) || !(gamma_32 > 0.0) || !(gamma_32 <= 1.7976931348623157e308)) return -2;
     const CloudPlan p = cloud_plan(B, N, N, 1, false, 256, device_cus());
     if (!p.fits()) return -3;
@@ -257,9 +186,9 @@ int iss_launch(const float* sorted, const long long* table_keys, const int* tabl
     return dispatch_T(p.T, [&](auto t) -> int {
         constexpr int T = decltype(t)::value;
         const dim3 grid((unsigned)p.blocks), block(T);
-        hipLaunchKernelGGL((iss_saliency_kernel<T>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, iss_reach(r2s),
+        hipLaunchKernelGGL((iss_saliency_kernel<T>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, grid_reach(r2s),
                            __builtin_bit_cast(unsigned, r2s), gamma_21, gamma_32, min_neighbors, saliency, eigenvalues, counts, N, cap, p.tiles);
-        hipLaunchKernelGGL((iss_select_kernel<T>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, iss_reach(r2n),
+        hipLaunchKernelGGL((iss_select_kernel<T>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, grid_reach(r2n),
                            __builtin_bit_cast(unsigned, r2n), min_neighbors, saliency, mask, N, cap, p.tiles);
         return (int)hipGetLastError();
     });

@@ -325,7 +325,8 @@ the points whose neighbourhood is not flat, not a line and not isotropic, and th
 `match_features` and `ransac_registration` work on hundreds of points instead of all N.  The route without it is `radius_search` into
 a CSR list, `repeat_interleave` and `index_add` (float atomics) for the moments, `torch.linalg.eigvalsh` on N little matrices, and a
 second `radius_search` with a `scatter_reduce`: two host synchronisations and two materialised neighbour lists.  Here a thread walks
-the cells of the grid index its ball can reach and pools in registers.  Definition (include/gecco_hip.h; tests/_iss_ref.py restates
+the cells of the grid index its ball can reach (csrc/grid_walk.h: the walk `radius_count(index=...)` makes, one spelling for both) and
+pools in registers.  Definition (include/gecco_hip.h; tests/_iss_ref.py restates
 it in numpy).  Per cloud, with r2s = fp32(salient_radius^2) and r2n = fp32(non_max_radius^2) formed as `radius_count` forms r2:
     ball       B_r(i) = the j with dist2(p_i, p_j) <= r2 on the bits, `radius_count`'s predicate, the point itself INCLUDED by index
                (Open3D's radius search returns the query).  A non-finite point is in nobody's ball, not even its own.  The ball is
@@ -1373,6 +1374,16 @@ class RadiusNeighbors(NamedTuple):
     counts: Tensor             # int64 (B, M): row_splits[r + 1] - row_splits[r]
 
 
+def _radius_f32(radius):
+    """A radius as the library takes it -> (the radius rounded to fp32, r2 = fp32(radius * radius)); ValueError unless both are finite
+    numbers > 0"""
+    rad = _positive_f32(radius, "radius", (TypeError, ValueError, OverflowError))
+    r2 = C.c_float(rad * rad).value   # exact in double, rounded to fp32 once
+    if not (math.isfinite(r2) and r2 > 0):
+        raise ValueError(f"radius = {radius!r}: its square must be a finite fp32 number > 0")
+    return rad, r2
+
+
 def _radius_arguments(query: Tensor, ref: Tensor | None, radius, exclude_self):
     """What the three radius operators check before any device call -> q (B, M, 3), r (B, N, 3) or None (= q), single, N,
     r2 = fp32(radius * radius) and exclude_self as a bool"""
@@ -1388,11 +1399,7 @@ def _radius_arguments(query: Tensor, ref: Tensor | None, radius, exclude_self):
     exclude_self = (ref is None) if exclude_self is None else bool(exclude_self)
     if exclude_self and M != N:
         raise ValueError(f"exclude_self needs the query cloud to be the reference cloud (M = {M}, N = {N})")
-    rad = _positive_f32(radius, "radius", (TypeError, ValueError, OverflowError))
-    r2 = C.c_float(rad * rad).value   # exact in double, rounded to fp32 once
-    if not (math.isfinite(r2) and r2 > 0):
-        raise ValueError(f"radius = {radius!r}: its square must be a finite fp32 number > 0")
-    return q, r, single, N, r2, exclude_self
+    return q, r, single, N, _radius_f32(radius)[1], exclude_self
 
 
 def _radius_inputs(q: Tensor, r: Tensor | None):
@@ -1501,20 +1508,16 @@ def _grid_arguments(query: Tensor, ref: Tensor | None, radius, exclude_self, ind
         exclude_self = bool(exclude_self) if exclude_self is not None else False
         if exclude_self and M != N:
             raise ValueError(f"exclude_self needs the query cloud to be the reference cloud (M = {M}, N = {N})")
-        rad = _positive_f32(radius, "radius", (TypeError, ValueError, OverflowError))
-        r2 = C.c_float(rad * rad).value
-        if not (math.isfinite(r2) and r2 > 0):
-            raise ValueError(f"radius = {radius!r}: its square must be a finite fp32 number > 0")
+        rad, r2 = _radius_f32(radius)
         if rad > index.cell_size:
             raise ValueError(f"radius = {rad} is above the index's cell_size = {index.cell_size}: build an index with a larger cell")
         return q, single, r2, exclude_self, index, None, None
     if not (isinstance(index, str) and index == "grid"):
         raise ValueError("index must be None, 'grid' or a GridIndex")
     q, r, single, _, r2, exclude_self = _radius_arguments(query, ref, radius, exclude_self)
-    rad = _positive_f32(radius, "radius", (TypeError, ValueError, OverflowError))
     if r is not None and r.shape[1] > VOXEL_MAX_POINTS:
         raise ValueError(f"N = {r.shape[1]} above {VOXEL_MAX_POINTS}")
-    return q, single, r2, exclude_self, None, r, _grid_cell_size(rad)
+    return q, single, r2, exclude_self, None, r, _grid_cell_size(_radius_f32(radius)[0])
 
 
 def _grid_inputs(q: Tensor, exclude_self: bool, index, r, size):
@@ -1731,9 +1734,11 @@ def iss_keypoints(points: Tensor, salient_radius: float, non_max_radius: float, 
     fp32 number > 0 with a finite square > 0, a gamma that is not a finite number > 0, min_neighbors that is not an integer >= 1,
     an index that is neither None nor a GridIndex, an index of another batching or another N, a radius above the index's cell;
     GeccoHipError for CPU tensors.  No gradient: a selection."""
-    p, _, single, N, r2s, _ = _radius_arguments(points, None, salient_radius, False)
-    r2n = _radius_arguments(points, None, non_max_radius, False)[4]
-    B = p.shape[0]
+    p, single = _cloud(points)
+    B, N, _ = p.shape
+    if B < 1 or N < 1:
+        raise ValueError("empty batch or cloud")
+    (rs, r2s), (rn, r2n) = _radius_f32(salient_radius), _radius_f32(non_max_radius)
     if N > VOXEL_MAX_POINTS:
         raise ValueError(f"N = {N} above {VOXEL_MAX_POINTS}")
     g21, g32 = _gamma(gamma_21, "gamma_21"), _gamma(gamma_32, "gamma_32")
@@ -1741,8 +1746,7 @@ def iss_keypoints(points: Tensor, salient_radius: float, non_max_radius: float, 
     if not 1 <= min_neighbors <= 0x7fffffff:
         raise ValueError(f"min_neighbors = {min_neighbors} must be in 1 .. 2^31 - 1")
     if index is None:
-        catch = (TypeError, ValueError, OverflowError)
-        size = _grid_cell_size(max(_positive_f32(salient_radius, "salient_radius", catch), _positive_f32(non_max_radius, "non_max_radius", catch)))
+        size = _grid_cell_size(max(rs, rn))
     elif isinstance(index, GridIndex):
         _same_batching(p, single, index.points, index.single, "points", "index")
         if index.points.shape[1] != N:

@@ -1483,8 +1483,8 @@ int gecco_grid_radius_search_f32(const float* query, const int32_t* qorder, cons
  * lambda = (0.18, 0.3, 0.6), saliency 0.18.  Point 7 = (0, 1, 1), on a face: m = 14, lambda1 = lambda2 = 4/7; point 43 = (1, 1, 1): m =
  * 19, lambda = 10/19 three times.  The candidates are the 48 points inside the 12 edges, all with saliency 0.18 up to rounding in
  * the last place; every one is a keypoint (a non-maximum ball holds 10 points and no larger saliency), and nothing else is.
- * Two launches, one thread per sorted position in both: the saliency of every point (a walk over the cells its ball can reach, the
- * count and the nine sums in registers, the 3 x 3 problem in registers), then the selection (the same walk at r2n, a gather of
+ * Two launches, one thread per sorted position in both: the saliency of every point (a walk over the cells its ball can reach, the one walk of
+ * csrc/grid_walk.h that gecco_grid_radius_count_f32 / _search_f32 make as well, the count and the nine sums in registers, the 3 x 3 problem in registers), then the selection (the same walk at r2n, a gather of
  * saliency by index).  A thread writes its own words only: no atomics, no workspace, no allocation, no synchronisation, asynchronous
  * on `stream`.  Return -2 before anything is enqueued (and gecco_last_error) for: a null required pointer, B or N < 1, N above
  * GECCO_VOXEL_MAX_POINTS, a cell_size that is not a finite number > 0 with a finite reciprocal, a radius2 that is not a finite

@@ -111,6 +111,52 @@ def test_index_and_grid_order_equal_the_restatement(ops, N):
     assert one.single and one.keys.shape == (1, N) and torch.equal(one.keys[0], g.keys[1]) and torch.equal(one.perm[0], g.perm[1])
 
 
+def test_wide_boxes_scan_the_whole_cloud_once(ops):
+    """The branch of the walk no other test here reaches: boxes wider than BOX cells, answered by a scan of all N sorted positions that
+    must visit neither the cells nor the tail a second time.  tests/_iss_ref.py's coarse lattice (fp32 resolves it more coarsely than
+    a cell) with the grid's upper x face through it, so that more than half the points are off-grid: a second visit of the tail would
+    double the neighbours found there.  Alone and as cloud 1 of 2 beside an ordinary cloud, against the restatement and the direct form"""
+    from tests import _iss_ref as iss
+    cell, origin = iss.COARSE_CELL, (965921.375, 1e6, 1e6)
+    p = iss.coarse_lattice()
+    want = grid.build(p, cell, origin)
+    rows = {self_mode: grid.grid_rows(p, want, cell, self_mode) for self_mode in (True, False)}
+    R = grid.reach(cell)
+    wide = np.array([grid.box(q, want, R)[2] for q in p])
+    tail = want.perm[want.n_in_grid:]
+    assert len(p) == 200 and want.n_in_grid == 95 and rows[False].widest == 5 and wide.sum() == 163   # the input is what it is meant to be
+    assert sum(bool(wide[i] and np.isin(rows[True].grid[i], tail).any()) for i in range(200)) == 79
+    plain = ref.clouds(200)[0]
+    plain_index = grid.build(plain, cell)
+    plain_rows = {self_mode: grid.grid_rows(plain, plain_index, cell, self_mode) for self_mode in (True, False)}
+    assert plain_rows[False].widest <= grid.BOX and plain_index.n_in_grid == 200
+    both = _dev(np.stack([plain, p]))
+    cases = ((_dev(p), origin, lambda s: [rows[s]], "alone"),
+             (both, _dev(np.array([(0, 0, 0), origin], dtype=np.float32)), lambda s: [plain_rows[s], rows[s]], "cloud 1 of 2"))
+    for tp, org, expected, what in cases:
+        g = ops.build_grid_index(tp, cell, org)
+        assert g.n_in_grid.reshape(-1).tolist()[-1] == 95
+        for self_mode in (True, False):
+            other = None if self_mode else tp
+            direct = ops.radius_search(tp, other, cell, self_mode)
+            for order in ("grid", "index"):
+                indices, splits, d2, counts = grid.csr(expected(self_mode), order)
+                res = ops.radius_search(tp, radius=cell, exclude_self=self_mode, order=order, index=g)
+                _equal(res.indices, indices, f"{what}, self={self_mode}, order {order}")
+                _equal(res.row_splits, splits, f"{what}, self={self_mode}, order {order}: row_splits")
+                _equal(res.counts.reshape(len(expected(self_mode)), 200), counts, f"{what}, self={self_mode}, order {order}: counts")
+                _poison.assert_same_bits(res.distances, _dev(d2).sqrt(), f"{what}, self={self_mode}, order {order}: distances")
+                if order == "index":
+                    _same(res, direct, f"{what}, self={self_mode}: the direct form")
+                else:
+                    by_j, perm = _rows_sorted_by_j(res)
+                    assert torch.equal(by_j, direct.indices), f"{what}, self={self_mode}: order grid, the rows' members"
+                    _poison.assert_same_bits(res.distances[perm], direct.distances, f"{what}, self={self_mode}: order grid, distances")
+            count = ops.radius_count(tp, radius=cell, exclude_self=self_mode, index=g)
+            _equal(count.reshape(-1, 200), counts, f"{what}, self={self_mode}: radius_count")
+            assert torch.equal(count, ops.radius_count(tp, other, cell, self_mode)) and torch.equal(count, direct.counts), what
+
+
 @pytest.mark.parametrize("N", [1, 2, 63, 64, 65, 257, 1500])
 def test_equals_the_direct_form_at_every_edge(ops, N):
     """M = N at the lane / wave / workgroup edges x self mode and not x three radii x every order, through an index built for the

@@ -128,9 +128,14 @@ def test_sources_header_and_binding(lib):
     assert _lib.SIGNATURES["gecco_iss_keypoints_f32"][0] is ctypes.c_int and lib.gecco_iss_keypoints_f32 is not None
     assert gecco_amd.ISSResult._fields == ("mask", "saliency", "eigenvalues", "counts", "n_keypoints")
     assert callable(gecco_amd.iss_keypoints) and callable(gecco_amd.cloud_resolution)
-    text = open(os.path.join(ROOT, "gecco_amd", "csrc", "iss.hip")).read()
-    assert "fp contract(off)" in text and "CHANGE TOGETHER" in text
-    assert "CHANGE TOGETHER" in open(os.path.join(ROOT, "gecco_amd", "csrc", "grid.hip")).read()
+    csrc = os.path.join(ROOT, "gecco_amd", "csrc")
+    for name in ("grid.hip", "iss.hip"):   # one spelling of the walk, the reach and the cell of a bound
+        text = open(os.path.join(csrc, name)).read()
+        assert '#include "grid_walk.h"' in text and "nextafterf" not in text, name
+        assert not re.search(r"\b(grid_u|iss_u)\s*\(float", text) and not re.search(r"\b(iss_walk|iss_reach|ISS_BOX)\b", text), name
+    assert "fp contract(off)" in open(os.path.join(csrc, "iss.hip")).read()   # (iss_rotate and the moments)
+    walk = open(os.path.join(csrc, "grid_walk.h")).read()
+    assert "fp contract(off)" in walk and re.search(r"\bgrid_u\s*\(float", walk) and "grid_walk(" in walk
 
 
 def test_c_refusals_without_a_gpu(lib):
