@@ -2,6 +2,7 @@
 the definition, exported by the library and bound with the declared arity; the workspace query runs without a GPU; bad arguments are
 refused before anything is enqueued; the Python interface has the specified signatures; the ABI version did not move; CPU tensors raise;
 the numpy float32 reference (tests/_knn_ref.py) is itself a k-nearest-neighbour search, checked against an fp64 brute force."""
+import importlib
 import inspect
 import os
 import re
@@ -130,7 +131,7 @@ def test_python_interface():
     assert [par[n].default for n in list(par)[1:]] == [16, 2.0, False]
     for name in ("knn", "knn_gather", "statistical_outlier_mask"):
         assert getattr(gecco_amd, name) is getattr(pointops, name)
-    doc = pointops.__doc__
+    doc = importlib.import_module("gecco_amd.pointops.knn").__doc__   # (pointops.knn is the function)
     for piece in ("(dx*dx + dy*dy) + dz*dz", "LOWEST index", "without FMA contraction", "replaced by +inf", "[1, 6, 36, 7, 37, 42, 43]",
                   "[179, 209, 214, 173, 178, 208, 172]", "[0, 1, 6, 36]", "[0, 1, 2, 4]", "[0, 1, 2, 3]", "direct", "split",
                   "no float atomics", "KNN_MAX_K"):

@@ -3,6 +3,7 @@ by the library and bound with the declared arity, and the ABI version did not mo
 enqueued; `estimate_normals` has the specified signature, validates before any device call and raises for CPU tensors; the numpy float32
 restatement (tests/_normals_ref.py), judged by float64 eigh, stays within 8 * 2^-24 * trace on the residual — the margin under the
 device's bar of 32 — and gives the worked cases of the definition."""
+import importlib
 import inspect
 import os
 import re
@@ -79,7 +80,7 @@ def test_python_interface():
                          "form"]
     assert [par[n].default for n in list(par)[1:]] == [16, None, None, None, None, False, False, False, None]
     assert gecco_amd.estimate_normals is pointops.estimate_normals
-    doc = pointops.__doc__
+    doc = importlib.import_module("gecco_amd.pointops.normals").__doc__
     for piece in ("estimate_normals", "two passes, centred", "4 cyclic Jacobi sweeps", "(0, 0, 1)", "m < 3", "lowest axis",
                   "hybrid search", "32 * 2^-24"):
         assert piece in doc, piece
