@@ -20,7 +20,7 @@ from .pointops import KNN_MAX_K, knn, knn_gather, statistical_outlier_mask  # no
 from .pointops import estimate_normals  # noqa: E402,F401
 from .pointops import voxel_downsample, voxel_pool  # noqa: E402,F401
 from .pointops import ICP_MAX_ITERATIONS, ICPResult, icp, transform_points  # noqa: E402,F401
-from .pointops import DBSCAN_MAX_ROUNDS, DBSCANResult, cluster_dbscan, cluster_sizes  # noqa: E402,F401
+from .pointops import DBSCAN_MAX_ROUNDS, DBSCANResult, cluster_dbscan, cluster_dbscan_grid, cluster_sizes  # noqa: E402,F401
 from .pointops import RadiusNeighbors, radius_count, radius_outlier_mask, radius_search  # noqa: E402,F401
 from .pointops import GridIndex, build_grid_index  # noqa: E402,F401
 from .pointops import ISSResult, cloud_resolution, iss_keypoints  # noqa: E402,F401

@@ -489,4 +489,25 @@ int gecco_iss_keypoints_f32(const float* sorted, const int64_t* table_keys, cons
     return 0;
 }
 
+// DBSCAN on the grid index (dbscan.hip's grid form): gecco_dbscan_f32's outputs and workspace, the index as gecco_iss_keypoints_f32
+// takes it.  It stands here, behind the grid entries, for their checks.  Every refusal is -2, null pointers included
+int gecco_dbscan_grid_f32(const float* sorted, const int64_t* table_keys, const int32_t* table_range, const int32_t* n_in_grid,
+                          const float* origin, float cell_size, int32_t* labels, int32_t* n_clusters, int32_t* count, int32_t* rounds,
+                          int32_t* status, void* ws, int B, int N, float eps2, int min_points, int max_rounds, void* stream) {
+    if (!sorted || !table_keys || !table_range || !n_in_grid || !labels || !n_clusters || !status || !ws)
+        return fail(-2, "dbscan_grid: null argument");
+    if (const int bad = grid_points("dbscan_grid", B, N)) return bad;
+    if (!finite_positive(eps2)) return fail(-2, "dbscan_grid: eps2 = %g must be a finite number > 0", (double)eps2);
+    if (const int bad = grid_cell_size("dbscan_grid", cell_size)) return bad;
+    if (const int bad = grid_radius2_fits("dbscan_grid", "eps2", cell_size, eps2)) return bad;
+    if (min_points < 1) return fail(-2, "dbscan_grid: min_points = %d must be >= 1", min_points);
+    if (max_rounds < 0 || max_rounds > GECCO_DBSCAN_MAX_ROUNDS)
+        return fail(-2, "dbscan_grid: max_rounds = %d is not in 0 .. %d", max_rounds, GECCO_DBSCAN_MAX_ROUNDS);
+    const int rc = dbscan_grid_launch(sorted, reinterpret_cast<const long long*>(table_keys), table_range, n_in_grid, origin, cell_size, labels,
+                                      n_clusters, count, rounds, status, ws, B, N, eps2, min_points, max_rounds, (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "dbscan_grid: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
+    TRY(rc, "dbscan_grid");
+    return 0;
+}
+
 }  // extern "C"

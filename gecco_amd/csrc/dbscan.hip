@@ -13,16 +13,23 @@
 // The result is unique, and it is the labelling Open3D and scikit-learn produce (both visit points in index order and finish a cluster
 // before they open the next).
 //
-// Launches: 1 + 2 R + 2 for R = max_rounds, whatever the data; no host synchronisation, no allocation, so a call can be captured in a
-// graph.
-//   count          scan: count_i; parent_i = i for a core point, DBSCAN_NONE (above every index) for a non-core one; hook_i = i; the
-//                  cloud's round flags are cleared
-//   R x hook       scan: Shiloach-Vishkin with minimum hooking.  Before a round the forest is a set of stars (parent[parent[i]] ==
-//                  parent[i]).  A core i takes m_i = the minimum of parent[j] over its core neighbours j; when m_i < parent[i] it does an
-//                  integer atomicMin of m_i into hook[parent[i]] and sets the cloud's flag of this round
+// Two forms, one definition and one forest.  They differ only in how the three passes that ask "who is within eps of i" (count, hook,
+// border) find their candidates: the direct form (gecco_dbscan_f32) scans the whole cloud, the grid form (gecco_dbscan_grid_f32) walks
+// the cells of a grid index (grid.hip) that the ball can reach.  The cells only filter: membership is cloud_dist2_bits(q, p) <=
+// eps2_bits in both, so all six outputs are the same bits, rounds and the labels of a run stopped by the round limit included.
+//
+// Launches: 1 + 2 R + 2 (direct) or 2 + 2 R + 2 (grid) for R = max_rounds, whatever the data; no host synchronisation, no allocation, so
+// a call can be captured in a graph.
+//   init           grid form only, in index order: parent_i = DBSCAN_NONE, hook_i = i, root_i = -1, count_i = 0, the round flags cleared
+//   count          scan / walk: count_i; parent_i = i for a core point, DBSCAN_NONE (above every index) for a non-core one; in the
+//                  direct form also hook_i = i and the cloud's round flags cleared
+//   R x hook       scan / walk: Shiloach-Vishkin with minimum hooking.  Before a round the forest is a set of stars (parent[parent[i]]
+//                  == parent[i]).  A core i takes m_i = the minimum of parent[j] over its core neighbours j; when m_i < parent[i] it does
+//                  an integer atomicMin of m_i into hook[parent[i]] and sets the cloud's flag of this round
 //       compress   every core point chases hook from its parent to a fixed point (hook[r] <= r, so the walk descends and ends) and
 //                  writes the new parent: stars again.  It also resets the other hook buffer to hook_i = i for the next round
-//   border         scan: a core point writes its root (= its parent); a non-core point the minimum root over its core neighbours or -1
+//   border         scan / walk: a core point writes its root (= its parent); a non-core point the minimum root over its core neighbours
+//                  or -1
 //   label          one workgroup per cloud: the exclusive prefix count of "root_i == i" over the point index numbers the clusters;
 //                  labels, n_clusters, rounds and status
 // A round whose hook pass set no flag has found the fixed point: its compress and every later workgroup of that cloud return at once,
@@ -34,17 +41,29 @@
 // atomicMin target and the round's flag, which no thread of that launch reads.  So the parents ping-pong between two buffers (round r
 // reads buffer r & 1 and writes the other one; a cloud that stopped in round k, or ran out of rounds with k = R, has its forest in
 // buffer k & 1, which every workgroup of the border launch works out from the flags), and so do the hook words (compress of round r
-// prepares buffer (r + 1) & 1).  A minimum of integers does not depend on arrival order, so the state after a round is a pure function
-// of the state before it: rounds, and the labels of a run that hit the limit, are the same bits run to run and in any batch position.
+// prepares buffer (r + 1) & 1).  A minimum of integers does not depend on arrival order, nor on the order in which a thread meets its
+// neighbours, so the state after a round is a pure function of the state before it, the same function in both forms: rounds, and the
+// labels of a run that hit the limit, are the same bits run to run, in any batch position, at any workgroup size and through any index.
 // The label launch is the one place where a workgroup reads what it wrote itself, the ranks of the roots, on the two sides of a
 // barrier; no other workgroup touches that cloud's words.  No float atomics, integer atomicMin in global memory only.
 //
-// The scan is the loop of knn_scan_kernel (cloud_nn.h says why it is written out per kernel rather than shared): one thread per point,
-// the cloud streamed through LDS in tiles of CLOUD_TILE as (x, y, z, w), the next tile prefetched into registers, four candidates per
-// step and one branch.  Here w, which knn leaves 0, carries the integer the pass needs (parent[j]), and the three scans are one loop
-// with the pass as a template argument.  Only the direct form exists: the queries are the cloud itself (M = N), so the grid
-// B * ceil(N / T) fills the device wherever the N * N work is worth filling it for.
+// The direct scan is the loop of knn_scan_kernel (cloud_nn.h says why it is written out per kernel rather than shared): one thread per
+// point, the cloud streamed through LDS in tiles of CLOUD_TILE as (x, y, z, w), the next tile prefetched into registers, four candidates
+// per step and one branch.  Here w, which knn leaves 0, carries the integer the pass needs (parent[j]), and the three scans are one loop
+// with the pass as a template argument.  The queries are the cloud itself (M = N), so the grid B * ceil(N / T) fills the device wherever
+// the N * N work is worth filling it for.
+//
+// The grid walk is grid_walk of grid_walk.h, the one grid.hip and iss.hip call, where it is proved to miss no neighbour and every loop
+// is bounded; the three walks are one kernel with the pass as a template argument, launched as iss.hip launches its kernels: one thread
+// per SORTED POSITION, whose 16-byte load gives the coordinates and, in .w, the original index i.  Every workspace array stays indexed
+// by the original index, so compress and label are the direct form's kernels: a neighbour's parent is a 4-byte gather by the index in
+// the visited entry's .w, made only for entries inside the ball.  The index is the caller's memory: i and every gathered j are checked
+// against N before they address anything, and the init launch writes every word a later kernel reads, so whatever `sorted` holds (not a
+// permutation, say) compress and label chase in-range values only.  With a real index each point is owned by exactly one thread and the
+// init values of count, parent and root are all overwritten.  The walks take 32 (count), 36 (hook) and 38 (border) VGPRs at every
+// workgroup size, no LDS and no scratch.
 #include "cloud_nn.h"
+#include "grid_walk.h"
 #include "kernels.h"
 #include "launch_state.h"
 
@@ -155,6 +174,73 @@ __global__ __launch_bounds__(T) void dbscan_scan_kernel(const float* __restrict_
     }
 }
 
+// grid: B * chunks blocks of DBSCAN_THREADS points.  The grid form's first launch: every word compress, the walks and label read
+__global__ __launch_bounds__(DBSCAN_THREADS) void dbscan_grid_init_kernel(int* __restrict__ par0, int* __restrict__ hook0, int* __restrict__ root,
+                                                                          int* __restrict__ count, int* __restrict__ flags, int N, int chunks,
+                                                                          int R) {
+    const int b = (int)(blockIdx.x / (unsigned)chunks), chunk = (int)(blockIdx.x % (unsigned)chunks);
+    if (chunk == 0)
+        for (int r = threadIdx.x; r < R; r += DBSCAN_THREADS) flags[(size_t)b * R + r] = 0;
+    const int i = chunk * DBSCAN_THREADS + (int)threadIdx.x;
+    if (i >= N) return;   // (no barrier below)
+    const size_t o = (size_t)b * N + i;
+    par0[o] = DBSCAN_NONE;
+    hook0[o] = i;
+    root[o] = -1;
+    if (count) count[o] = 0;
+}
+
+// grid: B * tiles blocks of T sorted positions.  COUNT: out = parent buffer 0.  HOOK (round `round`): out = hook buffer round & 1.
+// BORDER: out = root.  The passes of dbscan_scan_kernel, the neighbours found by grid_walk; acc, own and who walks are the same
+template <int T, int PASS>
+__global__ __launch_bounds__(T) void dbscan_grid_kernel(const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,
+                                                        const int2* __restrict__ table_range, const int* __restrict__ n_in_grid,
+                                                        const float* __restrict__ origin, float inv, float reach, unsigned eps2_bits,
+                                                        const int* __restrict__ par0, const int* __restrict__ par1, int* __restrict__ out,
+                                                        int* __restrict__ count, int* __restrict__ flags, int min_points, int N, unsigned cap,
+                                                        int tiles, int R, int round) {
+    const int b = (int)(blockIdx.x / (unsigned)tiles);
+    int sel = 0;
+    if (PASS == DBSCAN_HOOK) {
+        if (round > 0 && flags[(size_t)b * R + round - 1] == 0) return;   // the cloud has stopped (uniform)
+        sel = round & 1;
+    }
+    if (PASS == DBSCAN_BORDER) sel = dbscan_hooked_rounds(flags, b, R) & 1;
+    const int t = (int)(blockIdx.x % (unsigned)tiles) * T + (int)threadIdx.x;
+    if (t >= N) return;   // (no barrier below)
+    const f32x4* sb = sorted + (size_t)b * N;
+    const f32x4 q = sb[t];
+    const unsigned i = __float_as_uint(q[3]);
+    if (i >= (unsigned)N) return;   // a sorted array no build wrote: the init launch's words stand
+    const size_t o = (size_t)b * N;
+    const int* par = PASS == DBSCAN_COUNT ? nullptr : (sel ? par1 : par0) + o;
+    const int own = PASS == DBSCAN_COUNT ? 0 : par[i];
+    // who walks: every finite point counts; a core point hooks; a non-core point looks for its border root
+    const bool walks = cloud_finite3(q[0], q[1], q[2]) && (PASS == DBSCAN_COUNT || (PASS == DBSCAN_HOOK ? own != DBSCAN_NONE : own == DBSCAN_NONE));
+    int acc = PASS == DBSCAN_COUNT ? 0 : DBSCAN_NONE;   // the neighbour count, or the minimum parent over the core neighbours
+    if (walks)
+        grid_walk(q[0], q[1], q[2], sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, reach,
+                  eps2_bits, N, cap, [&](const f32x4 p, unsigned) {
+                      if (PASS == DBSCAN_COUNT) {
+                          ++acc;
+                      } else {
+                          const unsigned j = __float_as_uint(p[3]);
+                          if (j < (unsigned)N) acc = min(acc, par[j]);   // a 4-byte gather, for entries inside the ball only
+                      }
+                  });
+    if (PASS == DBSCAN_COUNT) {
+        if (count) count[o + i] = acc;
+        out[o + i] = acc >= min_points ? (int)i : DBSCAN_NONE;
+    } else if (PASS == DBSCAN_HOOK) {
+        if (walks && acc < own) {   // own is a parent the init, count or compress launch wrote and not NONE: an index of this cloud
+            atomicMin(out + o + own, acc);
+            flags[(size_t)b * R + round] = 1;
+        }
+    } else {
+        out[o + i] = own != DBSCAN_NONE ? own : acc == DBSCAN_NONE ? -1 : acc;
+    }
+}
+
 // grid: B * chunks blocks of DBSCAN_THREADS points.  Round `round`: reads parent and hook buffer round & 1, writes the other two
 __global__ __launch_bounds__(DBSCAN_THREADS) void dbscan_compress_kernel(const int* __restrict__ par_in, const int* __restrict__ hook_in,
                                                                          int* __restrict__ par_out, int* __restrict__ hook_out,
@@ -238,23 +324,34 @@ __global__ __launch_bounds__(DBSCAN_LABEL_THREADS) void dbscan_label_kernel(cons
     }
 }
 
+// ws of GECCO_DBSCAN_WORKSPACE_BYTES(B, N, R), as both forms carve it: two parent buffers, two hook buffers and the roots, (B, N) int32
+// each, then the round flags (B, R)
+struct DbscanCarve {
+    int *par[2], *hook[2], *root, *flags;
+    DbscanCarve(void* ws, int B, int N) {
+        const size_t pts = (size_t)B * N;
+        int* w = static_cast<int*>(ws);
+        par[0] = w, par[1] = w + pts;
+        hook[0] = w + 2 * pts, hook[1] = w + 3 * pts;
+        root = w + 4 * pts;
+        flags = w + 5 * pts;
+        static_assert(GECCO_DBSCAN_WORKSPACE_BYTES(1, 1, 1) == 24, "the carve above is the header's formula");
+    }
+};
+
 }  // namespace
 
-// 1 + 2 R + 2 launches.  ws of GECCO_DBSCAN_WORKSPACE_BYTES(B, N, R): two parent buffers, two hook buffers and the roots, (B, N) int32
-// each, then the round flags (B, R).  Returns -2 for arguments out of range, -3 when the grid would pass 2^31 - 1 workgroups.
+// The direct form: 1 + 2 R + 2 launches.  Returns -2 for arguments out of range, -3 when the grid would pass 2^31 - 1 workgroups.
 int dbscan_launch(const float* points, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
                   int min_points, int R, hipStream_t st) {
     if (B < 1 || N < 1 || !(eps2 > 0.f) || !(eps2 <= 3.402823466e38f) || min_points < 1 || R < 0 || R > GECCO_DBSCAN_MAX_ROUNDS || !ws) return -2;
     const CloudPlan p = cloud_plan(B, N, N, 1, false, 256, device_cus());
     if (!p.fits()) return -3;   // (T <= DBSCAN_THREADS: the compress grid is no larger)
     const int chunks = (N + DBSCAN_THREADS - 1) / DBSCAN_THREADS;
-    const size_t pts = (size_t)B * N;
-    int* w = static_cast<int*>(ws);
-    int* par[2] = {w, w + pts};
-    int* hook[2] = {w + 2 * pts, w + 3 * pts};
-    int* root = w + 4 * pts;
-    int* flags = w + 5 * pts;
-    static_assert(GECCO_DBSCAN_WORKSPACE_BYTES(1, 1, 1) == 24, "the carve above is the header's formula");
+    const DbscanCarve c(ws, B, N);
+    int* const* par = c.par;
+    int* const* hook = c.hook;
+    int *root = c.root, *flags = c.flags;
     const unsigned eps2_bits = __builtin_bit_cast(unsigned, eps2);
 
     return dispatch_T(p.T, [&](auto t) -> int {
@@ -274,6 +371,51 @@ int dbscan_launch(const float* points, int* labels, int* n_clusters, int* count,
                            (int*)nullptr, (int*)nullptr, flags, eps2_bits, min_points, N, p.tiles, R, 0);
         hipLaunchKernelGGL(dbscan_label_kernel, dim3((unsigned)B), dim3(DBSCAN_LABEL_THREADS), 0, st, (const int*)root, hook[0],
                            (const int*)flags, labels, n_clusters, rounds, status, N, R);
+        return (int)hipGetLastError();
+    });
+}
+
+// The grid form: 2 + 2 R + 2 launches, compress and label the direct form's own.  The index as iss_launch takes it; origin nullable.
+// Returns -2 for arguments out of range (an eps2 above fp32(cell_size^2) among them), -3 when the grid would pass 2^31 - 1 workgroups.
+int dbscan_grid_launch(const float* sorted, const long long* table_keys, const int* table_range, const int* n_in_grid, const float* origin,
+                       float cell_size, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
+                       int min_points, int R, hipStream_t st) {
+    if (!sorted || !table_keys || !table_range || !n_in_grid || !labels || !n_clusters || !status || !ws) return -2;
+    if (B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS || !grid_radius2_ok(eps2, cell_size)) return -2;
+    if (min_points < 1 || R < 0 || R > GECCO_DBSCAN_MAX_ROUNDS) return -2;
+    const CloudPlan p = cloud_plan(B, N, N, 1, false, 256, device_cus());
+    if (!p.fits()) return -3;   // (T <= DBSCAN_THREADS: the init and compress grids are no larger)
+    const int chunks = (N + DBSCAN_THREADS - 1) / DBSCAN_THREADS;
+    const DbscanCarve c(ws, B, N);
+    const unsigned cap = (unsigned)GECCO_GRID_CAPACITY(N);
+    const unsigned eps2_bits = __builtin_bit_cast(unsigned, eps2);
+    const float inv = 1.0f / cell_size, reach = grid_reach(eps2);
+    const u64* tk = reinterpret_cast<const u64*>(table_keys);
+    const int2* tr = reinterpret_cast<const int2*>(table_range);
+    const f32x4* sp = reinterpret_cast<const f32x4*>(sorted);
+    const dim3 per_chunk((unsigned)(B * chunks)), chunk(DBSCAN_THREADS);
+
+    return dispatch_T(p.T, [&](auto t) -> int {
+        constexpr int T = decltype(t)::value;
+        const dim3 grid((unsigned)p.blocks), block(T);
+        auto walk = [&](auto pass, int* out, int* cnt, int round) {   // (the count pass reads no parents: it writes buffer 0)
+            constexpr bool reads = decltype(pass)::value != DBSCAN_COUNT;
+            hipLaunchKernelGGL((dbscan_grid_kernel<T, decltype(pass)::value>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, reach,
+                               eps2_bits, reads ? (const int*)c.par[0] : nullptr, reads ? (const int*)c.par[1] : nullptr, out, cnt, c.flags,
+                               min_points, N, cap, p.tiles, R, round);
+        };
+        hipLaunchKernelGGL(dbscan_grid_init_kernel, per_chunk, chunk, 0, st, c.par[0], c.hook[0], c.root, count, c.flags, N, chunks, R);
+        walk(std::integral_constant<int, DBSCAN_COUNT>{}, c.par[0], count, 0);
+        for (int r = 0; r < R; ++r) {
+            walk(std::integral_constant<int, DBSCAN_HOOK>{}, c.hook[r & 1], nullptr, r);
+            hipLaunchKernelGGL(dbscan_compress_kernel, per_chunk, chunk, 0, st, (const int*)c.par[r & 1], (const int*)c.hook[r & 1],
+                               c.par[(r + 1) & 1], c.hook[(r + 1) & 1], (const int*)c.flags, N, chunks, R, r);
+            const int rc = (int)hipGetLastError();
+            if (rc) return rc;
+        }
+        walk(std::integral_constant<int, DBSCAN_BORDER>{}, c.root, nullptr, 0);
+        hipLaunchKernelGGL(dbscan_label_kernel, dim3((unsigned)B), dim3(DBSCAN_LABEL_THREADS), 0, st, (const int*)c.root, c.hook[0],
+                           (const int*)c.flags, labels, n_clusters, rounds, status, N, R);
         return (int)hipGetLastError();
     });
 }

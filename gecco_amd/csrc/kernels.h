@@ -542,9 +542,14 @@ int voxel_launch(const float* points, const float* origin, float voxel_size, flo
                  int* n_voxels, void* ws, int B, int N, int V, hipStream_t st);
 // dbscan.hip — DBSCAN clustering (definition: gecco_dbscan_f32).  eps2 = fp32(eps * eps); count, rounds nullable; ws of
 // GECCO_DBSCAN_WORKSPACE_BYTES(B, N, R); 1 + 2 R + 2 launches for R = max_rounds.  -2: arguments out of range, -3: the grid would pass
-// 2^31 - 1 workgroups
+// 2^31 - 1 workgroups.  The grid form (definition: gecco_dbscan_grid_f32) finds its neighbours on the index of grid.hip, taken as
+// iss_launch takes it (origin nullable): the same outputs and workspace, 2 + 2 R + 2 launches; -2 also for null pointers, N above
+// GECCO_VOXEL_MAX_POINTS and an eps2 above fp32(cell_size^2)
 int dbscan_launch(const float* points, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
                   int min_points, int R, hipStream_t st);
+int dbscan_grid_launch(const float* sorted, const long long* table_keys, const int* table_range, const int* n_in_grid, const float* origin,
+                       float cell_size, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
+                       int min_points, int R, hipStream_t st);
 // radius.hip — fixed-radius neighbour search (definition: gecco_radius_search_f32): one launch.  r2 = fp32(r * r).  idx null: the counts
 // alone (count required).  row_start (the int64 exclusive prefix sum of the counts) given: the CSR fill, K = 0, d2 nullable.  Otherwise
 // the fixed-width fill, K >= 1 slots per row, d2 and count nullable.  -2: arguments out of range, -3: the grid would pass 2^31 - 1

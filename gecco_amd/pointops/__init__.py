@@ -12,15 +12,15 @@ definition, with its worked examples, launch counts and determinism guarantees:
     fpfh     FPFH descriptors and nearest-neighbour matching in feature space (csrc/fpfh.hip, gecco_fpfh_f32, gecco_feature_nn_f32)
     ransac   RANSAC registration from correspondences (csrc/ransac.hip, gecco_ransac_f32)
     plane    RANSAC plane segmentation, one plane or several (csrc/plane.hip, gecco_plane_ransac_f32)
-    dbscan   DBSCAN clustering (csrc/dbscan.hip, gecco_dbscan_f32)
+    dbscan   DBSCAN clustering, by direct scans (csrc/dbscan.hip, gecco_dbscan_f32) or on the grid index (gecco_dbscan_grid_f32)
     radius   fixed-radius neighbour search with the radius outlier filter, by a direct scan (csrc/radius.hip, gecco_radius_count_f32,
              gecco_radius_search_f32) or on a uniform-grid index for large clouds (csrc/grid.hip, gecco_grid_build_f32)
     iss      ISS keypoint detection on that index (csrc/iss.hip, gecco_iss_keypoints_f32)
     _args    the argument checks, moves to the device and result tails the families share
 
-Imports point one way: _args <- every family; knn <- normals, fpfh, radius; radius <- iss.  Every public name is passed on here and
-by `gecco_amd`: `gecco_amd.knn_gather is gecco_amd.pointops.knn_gather is` the one in the knn module.  `knn`, `icp` and `fpfh` are
-functions that share their module's name, so as attributes of this package those names are the functions;
+Imports point one way: _args <- every family; knn <- normals, fpfh, radius; radius <- iss, dbscan.  Every public name is passed on
+here and by `gecco_amd`: `gecco_amd.knn_gather is gecco_amd.pointops.knn_gather is` the one in the knn module.  `knn`, `icp` and
+`fpfh` are functions that share their module's name, so as attributes of this package those names are the functions;
 `importlib.import_module("gecco_amd.pointops.knn")` reaches the module.
 
 HIP tensors only: there is no CPU fallback (`voxel_pool`, `cluster_sizes` and `point_plane_distance`, plain torch, run on any device)."""
@@ -34,6 +34,7 @@ from .fpfh import FEATURE_MAX_DIM, FPFH_BINS, _feature_nn, _feature_nn_workspace
 from .ransac import RANSAC_MAX_HYPOTHESES, RANSAC_MAX_REFINE, RANSACResult, _ransac_workspace_bytes, ransac_registration  # noqa: F401
 from .plane import PLANE_MAX_HYPOTHESES, PLANE_MAX_REFINE, _PLANE_BLOCK_HYPOTHESES, PlaneResult, PlanesResult, _plane_workspace_bytes  # noqa: F401
 from .plane import point_plane_distance, segment_plane, segment_planes  # noqa: F401
-from .dbscan import DBSCAN_MAX_ROUNDS, DBSCANResult, _dbscan_workspace_bytes, cluster_dbscan, cluster_sizes, dbscan_default_rounds  # noqa: F401
+from .dbscan import DBSCAN_MAX_ROUNDS, DBSCANResult, _dbscan_workspace_bytes, cluster_dbscan, cluster_dbscan_grid, cluster_sizes  # noqa: F401
+from .dbscan import dbscan_default_rounds  # noqa: F401
 from .radius import GridIndex, RadiusNeighbors, _grid_sorted_keys, build_grid_index, radius_count, radius_outlier_mask, radius_search  # noqa: F401
 from .iss import ISSResult, iss_keypoints  # noqa: F401

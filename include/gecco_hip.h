@@ -1494,6 +1494,31 @@ int gecco_iss_keypoints_f32(const float* sorted, const int64_t* table_keys, cons
                             const float* origin, float cell_size, double* saliency, double* eigenvalues, int32_t* counts, uint8_t* mask, int B,
                             int N, float salient_radius2, float non_max_radius2, double gamma_21, double gamma_32, int min_neighbors,
                             void* stream);
+/* DBSCAN clustering on the grid index above (csrc/dbscan.hip, the grid form): gecco_dbscan_f32 with its three scans of the whole cloud
+ * (count, hook, border) replaced by walks over the cells a ball of eps can reach.  The cloud is the one the index was built over;
+ * sorted, table_keys, table_range, n_in_grid, origin and cell_size are that index, as gecco_iss_keypoints_f32 takes it.
+ * The DEFINITION is gecco_dbscan_f32's, word for word: the cells only filter, j is a neighbour of i iff dist2(i, j) <= eps2 on the
+ * bits, and nothing else.  labels, n_clusters, count, rounds and status are the direct form's bit for bit, through any index whose
+ * cell_size serves eps2 (any origin, any cell), also rounds and the labels of a run stopped by max_rounds: a minimum of integers depends
+ * neither on arrival order nor on the order in which a thread meets its neighbours, so the state after a round is the same function
+ * of the state before it in both forms.  The same bits run to run, in any batch position and at any workgroup size.
+ * 2 + 2 max_rounds + 2 launches whatever the data: init (in index order: no parent, hook_i = i, no root, count 0, the round flags
+ * cleared), count, max_rounds rounds of hook + compress, border, label.  The walks are one thread per sorted position (the one walk of
+ * csrc/grid_walk.h); every workspace array stays indexed by the original point index, compress and label are gecco_dbscan_f32's own
+ * kernels, and a neighbour's parent is a 4-byte gather for the entries inside the ball.  Memory safety does not depend on the index's
+ * contents: the original index in sorted[.].w is checked against N before it addresses anything and the init launch writes every word a
+ * later kernel reads, so a `sorted` that is no permutation gives meaningless labels and no access outside the buffers.
+ * Outputs and workspace are gecco_dbscan_f32's: labels (B, N), n_clusters (B), status (B) int32 required, count (B, N) and rounds (B)
+ * may each be NULL, every element of a given output is written; ws of GECCO_DBSCAN_WORKSPACE_BYTES(B, N, max_rounds) bytes, carved the
+ * same way, never read before the call has written it; origin may be NULL (zeros).  No float atomics (the integer atomicMin of the
+ * hook pass only), no allocation, no host synchronisation, asynchronous on `stream`: the call can be captured in a graph.
+ * Return -2 before anything is enqueued (and gecco_last_error) for: a null required pointer, B or N < 1, N above
+ * GECCO_VOXEL_MAX_POINTS, an eps2 that is not a finite number > 0, a cell_size that is not a finite number > 0 with a finite
+ * reciprocal, an eps2 above fp32(cell_size * cell_size) (build an index with a larger cell), min_points < 1, max_rounds outside 0 ..
+ * GECCO_DBSCAN_MAX_ROUNDS; -3 for a grid above 2^31 - 1 workgroups. */
+int gecco_dbscan_grid_f32(const float* sorted, const int64_t* table_keys, const int32_t* table_range, const int32_t* n_in_grid,
+                          const float* origin, float cell_size, int32_t* labels, int32_t* n_clusters, int32_t* count, int32_t* rounds,
+                          int32_t* status, void* ws, int B, int N, float eps2, int min_points, int max_rounds, void* stream);
 
 /* ---- ConvNeXt conditioner, channels-last on the device (ConvNeXtExtractor, models/feature_pyramid.py:28-73,
  * = torchvision's ConvNeXt stages).  Activations are (B, H, W, C) fp32.  The pointwise linears of a CNBlock run through

@@ -1,8 +1,9 @@
-"""Time DBSCAN clustering (gecco_amd.pointops.cluster_dbscan, csrc/dbscan.hip) at the three shapes it exists for, beside the only thing a
-user has without it on the same device: torch.cdist <= eps as an adjacency matrix, core points from its row sums, and minimum-label
-propagation by masked row minima in a host loop to its fixed point.
+"""Time DBSCAN clustering (gecco_amd.pointops.cluster_dbscan and cluster_dbscan_grid, csrc/dbscan.hip) at the three shapes it exists for:
+the direct form beside the grid form, and beside the only thing a user has without either on the same device: torch.cdist <= eps as
+an adjacency matrix, core points from its row sums, and minimum-label propagation by masked row minima in a host loop to its fixed
+point.
 
-    python tools/bench_dbscan.py [--reps 10] [--out FILE] [--trace-dir DIR]
+    python tools/bench_dbscan.py [--reps 10] [--torch 1] [--out FILE] [--trace-dir DIR]
 
 (a) 16 x 2048 points and (b) 64 x 2048 points (evaluation / training clouds): 24 Gaussian blobs (sigma 0.02, centres uniform in the unit
 cube) of 75 points and 248 uniform clutter points, eps = 0.025; (c) 1 x 100 000 points (the upsampler's output): 40 blobs of 2250 points
@@ -12,6 +13,11 @@ actually needed (the difference is the cost of the launches that return at once)
 composition keeps the boolean adjacency matrix where the whole batch's fits 1 GiB (a, b) and recomputes it per sweep in row chunks
 whose (rows, N) matrix stays under 1 GiB where it does not (c: 10 GB), and synchronises once per sweep.  cdist forms its distances in
 another order of roundings, so a pair at the bound may fall differently: the agreement of the two partitions is reported, not required.
+The two forms (`forms`): the direct call, the grid call on a prebuilt index (cell_size = eps, origin 0: what index=None builds), the
+grid call including the build of that index, and the build alone (`build_grid_index`: the key launch, torch's sort, the build launch),
+all at the default round limit and timed in ALTERNATION rounds of direct, grid, grid + build, build, so that a drift of the machine
+falls on all four alike; the median of each over the rounds is reported with its spread (max - min over the rounds), and the outputs
+of the two forms are required to be equal.  --torch 0 leaves the torch composition out.
 Every callable is warmed up once and timed by HIP events over `reps` windows (the median is reported; a window of the library call is
 INNER back-to-back calls, divided by INNER); each shape runs in a child process of its own under a time limit, and the first failure
 ends the run.  With --trace-dir every shape is run once more, alone, under `rocprofv3 --kernel-trace --stats` (no counters), and the
@@ -31,6 +37,7 @@ MIN_POINTS = 10
 STEP_SECONDS = 300
 INNER = {"a_16x2048": 10, "b_64x2048": 5, "c_1x100000": 1}   # library calls per timing window
 TRACE_CALLS = 3
+ALTERNATION = 3   # rounds of (direct, grid, grid + build, build)
 GIB = 1 << 30
 
 
@@ -113,7 +120,61 @@ def raw_call(pointops, p, eps, R):
     return go, out
 
 
-def run_shape(name, reps, trace_only=0):
+def raw_grid_call(pointops, index, eps, R):
+    """gecco_dbscan_grid_f32 alone on a ready index and ready buffers: returns the callable and its outputs"""
+    import ctypes as C
+    import torch
+    from gecco_amd import _lib
+    lib = _lib.load()
+    B, N, _ = index.points.shape
+    dev = index.points.device
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = dict(labels=i32(B, N), n_clusters=i32(B), count=i32(B, N), rounds=i32(B), status=i32(B))
+    ws = torch.empty(pointops._dbscan_workspace_bytes(B, N, R), dtype=torch.uint8, device=dev)
+    e = C.c_float(eps).value
+    eps2 = C.c_float(e * e).value
+    st = stream()
+
+    def go():
+        _lib.check(lib.gecco_dbscan_grid_f32(vp(index.sorted_points), vp(index.table_keys), vp(index.table_range), vp(index.n_in_grid),
+                                             vp(index.origin), index.cell_size, vp(out["labels"]), vp(out["n_clusters"]), vp(out["count"]),
+                                             vp(out["rounds"]), vp(out["status"]), vp(ws), B, N, eps2, MIN_POINTS, R, st), "gecco_dbscan_grid_f32")
+    return go, out
+
+
+def forms(pointops, p, eps, R, go_direct, out_direct, reps, inner):
+    """the direct form beside the grid form (module docstring): {name: median ms over the alternation rounds} and the spreads"""
+    import statistics
+    import torch
+    index = pointops.build_grid_index(p, eps)
+    go_grid, out_grid = raw_grid_call(pointops, index, eps, R)
+    built = []
+
+    def build():
+        built[:] = [pointops.build_grid_index(p, eps)]
+
+    def grid_with_build():
+        build()
+        raw_grid_call(pointops, built[0], eps, R)[0]()   # (fresh outputs and workspace: what a call through Python allocates)
+    calls = (("direct_ms", go_direct, inner), ("grid_prebuilt_ms", go_grid, inner), ("grid_with_build_ms", grid_with_build, 1),
+             ("grid_build_ms", build, 1))
+    ms = {name: [] for name, _, _ in calls}
+    for _ in range(ALTERNATION):
+        for name, fn, n in calls:
+            ms[name].append(timed(fn, reps, n))
+    for k in ("labels", "n_clusters", "count", "rounds", "status"):
+        assert torch.equal(out_grid[k], out_direct[k]), f"the grid form's {k} differ from the direct form's"
+    res = {name: round(statistics.median(v), 4) for name, v in ms.items()}
+    res["spread_ms"] = {name: round(max(v) - min(v), 4) for name, v in ms.items()}
+    res["direct_over_grid_prebuilt"] = round(res["direct_ms"] / res["grid_prebuilt_ms"], 2)
+    res["direct_over_grid_with_build"] = round(res["direct_ms"] / res["grid_with_build_ms"], 2)
+    res["launches_grid"] = 2 + 2 * R + 2
+    res["python_grid_call_ms"] = round(timed(lambda: pointops.cluster_dbscan_grid(p, eps, MIN_POINTS), reps), 4)
+    res["python_grid_call_prebuilt_ms"] = round(timed(lambda: pointops.cluster_dbscan_grid(p, eps, MIN_POINTS, index=index), reps), 4)
+    return res
+
+
+def run_shape(name, reps, trace_only=0, with_torch=1):
     import torch
     pointops = setup(__file__)
     B, blobs, per, clutter, eps = SHAPES[name]
@@ -139,6 +200,10 @@ def run_shape(name, reps, trace_only=0):
     res["kernel_at_rounds_needed_ms"] = round(timed(go_needed, reps, INNER[name]), 4)
     assert torch.equal(out_needed["labels"], labels) and int(out_needed["status"].max()) == 0
     res["python_call_ms"] = round(timed(lambda: pointops.cluster_dbscan(p, eps, MIN_POINTS), reps), 4)
+    res["forms"] = forms(pointops, p, eps, R, go, out, reps, INNER[name])
+    if not with_torch:
+        print(json.dumps({name: res}))
+        return
     sweeps = []
 
     def route():
@@ -200,7 +265,7 @@ if __name__ == "__main__":
         at = sys.argv.index("--trace-dir")
         directory = sys.argv[at + 1]
         del sys.argv[at:at + 2]
-        main(__file__, "dbscan", SHAPES, STEP_SECONDS, run_shape)
+        main(__file__, "dbscan", SHAPES, STEP_SECONDS, run_shape, options=(("--traceonly", 0), ("--torch", 1)))
         print(json.dumps({"bench": "dbscan_trace", **trace(directory)}))
     else:
-        main(__file__, "dbscan", SHAPES, STEP_SECONDS, run_shape, options=(("--traceonly", 0),))
+        main(__file__, "dbscan", SHAPES, STEP_SECONDS, run_shape, options=(("--traceonly", 0), ("--torch", 1)))
