@@ -433,19 +433,28 @@ static int grid_radius2_fits(const char* who, const char* name, float cell_size,
                     (double)(cell_size * cell_size));
     return 0;
 }
-static int grid_radius_common(const char* who, int B, int M, int N, float cell_size, float radius2, int exclude_self) {
-    if (const int bad = radius_common(who, B, M, N, radius2, exclude_self)) return bad;
-    if (N > GECCO_VOXEL_MAX_POINTS) return fail(-2, "%s: N = %d above %d", who, N, GECCO_VOXEL_MAX_POINTS);
+// The built index of an entry point that reads one, as the launchers take it (kernels.h's GridIndexArgs), behind the checks every such
+// entry makes of it: the four required pointers, grid_points and grid_cell_size.  The two radius entries call radius_common first, which
+// leaves grid_points only N's upper bound to refuse
+static int grid_index(const char* who, const float* sorted, const int64_t* table_keys, const int32_t* table_range, const int32_t* n_in_grid,
+                      const float* origin, float cell_size, int B, int N, GridIndexArgs& index) {
+    if (!sorted || !table_keys || !table_range || !n_in_grid) return fail(-2, "%s: null argument", who);
+    if (const int bad = grid_points(who, B, N)) return bad;
     if (const int bad = grid_cell_size(who, cell_size)) return bad;
-    return grid_radius2_fits(who, "radius2", cell_size, radius2);
+    static_assert(sizeof(long long) == sizeof(int64_t), "table_keys are read as long long");
+    index = GridIndexArgs{sorted, reinterpret_cast<const long long*>(table_keys), table_range, n_in_grid, origin, cell_size};
+    return 0;
 }
 int gecco_grid_radius_count_f32(const float* query, const int32_t* qorder, const float* sorted, const int64_t* table_keys,
                                 const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size, int32_t* count,
                                 int B, int M, int N, float radius2, int exclude_self, void* stream) {
-    if (!query || !sorted || !table_keys || !table_range || !n_in_grid || !count) return fail(-2, "grid_radius_count: null argument");
-    if (const int bad = grid_radius_common("grid_radius_count", B, M, N, cell_size, radius2, exclude_self)) return bad;
-    const int rc = grid_radius_launch(query, qorder, sorted, reinterpret_cast<const long long*>(table_keys), table_range, n_in_grid, origin,
-                                      cell_size, nullptr, nullptr, nullptr, count, B, M, N, radius2, exclude_self ? 1 : 0, (hipStream_t)stream);
+    if (!query || !count) return fail(-2, "grid_radius_count: null argument");
+    if (const int bad = radius_common("grid_radius_count", B, M, N, radius2, exclude_self)) return bad;
+    GridIndexArgs index;
+    if (const int bad = grid_index("grid_radius_count", sorted, table_keys, table_range, n_in_grid, origin, cell_size, B, N, index)) return bad;
+    if (const int bad = grid_radius2_fits("grid_radius_count", "radius2", cell_size, radius2)) return bad;
+    const int rc = grid_radius_launch(query, qorder, index, nullptr, nullptr, nullptr, count, B, M, N, radius2, exclude_self ? 1 : 0,
+                                      (hipStream_t)stream);
     if (rc == -3) return fail(-3, "grid_radius_count: the grid for B = %d, M = %d passes 2^31 - 1 workgroups", B, M);
     TRY(rc, "grid_radius_count");
     return 0;
@@ -454,10 +463,12 @@ int gecco_grid_radius_search_f32(const float* query, const int32_t* qorder, cons
                                  const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size,
                                  const int64_t* row_start, int32_t* idx, float* d2, int B, int M, int N, float radius2, int exclude_self,
                                  void* stream) {
-    if (!query || !sorted || !table_keys || !table_range || !n_in_grid || !row_start || !idx) return fail(-2, "grid_radius_search: null argument");
-    if (const int bad = grid_radius_common("grid_radius_search", B, M, N, cell_size, radius2, exclude_self)) return bad;
-    const int rc = grid_radius_launch(query, qorder, sorted, reinterpret_cast<const long long*>(table_keys), table_range, n_in_grid, origin,
-                                      cell_size, reinterpret_cast<const long long*>(row_start), idx, d2, nullptr, B, M, N, radius2,
+    if (!query || !row_start || !idx) return fail(-2, "grid_radius_search: null argument");
+    if (const int bad = radius_common("grid_radius_search", B, M, N, radius2, exclude_self)) return bad;
+    GridIndexArgs index;
+    if (const int bad = grid_index("grid_radius_search", sorted, table_keys, table_range, n_in_grid, origin, cell_size, B, N, index)) return bad;
+    if (const int bad = grid_radius2_fits("grid_radius_search", "radius2", cell_size, radius2)) return bad;
+    const int rc = grid_radius_launch(query, qorder, index, reinterpret_cast<const long long*>(row_start), idx, d2, nullptr, B, M, N, radius2,
                                       exclude_self ? 1 : 0, (hipStream_t)stream);
     if (rc == -3) return fail(-3, "grid_radius_search: the grid for B = %d, M = %d passes 2^31 - 1 workgroups", B, M);
     TRY(rc, "grid_radius_search");
@@ -473,38 +484,36 @@ int gecco_iss_keypoints_f32(const float* sorted, const int64_t* table_keys, cons
                             const float* origin, float cell_size, double* saliency, double* eigenvalues, int32_t* counts, uint8_t* mask, int B,
                             int N, float salient_radius2, float non_max_radius2, double gamma_21, double gamma_32, int min_neighbors,
                             void* stream) {
-    if (!sorted || !table_keys || !table_range || !n_in_grid || !saliency || !mask) return fail(-2, "iss_keypoints: null argument");
-    if (const int bad = grid_points("iss_keypoints", B, N)) return bad;
-    if (const int bad = grid_cell_size("iss_keypoints", cell_size)) return bad;
+    if (!saliency || !mask) return fail(-2, "iss_keypoints: null argument");
+    GridIndexArgs index;
+    if (const int bad = grid_index("iss_keypoints", sorted, table_keys, table_range, n_in_grid, origin, cell_size, B, N, index)) return bad;
     if (const int bad = iss_radius2("salient_radius2", cell_size, salient_radius2)) return bad;
     if (const int bad = iss_radius2("non_max_radius2", cell_size, non_max_radius2)) return bad;
     if (!(gamma_21 > 0.0) || !(gamma_21 <= 1.7976931348623157e308) || !(gamma_32 > 0.0) || !(gamma_32 <= 1.7976931348623157e308))
         return fail(-2, "iss_keypoints: gamma_21 = %g and gamma_32 = %g must be finite numbers > 0", gamma_21, gamma_32);
     if (min_neighbors < 1) return fail(-2, "iss_keypoints: min_neighbors = %d must be >= 1", min_neighbors);
-    const int rc = iss_launch(sorted, reinterpret_cast<const long long*>(table_keys), table_range, n_in_grid, origin, cell_size, saliency,
-                              eigenvalues, counts, mask, B, N, salient_radius2, non_max_radius2, gamma_21, gamma_32, min_neighbors,
-                              (hipStream_t)stream);
+    const int rc = iss_launch(index, saliency, eigenvalues, counts, mask, B, N, salient_radius2, non_max_radius2, gamma_21, gamma_32,
+                              min_neighbors, (hipStream_t)stream);
     if (rc == -3) return fail(-3, "iss_keypoints: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
     TRY(rc, "iss_keypoints");
     return 0;
 }
 
-// DBSCAN on the grid index (dbscan.hip's grid form): gecco_dbscan_f32's outputs and workspace, the index as gecco_iss_keypoints_f32
-// takes it.  It stands here, behind the grid entries, for their checks.  Every refusal is -2, null pointers included
+// DBSCAN on the grid index (dbscan.hip's grid form): gecco_dbscan_f32's outputs and workspace, the index through grid_index as every
+// entry above.  It stands here, behind the grid entries, for their checks.  Every refusal is -2, null pointers included
 int gecco_dbscan_grid_f32(const float* sorted, const int64_t* table_keys, const int32_t* table_range, const int32_t* n_in_grid,
                           const float* origin, float cell_size, int32_t* labels, int32_t* n_clusters, int32_t* count, int32_t* rounds,
                           int32_t* status, void* ws, int B, int N, float eps2, int min_points, int max_rounds, void* stream) {
-    if (!sorted || !table_keys || !table_range || !n_in_grid || !labels || !n_clusters || !status || !ws)
-        return fail(-2, "dbscan_grid: null argument");
-    if (const int bad = grid_points("dbscan_grid", B, N)) return bad;
+    if (!labels || !n_clusters || !status || !ws) return fail(-2, "dbscan_grid: null argument");
+    GridIndexArgs index;
+    if (const int bad = grid_index("dbscan_grid", sorted, table_keys, table_range, n_in_grid, origin, cell_size, B, N, index)) return bad;
     if (!finite_positive(eps2)) return fail(-2, "dbscan_grid: eps2 = %g must be a finite number > 0", (double)eps2);
-    if (const int bad = grid_cell_size("dbscan_grid", cell_size)) return bad;
     if (const int bad = grid_radius2_fits("dbscan_grid", "eps2", cell_size, eps2)) return bad;
     if (min_points < 1) return fail(-2, "dbscan_grid: min_points = %d must be >= 1", min_points);
     if (max_rounds < 0 || max_rounds > GECCO_DBSCAN_MAX_ROUNDS)
         return fail(-2, "dbscan_grid: max_rounds = %d is not in 0 .. %d", max_rounds, GECCO_DBSCAN_MAX_ROUNDS);
-    const int rc = dbscan_grid_launch(sorted, reinterpret_cast<const long long*>(table_keys), table_range, n_in_grid, origin, cell_size, labels,
-                                      n_clusters, count, rounds, status, ws, B, N, eps2, min_points, max_rounds, (hipStream_t)stream);
+    const int rc = dbscan_grid_launch(index, labels, n_clusters, count, rounds, status, ws, B, N, eps2, min_points, max_rounds,
+                                      (hipStream_t)stream);
     if (rc == -3) return fail(-3, "dbscan_grid: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
     TRY(rc, "dbscan_grid");
     return 0;

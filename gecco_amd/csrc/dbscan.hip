@@ -19,7 +19,7 @@
 // eps2_bits in both, so all six outputs are the same bits, rounds and the labels of a run stopped by the round limit included.
 //
 // Launches: 1 + 2 R + 2 (direct) or 2 + 2 R + 2 (grid) for R = max_rounds, whatever the data; no host synchronisation, no allocation, so
-// a call can be captured in a graph.
+// a call can be captured in a graph.  Both forms run them through one driver (dbscan_drive); a form supplies how a pass is launched.
 //   init           grid form only, in index order: parent_i = DBSCAN_NONE, hook_i = i, root_i = -1, count_i = 0, the round flags cleared
 //   count          scan / walk: count_i; parent_i = i for a core point, DBSCAN_NONE (above every index) for a non-core one; in the
 //                  direct form also hook_i = i and the cloud's round flags cleared
@@ -54,8 +54,9 @@
 // the N * N work is worth filling it for.
 //
 // The grid walk is grid_walk of grid_walk.h, the one grid.hip and iss.hip call, where it is proved to miss no neighbour and every loop
-// is bounded; the three walks are one kernel with the pass as a template argument, launched as iss.hip launches its kernels: one thread
-// per SORTED POSITION, whose 16-byte load gives the coordinates and, in .w, the original index i.  Every workspace array stays indexed
+// is bounded; the three walks are one kernel with the pass as a template argument, which takes the index as one GridView by value (made
+// by grid_walk.h's grid_view of the launcher's GridIndexArgs, kernels.h) and runs, as iss.hip's kernels do, one thread per SORTED
+// POSITION, whose 16-byte load gives the coordinates and, in .w, the original index i.  Every workspace array stays indexed
 // by the original index, so compress and label are the direct form's kernels: a neighbour's parent is a 4-byte gather by the index in
 // the visited entry's .w, made only for entries inside the ball.  The index is the caller's memory: i and every gathered j are checked
 // against N before they address anything, and the init launch writes every word a later kernel reads, so whatever `sorted` holds (not a
@@ -193,12 +194,10 @@ __global__ __launch_bounds__(DBSCAN_THREADS) void dbscan_grid_init_kernel(int* _
 // grid: B * tiles blocks of T sorted positions.  COUNT: out = parent buffer 0.  HOOK (round `round`): out = hook buffer round & 1.
 // BORDER: out = root.  The passes of dbscan_scan_kernel, the neighbours found by grid_walk; acc, own and who walks are the same
 template <int T, int PASS>
-__global__ __launch_bounds__(T) void dbscan_grid_kernel(const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,
-                                                        const int2* __restrict__ table_range, const int* __restrict__ n_in_grid,
-                                                        const float* __restrict__ origin, float inv, float reach, unsigned eps2_bits,
-                                                        const int* __restrict__ par0, const int* __restrict__ par1, int* __restrict__ out,
-                                                        int* __restrict__ count, int* __restrict__ flags, int min_points, int N, unsigned cap,
-                                                        int tiles, int R, int round) {
+__global__ __launch_bounds__(T) void dbscan_grid_kernel(const GridView index, float reach, unsigned eps2_bits, const int* __restrict__ par0,
+                                                        const int* __restrict__ par1, int* __restrict__ out, int* __restrict__ count,
+                                                        int* __restrict__ flags, int min_points, int tiles, int R, int round) {
+    const int N = index.N;
     const int b = (int)(blockIdx.x / (unsigned)tiles);
     int sel = 0;
     if (PASS == DBSCAN_HOOK) {
@@ -208,8 +207,7 @@ __global__ __launch_bounds__(T) void dbscan_grid_kernel(const f32x4* __restrict_
     if (PASS == DBSCAN_BORDER) sel = dbscan_hooked_rounds(flags, b, R) & 1;
     const int t = (int)(blockIdx.x % (unsigned)tiles) * T + (int)threadIdx.x;
     if (t >= N) return;   // (no barrier below)
-    const f32x4* sb = sorted + (size_t)b * N;
-    const f32x4 q = sb[t];
+    const f32x4 q = index.cloud(b)[t];
     const unsigned i = __float_as_uint(q[3]);
     if (i >= (unsigned)N) return;   // a sorted array no build wrote: the init launch's words stand
     const size_t o = (size_t)b * N;
@@ -219,15 +217,14 @@ __global__ __launch_bounds__(T) void dbscan_grid_kernel(const f32x4* __restrict_
     const bool walks = cloud_finite3(q[0], q[1], q[2]) && (PASS == DBSCAN_COUNT || (PASS == DBSCAN_HOOK ? own != DBSCAN_NONE : own == DBSCAN_NONE));
     int acc = PASS == DBSCAN_COUNT ? 0 : DBSCAN_NONE;   // the neighbour count, or the minimum parent over the core neighbours
     if (walks)
-        grid_walk(q[0], q[1], q[2], sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, reach,
-                  eps2_bits, N, cap, [&](const f32x4 p, unsigned) {
-                      if (PASS == DBSCAN_COUNT) {
-                          ++acc;
-                      } else {
-                          const unsigned j = __float_as_uint(p[3]);
-                          if (j < (unsigned)N) acc = min(acc, par[j]);   // a 4-byte gather, for entries inside the ball only
-                      }
-                  });
+        grid_walk(index, b, q[0], q[1], q[2], reach, eps2_bits, [&](const f32x4 p, unsigned) {
+            if (PASS == DBSCAN_COUNT) {
+                ++acc;
+            } else {
+                const unsigned j = __float_as_uint(p[3]);
+                if (j < (unsigned)N) acc = min(acc, par[j]);   // a 4-byte gather, for entries inside the ball only
+            }
+        });
     if (PASS == DBSCAN_COUNT) {
         if (count) count[o + i] = acc;
         out[o + i] = acc >= min_points ? (int)i : DBSCAN_NONE;
@@ -339,83 +336,77 @@ struct DbscanCarve {
     }
 };
 
+// What both forms test and plan before their first launch: -2 for arguments out of range, -3 when the grid of a neighbourhood pass would
+// pass 2^31 - 1 workgroups (T <= DBSCAN_THREADS: the init and compress grids are no larger), 0 with the plan of the passes in p
+int dbscan_plan(int B, int N, float eps2, int min_points, int R, const void* ws, CloudPlan& p) {
+    if (B < 1 || N < 1 || !(eps2 > 0.f) || !(eps2 <= 3.402823466e38f) || min_points < 1 || R < 0 || R > GECCO_DBSCAN_MAX_ROUNDS || !ws) return -2;
+    p = cloud_plan(B, N, N, 1, false, 256, device_cus());
+    return p.fits() ? 0 : -3;
+}
+
+// The launches of both forms, in the order of the header's table: the count pass, R x (hook pass, compress), the border pass, label.
+// pass(kind, out, count, round) launches one neighbourhood pass of the form, kind an integral_constant of DBSCAN_COUNT / HOOK / BORDER
+// (the grid form's launches its init kernel ahead of the count pass); the buffers a pass and a compress read and write are chosen here
+template <class Pass>
+int dbscan_drive(const DbscanCarve& c, int* labels, int* n_clusters, int* count, int* rounds, int* status, int B, int N, int R, int chunks,
+                 hipStream_t st, Pass pass) {
+    pass(std::integral_constant<int, DBSCAN_COUNT>{}, c.par[0], count, 0);
+    for (int r = 0; r < R; ++r) {
+        pass(std::integral_constant<int, DBSCAN_HOOK>{}, c.hook[r & 1], nullptr, r);
+        hipLaunchKernelGGL(dbscan_compress_kernel, dim3((unsigned)(B * chunks)), dim3(DBSCAN_THREADS), 0, st, (const int*)c.par[r & 1],
+                           (const int*)c.hook[r & 1], c.par[(r + 1) & 1], c.hook[(r + 1) & 1], (const int*)c.flags, N, chunks, R, r);
+        const int rc = (int)hipGetLastError();
+        if (rc) return rc;
+    }
+    pass(std::integral_constant<int, DBSCAN_BORDER>{}, c.root, nullptr, 0);
+    hipLaunchKernelGGL(dbscan_label_kernel, dim3((unsigned)B), dim3(DBSCAN_LABEL_THREADS), 0, st, (const int*)c.root, c.hook[0],
+                       (const int*)c.flags, labels, n_clusters, rounds, status, N, R);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 // The direct form: 1 + 2 R + 2 launches.  Returns -2 for arguments out of range, -3 when the grid would pass 2^31 - 1 workgroups.
 int dbscan_launch(const float* points, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
                   int min_points, int R, hipStream_t st) {
-    if (B < 1 || N < 1 || !(eps2 > 0.f) || !(eps2 <= 3.402823466e38f) || min_points < 1 || R < 0 || R > GECCO_DBSCAN_MAX_ROUNDS || !ws) return -2;
-    const CloudPlan p = cloud_plan(B, N, N, 1, false, 256, device_cus());
-    if (!p.fits()) return -3;   // (T <= DBSCAN_THREADS: the compress grid is no larger)
+    CloudPlan p;
+    if (const int rc = dbscan_plan(B, N, eps2, min_points, R, ws, p)) return rc;
     const int chunks = (N + DBSCAN_THREADS - 1) / DBSCAN_THREADS;
     const DbscanCarve c(ws, B, N);
-    int* const* par = c.par;
-    int* const* hook = c.hook;
-    int *root = c.root, *flags = c.flags;
     const unsigned eps2_bits = __builtin_bit_cast(unsigned, eps2);
-
     return dispatch_T(p.T, [&](auto t) -> int {
         constexpr int T = decltype(t)::value;
-        const dim3 grid((unsigned)p.blocks), block(T);
-        hipLaunchKernelGGL((dbscan_scan_kernel<T, DBSCAN_COUNT>), grid, block, 0, st, points, (const int*)nullptr, (const int*)nullptr, par[0],
-                           hook[0], count, flags, eps2_bits, min_points, N, p.tiles, R, 0);
-        for (int r = 0; r < R; ++r) {
-            hipLaunchKernelGGL((dbscan_scan_kernel<T, DBSCAN_HOOK>), grid, block, 0, st, points, (const int*)par[0], (const int*)par[1],
-                               hook[r & 1], (int*)nullptr, (int*)nullptr, flags, eps2_bits, min_points, N, p.tiles, R, r);
-            hipLaunchKernelGGL(dbscan_compress_kernel, dim3((unsigned)(B * chunks)), dim3(DBSCAN_THREADS), 0, st, (const int*)par[r & 1],
-                               (const int*)hook[r & 1], par[(r + 1) & 1], hook[(r + 1) & 1], (const int*)flags, N, chunks, R, r);
-            const int rc = (int)hipGetLastError();
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL((dbscan_scan_kernel<T, DBSCAN_BORDER>), grid, block, 0, st, points, (const int*)par[0], (const int*)par[1], root,
-                           (int*)nullptr, (int*)nullptr, flags, eps2_bits, min_points, N, p.tiles, R, 0);
-        hipLaunchKernelGGL(dbscan_label_kernel, dim3((unsigned)B), dim3(DBSCAN_LABEL_THREADS), 0, st, (const int*)root, hook[0],
-                           (const int*)flags, labels, n_clusters, rounds, status, N, R);
-        return (int)hipGetLastError();
+        return dbscan_drive(c, labels, n_clusters, count, rounds, status, B, N, R, chunks, st, [&](auto pass, int* out, int* cnt, int round) {
+            constexpr bool first = decltype(pass)::value == DBSCAN_COUNT;   // reads no parents, prepares hook buffer 0
+            hipLaunchKernelGGL((dbscan_scan_kernel<T, decltype(pass)::value>), dim3((unsigned)p.blocks), dim3(T), 0, st, points,
+                               first ? nullptr : (const int*)c.par[0], first ? nullptr : (const int*)c.par[1], out,
+                               first ? c.hook[0] : nullptr, cnt, c.flags, eps2_bits, min_points, N, p.tiles, R, round);
+        });
     });
 }
 
-// The grid form: 2 + 2 R + 2 launches, compress and label the direct form's own.  The index as iss_launch takes it; origin nullable.
-// Returns -2 for arguments out of range (an eps2 above fp32(cell_size^2) among them), -3 when the grid would pass 2^31 - 1 workgroups.
-int dbscan_grid_launch(const float* sorted, const long long* table_keys, const int* table_range, const int* n_in_grid, const float* origin,
-                       float cell_size, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
-                       int min_points, int R, hipStream_t st) {
-    if (!sorted || !table_keys || !table_range || !n_in_grid || !labels || !n_clusters || !status || !ws) return -2;
-    if (B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS || !grid_radius2_ok(eps2, cell_size)) return -2;
-    if (min_points < 1 || R < 0 || R > GECCO_DBSCAN_MAX_ROUNDS) return -2;
-    const CloudPlan p = cloud_plan(B, N, N, 1, false, 256, device_cus());
-    if (!p.fits()) return -3;   // (T <= DBSCAN_THREADS: the init and compress grids are no larger)
+// The grid form: 2 + 2 R + 2 launches, compress and label the direct form's own.  Returns -2 for arguments out of range (an eps2 above
+// fp32(cell_size^2) among them), -3 when the grid would pass 2^31 - 1 workgroups.
+int dbscan_grid_launch(const GridIndexArgs& index, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N,
+                       float eps2, int min_points, int R, hipStream_t st) {
+    const GridView g = grid_view(index, B, N);
+    if (!g.sorted || !labels || !n_clusters || !status || !grid_radius2_ok(eps2, index.cell_size)) return -2;
+    CloudPlan p;
+    if (const int rc = dbscan_plan(B, N, eps2, min_points, R, ws, p)) return rc;
     const int chunks = (N + DBSCAN_THREADS - 1) / DBSCAN_THREADS;
     const DbscanCarve c(ws, B, N);
-    const unsigned cap = (unsigned)GECCO_GRID_CAPACITY(N);
     const unsigned eps2_bits = __builtin_bit_cast(unsigned, eps2);
-    const float inv = 1.0f / cell_size, reach = grid_reach(eps2);
-    const u64* tk = reinterpret_cast<const u64*>(table_keys);
-    const int2* tr = reinterpret_cast<const int2*>(table_range);
-    const f32x4* sp = reinterpret_cast<const f32x4*>(sorted);
-    const dim3 per_chunk((unsigned)(B * chunks)), chunk(DBSCAN_THREADS);
-
+    const float reach = grid_reach(eps2);
     return dispatch_T(p.T, [&](auto t) -> int {
         constexpr int T = decltype(t)::value;
-        const dim3 grid((unsigned)p.blocks), block(T);
-        auto walk = [&](auto pass, int* out, int* cnt, int round) {   // (the count pass reads no parents: it writes buffer 0)
-            constexpr bool reads = decltype(pass)::value != DBSCAN_COUNT;
-            hipLaunchKernelGGL((dbscan_grid_kernel<T, decltype(pass)::value>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, reach,
-                               eps2_bits, reads ? (const int*)c.par[0] : nullptr, reads ? (const int*)c.par[1] : nullptr, out, cnt, c.flags,
-                               min_points, N, cap, p.tiles, R, round);
-        };
-        hipLaunchKernelGGL(dbscan_grid_init_kernel, per_chunk, chunk, 0, st, c.par[0], c.hook[0], c.root, count, c.flags, N, chunks, R);
-        walk(std::integral_constant<int, DBSCAN_COUNT>{}, c.par[0], count, 0);
-        for (int r = 0; r < R; ++r) {
-            walk(std::integral_constant<int, DBSCAN_HOOK>{}, c.hook[r & 1], nullptr, r);
-            hipLaunchKernelGGL(dbscan_compress_kernel, per_chunk, chunk, 0, st, (const int*)c.par[r & 1], (const int*)c.hook[r & 1],
-                               c.par[(r + 1) & 1], c.hook[(r + 1) & 1], (const int*)c.flags, N, chunks, R, r);
-            const int rc = (int)hipGetLastError();
-            if (rc) return rc;
-        }
-        walk(std::integral_constant<int, DBSCAN_BORDER>{}, c.root, nullptr, 0);
-        hipLaunchKernelGGL(dbscan_label_kernel, dim3((unsigned)B), dim3(DBSCAN_LABEL_THREADS), 0, st, (const int*)c.root, c.hook[0],
-                           (const int*)c.flags, labels, n_clusters, rounds, status, N, R);
-        return (int)hipGetLastError();
+        return dbscan_drive(c, labels, n_clusters, count, rounds, status, B, N, R, chunks, st, [&](auto pass, int* out, int* cnt, int round) {
+            constexpr bool first = decltype(pass)::value == DBSCAN_COUNT;   // reads no parents, follows the init launch
+            if (first)
+                hipLaunchKernelGGL(dbscan_grid_init_kernel, dim3((unsigned)(B * chunks)), dim3(DBSCAN_THREADS), 0, st, c.par[0], c.hook[0],
+                                   c.root, count, c.flags, N, chunks, R);
+            hipLaunchKernelGGL((dbscan_grid_kernel<T, decltype(pass)::value>), dim3((unsigned)p.blocks), dim3(T), 0, st, g, reach, eps2_bits,
+                               first ? nullptr : (const int*)c.par[0], first ? nullptr : (const int*)c.par[1], out, cnt, c.flags, min_points,
+                               p.tiles, R, round);
+        });
     });
 }

@@ -27,8 +27,9 @@
 // the lanes of a wave probe the same cells and read the same runs, which the L2 then serves once.
 //
 // The walk itself (the reach, the box, the probe, the runs, the tail, the scan of the whole cloud for a box wider than GRID_BOX cells) is
-// grid_walk of grid_walk.h, which iss.hip's kernels call as well; that header proves that the walk misses no neighbour and bounds
-// every loop.
+// grid_walk of grid_walk.h, which iss.hip's and dbscan.hip's kernels call as well; that header proves that the walk misses no neighbour
+// and bounds every loop.  The built index reaches a launcher as one GridIndexArgs (kernels.h), of which grid_walk.h's grid_view makes
+// the GridView the walk reads (the tests, the casts, inv and cap); grid_query_kernel is handed that view's members (its own comment).
 //
 // The radius may not exceed the cell edge; an index serves every smaller radius (at r = cell_size / 2 the 27 to 64 cells hold 8 times
 // the candidates that cells of edge r would: build another index when that matters).  The fixed-width forms stay on radius.hip.
@@ -101,7 +102,9 @@ __global__ __launch_bounds__(GRID_THREADS) void grid_build_kernel(const float* _
 }
 
 // grid: B * tiles blocks of T queries.  COUNT: count.  FILL_CSR: row_start, idx, d2 (nullable).  The walk is grid_walk (grid_walk.h); what
-// is this kernel's own is the visitor: self exclusion by the index in .w, the stores, the counter
+// is this kernel's own is the visitor: self exclusion by the index in .w, the stores, the counter.  The index comes in as the view's
+// members, each pointer __restrict__, and the view is put together here: with the view as one parameter the CSR fill at 16 x 2048 measured
+// 2.5 % slower than the parent, and a struct member cannot carry the noalias a parameter does
 template <int T, int MODE>
 __global__ __launch_bounds__(T) void grid_query_kernel(const float* __restrict__ query, const int* __restrict__ qorder,
                                                        const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,
@@ -110,6 +113,7 @@ __global__ __launch_bounds__(T) void grid_query_kernel(const float* __restrict__
                                                        const long long* __restrict__ row_start, int* __restrict__ idx, float* __restrict__ d2,
                                                        int* __restrict__ count, unsigned r2_bits, int M, int N, unsigned cap, int exclude_self,
                                                        int tiles) {
+    const GridView index{sorted, table_keys, table_range, n_in_grid, origin, inv, N, cap};
     const int b = (int)(blockIdx.x / (unsigned)tiles);
     const int t = (int)(blockIdx.x % (unsigned)tiles) * T + (int)threadIdx.x;
     if (t >= M) return;   // (no barrier below)
@@ -121,17 +125,16 @@ __global__ __launch_bounds__(T) void grid_query_kernel(const float* __restrict__
     const size_t o = MODE == GRID_FILL_CSR ? (size_t)row_start[row] : 0;
     int n = 0;   // neighbours so far (n <= N)
     if (cloud_finite3(qx, qy, qz))   // (a non-finite query has dist2 = +inf to everything)
-        grid_walk(qx, qy, qz, sorted + (size_t)b * N, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv,
-                  R, r2_bits, N, cap, [&](const f32x4 p, unsigned u) {
-                      const unsigned j = __float_as_uint(p[3]);
-                      if (j != self) {
-                          if (MODE == GRID_FILL_CSR) {
-                              idx[o + (size_t)n] = (int)j;
-                              if (d2) d2[o + (size_t)n] = __uint_as_float(u);
-                          }
-                          ++n;
-                      }
-                  });
+        grid_walk(index, b, qx, qy, qz, R, r2_bits, [&](const f32x4 p, unsigned u) {
+            const unsigned j = __float_as_uint(p[3]);
+            if (j != self) {
+                if (MODE == GRID_FILL_CSR) {
+                    idx[o + (size_t)n] = (int)j;
+                    if (d2) d2[o + (size_t)n] = __uint_as_float(u);
+                }
+                ++n;
+            }
+        });
     if (MODE == GRID_COUNT) count[row] = n;
 }
 
@@ -167,29 +170,25 @@ int grid_build_launch(const float* points, const long long* keys, const int* per
 
 // One launch.  idx null: COUNT (count required, row_start and d2 null).  Otherwise FILL_CSR (row_start required, d2 nullable, count not
 // written).  -2: arguments out of range (radius2 above fp32(cell_size^2) among them), -3: the grid would pass 2^31 - 1 workgroups
-int grid_radius_launch(const float* query, const int* qorder, const float* sorted, const long long* table_keys, const int* table_range,
-                       const int* n_in_grid, const float* origin, float cell_size, const long long* row_start, int* idx, float* d2, int* count,
-                       int B, int M, int N, float r2, int exclude_self, hipStream_t st) {
-    if (!query || !sorted || !table_keys || !table_range || !n_in_grid || B < 1 || M < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return -2;
-    if (!grid_radius2_ok(r2, cell_size) || (exclude_self && M != N)) return -2;
+int grid_radius_launch(const float* query, const int* qorder, const GridIndexArgs& index, const long long* row_start, int* idx, float* d2,
+                       int* count, int B, int M, int N, float r2, int exclude_self, hipStream_t st) {
+    const GridView g = grid_view(index, B, N);
+    if (!g.sorted || !query || M < 1 || !grid_radius2_ok(r2, index.cell_size) || (exclude_self && M != N)) return -2;
     if (idx ? !row_start : !count || row_start || d2) return -2;
     const CloudPlan p = cloud_plan(B, M, N, 1, false, 256, device_cus());
     if (!p.fits()) return -3;
-    const unsigned r2_bits = __builtin_bit_cast(unsigned, r2), cap = (unsigned)GECCO_GRID_CAPACITY(N);
-    const float inv = 1.0f / cell_size, R = grid_reach(r2);
+    const unsigned r2_bits = __builtin_bit_cast(unsigned, r2);
+    const float R = grid_reach(r2);
     const int self = exclude_self ? 1 : 0;
-    const u64* tk = reinterpret_cast<const u64*>(table_keys);
-    const int2* tr = reinterpret_cast<const int2*>(table_range);
-    const f32x4* sp = reinterpret_cast<const f32x4*>(sorted);
     return dispatch_T(p.T, [&](auto t) -> int {
         constexpr int T = decltype(t)::value;
         const dim3 grid((unsigned)p.blocks), block(T);
         if (!idx)
-            hipLaunchKernelGGL((grid_query_kernel<T, GRID_COUNT>), grid, block, 0, st, query, qorder, sp, tk, tr, n_in_grid, origin, inv, R,
-                               row_start, idx, d2, count, r2_bits, M, N, cap, self, p.tiles);
+            hipLaunchKernelGGL((grid_query_kernel<T, GRID_COUNT>), grid, block, 0, st, query, qorder, g.sorted, g.table_keys, g.table_range,
+                               g.n_in_grid, g.origin, g.inv, R, row_start, idx, d2, count, r2_bits, M, N, g.cap, self, p.tiles);
         else
-            hipLaunchKernelGGL((grid_query_kernel<T, GRID_FILL_CSR>), grid, block, 0, st, query, qorder, sp, tk, tr, n_in_grid, origin, inv, R,
-                               row_start, idx, d2, count, r2_bits, M, N, cap, self, p.tiles);
+            hipLaunchKernelGGL((grid_query_kernel<T, GRID_FILL_CSR>), grid, block, 0, st, query, qorder, g.sorted, g.table_keys, g.table_range,
+                               g.n_in_grid, g.origin, g.inv, R, row_start, idx, d2, count, r2_bits, M, N, g.cap, self, p.tiles);
         return (int)hipGetLastError();
     });
 }

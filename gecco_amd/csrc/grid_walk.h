@@ -1,7 +1,13 @@
-// The cell walk of the grid index, as every kernel that reads the index shares it (grid.hip's grid_query_kernel, iss.hip's two kernels):
-// the reach of a ball, the clamped box of cells it can touch, the table probe, the runs, the off-grid tail and the scan of the whole
-// cloud for a box too wide to walk.  The proofs that the walk misses no neighbour and that every loop is bounded stand here, once,
-// beside the one spelling of the code they are about.  Device code is static __device__ __forceinline__, host helpers are inline.
+// The cell walk of the grid index, as every kernel that reads the index shares it (grid.hip's grid_query_kernel, iss.hip's two kernels,
+// dbscan.hip's dbscan_grid_kernel): the reach of a ball, the clamped box of cells it can touch, the table probe, the runs, the off-grid
+// tail and the scan of the whole cloud for a box too wide to walk.  The proofs that the walk misses no neighbour and that every loop is
+// bounded stand here, once, beside the one spelling of the code they are about.  Device code is static __device__ __forceinline__, host
+// helpers are inline.
+//
+// How the index travels.  A launcher is handed the six values of the C ABI as one GridIndexArgs (kernels.h) and makes one GridView of
+// them (grid_view, below: the null and range tests, the casts, inv and cap, written once); a kernel takes the view by value
+// (grid_query_kernel its members, for the reason given there), reads its own cloud's sorted points through view.cloud(b) and hands the
+// view and b to grid_walk, which forms the cloud's tables itself.
 //
 // The walk (grid.hip's header defines the index: cells, keys, the sorted order, the table, n_in_grid).  For a finite point q, with R the
 // host's fp32 reach (grid_reach), per axis the cells lo = cell(fp32(q - R)) .. hi = cell(fp32(q + R)), voxel_cell's u and floor, clamped
@@ -32,6 +38,7 @@
 #include <cmath>
 
 #include "cloud_nn.h"
+#include "kernels.h"
 #include "voxel_cell.h"
 
 constexpr int GRID_BOX = 4;   // cells per axis a walk visits; a wider box is answered by a scan of the whole cloud
@@ -55,13 +62,39 @@ inline float grid_reach(float r2) {
 // a radius2 an index of this cell_size serves: a finite number > 0 (false for NaN) and not above fp32(cell_size^2)
 inline bool grid_radius2_ok(float r2, float cell_size) { return r2 > 0.f && r2 <= 3.402823466e38f && r2 <= cell_size * cell_size; }
 
+// The index of B clouds of N points as a kernel reads it, passed by value
+struct GridView {
+    const f32x4* sorted;       // (B, N): (x, y, z, the bits of perm) per sorted position
+    const u64* table_keys;     // (B, cap)
+    const int2* table_range;   // (B, cap): the run [start, end) of the slot's key
+    const int* n_in_grid;      // (B,): where the tail starts
+    const float* origin;       // (B, 3), or null: 0
+    float inv;                 // fp32(1 / cell_size), once, on the host
+    int N;
+    unsigned cap;              // GECCO_GRID_CAPACITY(N)
+    __device__ __forceinline__ const f32x4* cloud(int b) const { return sorted + (size_t)b * N; }
+};
+
+// The view of the index `g` over B clouds of N points; sorted == nullptr (a launcher's -2) when a required pointer is null or B, N are
+// out of range
+inline GridView grid_view(const GridIndexArgs& g, int B, int N) {
+    if (!g.sorted || !g.table_keys || !g.table_range || !g.n_in_grid || B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return GridView{};
+    return GridView{reinterpret_cast<const f32x4*>(g.sorted), reinterpret_cast<const u64*>(g.table_keys),
+                    reinterpret_cast<const int2*>(g.table_range), g.n_in_grid, g.origin, 1.0f / g.cell_size, N,
+                    (unsigned)GECCO_GRID_CAPACITY(N)};
+}
+
 // The walk for the finite point (qx, qy, qz) of cloud b: visit(p, u) for every sorted entry p with u = cloud_dist2_bits(q, p) <=
-// r2_bits, in ascending sorted position, each entry once.  sb, tk, tr: the cloud's own sorted points and table; tail: its n_in_grid
+// r2_bits, in ascending sorted position, each entry once
 template <class Visit>
-static __device__ __forceinline__ void grid_walk(float qx, float qy, float qz, const f32x4* __restrict__ sb, const u64* __restrict__ tk,
-                                                 const int2* __restrict__ tr, int tail, const float* __restrict__ origin, int b, float inv,
-                                                 float R, unsigned r2_bits, int N, unsigned cap, Visit visit) {
+static __device__ __forceinline__ void grid_walk(const GridView& g, int b, float qx, float qy, float qz, float R, unsigned r2_bits,
+                                                 Visit visit) {
 #pragma clang fp contract(off)
+    const f32x4* sb = g.cloud(b);   // the cloud's own sorted points, table and tail
+    const u64* tk = g.table_keys + (size_t)b * g.cap;
+    const int2* tr = g.table_range + (size_t)b * g.cap;
+    const int N = g.N, tail = g.n_in_grid[b];
+    const unsigned cap = g.cap;
     auto scan = [&](int from, int to) {
         for (int s = from; s < to; ++s) {
             const f32x4 p = sb[s];   // one 16-byte load
@@ -74,9 +107,9 @@ static __device__ __forceinline__ void grid_walk(float qx, float qy, float qz, c
     bool wide = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float org = origin ? origin[3 * b + a] : 0.f;
+        const float org = g.origin ? g.origin[3 * b + a] : 0.f;
         const float below = q[a] - R, above = q[a] + R;   // rounded to fp32 before the cell arithmetic
-        const float fl = grid_u(below, org, inv), fh = grid_u(above, org, inv);
+        const float fl = grid_u(below, org, g.inv), fh = grid_u(above, org, g.inv);
         // clamped to the grid: a bound beyond it on the far side leaves an empty box, a NaN (a non-finite origin) the widest one
         lo[a] = fl >= -VOXEL_HALF ? (fl < VOXEL_HALF ? (int)fl : GRID_HALF) : -GRID_HALF;
         hi[a] = fh < VOXEL_HALF ? (fh >= -VOXEL_HALF ? (int)fh : -GRID_HALF - 1) : GRID_HALF - 1;

@@ -37,7 +37,8 @@
 // words only: no atomics, no LDS, no workspace, no thread waits on another, every loop is bounded by a constant, by cap or by N.
 //
 // The walk (the reach, the clamped cells, the table probe, the runs, the tail, the scan of all N positions for a wide box) is grid_walk of
-// grid_walk.h, the one grid_query_kernel calls, where it is proved to miss no neighbour and every loop is bounded.
+// grid_walk.h, the one grid_query_kernel calls, where it is proved to miss no neighbour and every loop is bounded.  The index comes in as
+// one GridIndexArgs (kernels.h); both kernels take the GridView that grid_walk.h's grid_view makes of it, by value.
 #include <cmath>
 
 #include "cloud_nn.h"
@@ -77,18 +78,15 @@ static __device__ __forceinline__ void iss_rotate(double& app, double& aqq, doub
 
 // grid: B * tiles blocks of T sorted positions.  eigenvalues, counts nullable
 template <int T>
-__global__ __launch_bounds__(T) void iss_saliency_kernel(const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,
-                                                         const int2* __restrict__ table_range, const int* __restrict__ n_in_grid,
-                                                         const float* __restrict__ origin, float inv, float R, unsigned r2_bits,
-                                                         double gamma_21, double gamma_32, int min_neighbors,
-                                                         double* __restrict__ saliency, double* __restrict__ eigenvalues,
-                                                         int* __restrict__ counts, int N, unsigned cap, int tiles) {
+__global__ __launch_bounds__(T) void iss_saliency_kernel(const GridView index, float R, unsigned r2_bits, double gamma_21, double gamma_32,
+                                                         int min_neighbors, double* __restrict__ saliency, double* __restrict__ eigenvalues,
+                                                         int* __restrict__ counts, int tiles) {
 #pragma clang fp contract(off)
+    const int N = index.N;
     const int b = (int)(blockIdx.x / (unsigned)tiles);
     const int t = (int)(blockIdx.x % (unsigned)tiles) * T + (int)threadIdx.x;
     if (t >= N) return;   // (no barrier below)
-    const f32x4* sb = sorted + (size_t)b * N;
-    const f32x4 own = sb[t];
+    const f32x4 own = index.cloud(b)[t];
     const unsigned i = __float_as_uint(own[3]);
     if (i >= (unsigned)N) return;   // a sorted array no build wrote: nothing outside the outputs is written
     const float qx = own[0], qy = own[1], qz = own[2];
@@ -96,14 +94,13 @@ __global__ __launch_bounds__(T) void iss_saliency_kernel(const f32x4* __restrict
     int m = 0;
     double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
     if (cloud_finite3(qx, qy, qz))   // (a non-finite point has dist2 = +inf to everything)
-        grid_walk(qx, qy, qz, sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, R, r2_bits, N, cap,
-                  [&](const f32x4 p, unsigned) {
-                      const double dx = (double)p[0] - cx, dy = (double)p[1] - cy, dz = (double)p[2] - cz;
-                      ++m;
-                      sx += dx, sy += dy, sz += dz;
-                      sxx += dx * dx, sxy += dx * dy, sxz += dx * dz;
-                      syy += dy * dy, syz += dy * dz, szz += dz * dz;
-                  });
+        grid_walk(index, b, qx, qy, qz, R, r2_bits, [&](const f32x4 p, unsigned) {
+            const double dx = (double)p[0] - cx, dy = (double)p[1] - cy, dz = (double)p[2] - cz;
+            ++m;
+            sx += dx, sy += dy, sz += dz;
+            sxx += dx * dx, sxy += dx * dy, sxz += dx * dz;
+            syy += dy * dy, syz += dy * dz, szz += dz * dz;
+        });
     double l0 = 0.0, l1 = 0.0, l2 = 0.0, sal = 0.0;
     if (m >= min_neighbors) {
         const double im = 1.0 / (double)m;
@@ -137,16 +134,13 @@ __global__ __launch_bounds__(T) void iss_saliency_kernel(const f32x4* __restrict
 
 // grid: B * tiles blocks of T sorted positions
 template <int T>
-__global__ __launch_bounds__(T) void iss_select_kernel(const f32x4* __restrict__ sorted, const u64* __restrict__ table_keys,
-                                                       const int2* __restrict__ table_range, const int* __restrict__ n_in_grid,
-                                                       const float* __restrict__ origin, float inv, float R, unsigned r2_bits,
-                                                       int min_neighbors, const double* __restrict__ saliency,
-                                                       unsigned char* __restrict__ mask, int N, unsigned cap, int tiles) {
+__global__ __launch_bounds__(T) void iss_select_kernel(const GridView index, float R, unsigned r2_bits, int min_neighbors,
+                                                       const double* __restrict__ saliency, unsigned char* __restrict__ mask, int tiles) {
+    const int N = index.N;
     const int b = (int)(blockIdx.x / (unsigned)tiles);
     const int t = (int)(blockIdx.x % (unsigned)tiles) * T + (int)threadIdx.x;
     if (t >= N) return;   // (no barrier below)
-    const f32x4* sb = sorted + (size_t)b * N;
-    const f32x4 own = sb[t];
+    const f32x4 own = index.cloud(b)[t];
     const unsigned i = __float_as_uint(own[3]);
     if (i >= (unsigned)N) return;
     const double* sal = saliency + (size_t)b * N;
@@ -155,12 +149,11 @@ __global__ __launch_bounds__(T) void iss_select_kernel(const f32x4* __restrict__
     if (mine > 0.0) {   // a candidate: its point is finite
         int n = 0;
         bool beaten = false;
-        grid_walk(own[0], own[1], own[2], sb, table_keys + (size_t)b * cap, table_range + (size_t)b * cap, n_in_grid[b], origin, b, inv, R,
-                  r2_bits, N, cap, [&](const f32x4 p, unsigned) {
-                      const unsigned j = __float_as_uint(p[3]);
-                      ++n;
-                      beaten = beaten || (j < (unsigned)N && sal[j] > mine);
-                  });
+        grid_walk(index, b, own[0], own[1], own[2], R, r2_bits, [&](const f32x4 p, unsigned) {
+            const unsigned j = __float_as_uint(p[3]);
+            ++n;
+            beaten = beaten || (j < (unsigned)N && sal[j] > mine);
+        });
         keep = n >= min_neighbors && !beaten;
     }
     mask[(size_t)b * N + i] = keep ? 1 : 0;
@@ -170,26 +163,21 @@ __global__ __launch_bounds__(T) void iss_select_kernel(const f32x4* __restrict__
 
 // Two launches: the saliency of every point, then the selection.  eigenvalues, counts nullable.  -2: arguments out of range (a radius2
 // above fp32(cell_size^2) among them), -3: the grid would pass 2^31 - 1 workgroups
-int iss_launch(const float* sorted, const long long* table_keys, const int* table_range, const int* n_in_grid, const float* origin,
-               float cell_size, double* saliency, double* eigenvalues, int* counts, unsigned char* mask, int B, int N, float r2s, float r2n,
-               double gamma_21, double gamma_32, int min_neighbors, hipStream_t st) {
-    if (!sorted || !table_keys || !table_range || !n_in_grid || !saliency || !mask || B < 1 || N < 1 || N > GECCO_VOXEL_MAX_POINTS) return -2;
-    if (!grid_radius2_ok(r2s, cell_size) || !grid_radius2_ok(r2n, cell_size) || min_neighbors < 1) return -2;
+int iss_launch(const GridIndexArgs& index, double* saliency, double* eigenvalues, int* counts, unsigned char* mask, int B, int N, float r2s,
+               float r2n, double gamma_21, double gamma_32, int min_neighbors, hipStream_t st) {
+    const GridView g = grid_view(index, B, N);
+    if (!g.sorted || !saliency || !mask) return -2;
+    if (!grid_radius2_ok(r2s, index.cell_size) || !grid_radius2_ok(r2n, index.cell_size) || min_neighbors < 1) return -2;
     if (!(gamma_21 > 0.0) || !(gamma_21 <= 1.7976931348623157e308) || !(gamma_32 > 0.0) || !(gamma_32 <= 1.7976931348623157e308)) return -2;
     const CloudPlan p = cloud_plan(B, N, N, 1, false, 256, device_cus());
     if (!p.fits()) return -3;
-    const unsigned cap = (unsigned)GECCO_GRID_CAPACITY(N);
-    const float inv = 1.0f / cell_size;
-    const u64* tk = reinterpret_cast<const u64*>(table_keys);
-    const int2* tr = reinterpret_cast<const int2*>(table_range);
-    const f32x4* sp = reinterpret_cast<const f32x4*>(sorted);
     return dispatch_T(p.T, [&](auto t) -> int {
         constexpr int T = decltype(t)::value;
         const dim3 grid((unsigned)p.blocks), block(T);
-        hipLaunchKernelGGL((iss_saliency_kernel<T>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, grid_reach(r2s),
-                           __builtin_bit_cast(unsigned, r2s), gamma_21, gamma_32, min_neighbors, saliency, eigenvalues, counts, N, cap, p.tiles);
-        hipLaunchKernelGGL((iss_select_kernel<T>), grid, block, 0, st, sp, tk, tr, n_in_grid, origin, inv, grid_reach(r2n),
-                           __builtin_bit_cast(unsigned, r2n), min_neighbors, saliency, mask, N, cap, p.tiles);
+        hipLaunchKernelGGL((iss_saliency_kernel<T>), grid, block, 0, st, g, grid_reach(r2s), __builtin_bit_cast(unsigned, r2s), gamma_21,
+                           gamma_32, min_neighbors, saliency, eigenvalues, counts, p.tiles);
+        hipLaunchKernelGGL((iss_select_kernel<T>), grid, block, 0, st, g, grid_reach(r2n), __builtin_bit_cast(unsigned, r2n), min_neighbors,
+                           saliency, mask, p.tiles);
         return (int)hipGetLastError();
     });
 }

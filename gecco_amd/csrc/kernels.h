@@ -540,16 +540,25 @@ int plane_ransac_launch(const float* points, const unsigned char* mask, float r,
 // GECCO_VOXEL_WORKSPACE_BYTES(B, N); V = max_voxels rows per cloud.  -2: sizes out of range, -3: a grid would pass 2^31 - 1 workgroups
 int voxel_launch(const float* points, const float* origin, float voxel_size, float* centroids, int* first, int* count, int* inverse,
                  int* n_voxels, void* ws, int B, int N, int V, hipStream_t st);
+// The built grid index of grid.hip (definition: gecco_grid_build_f32), B clouds of N points, as every launcher that reads it takes it: the
+// six values of the C ABI in its order (grid_walk.h's grid_view makes of them what the kernels read)
+struct GridIndexArgs {
+    const float* sorted;           // (B, N, 4)
+    const long long* table_keys;   // (B, cap), cap = GECCO_GRID_CAPACITY(N)
+    const int* table_range;        // (B, cap, 2)
+    const int* n_in_grid;          // (B,)
+    const float* origin;           // (B, 3), or null: 0
+    float cell_size;
+};
 // dbscan.hip — DBSCAN clustering (definition: gecco_dbscan_f32).  eps2 = fp32(eps * eps); count, rounds nullable; ws of
 // GECCO_DBSCAN_WORKSPACE_BYTES(B, N, R); 1 + 2 R + 2 launches for R = max_rounds.  -2: arguments out of range, -3: the grid would pass
-// 2^31 - 1 workgroups.  The grid form (definition: gecco_dbscan_grid_f32) finds its neighbours on the index of grid.hip, taken as
-// iss_launch takes it (origin nullable): the same outputs and workspace, 2 + 2 R + 2 launches; -2 also for null pointers, N above
-// GECCO_VOXEL_MAX_POINTS and an eps2 above fp32(cell_size^2)
+// 2^31 - 1 workgroups.  The grid form (definition: gecco_dbscan_grid_f32) finds its neighbours on the index of grid.hip, a GridIndexArgs
+// (above): the same outputs and workspace, 2 + 2 R + 2 launches; -2 also for null pointers, N above GECCO_VOXEL_MAX_POINTS and an eps2
+// above fp32(cell_size^2)
 int dbscan_launch(const float* points, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
                   int min_points, int R, hipStream_t st);
-int dbscan_grid_launch(const float* sorted, const long long* table_keys, const int* table_range, const int* n_in_grid, const float* origin,
-                       float cell_size, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N, float eps2,
-                       int min_points, int R, hipStream_t st);
+int dbscan_grid_launch(const GridIndexArgs& index, int* labels, int* n_clusters, int* count, int* rounds, int* status, void* ws, int B, int N,
+                       float eps2, int min_points, int R, hipStream_t st);
 // radius.hip — fixed-radius neighbour search (definition: gecco_radius_search_f32): one launch.  r2 = fp32(r * r).  idx null: the counts
 // alone (count required).  row_start (the int64 exclusive prefix sum of the counts) given: the CSR fill, K = 0, d2 nullable.  Otherwise
 // the fixed-width fill, K >= 1 slots per row, d2 and count nullable.  -2: arguments out of range, -3: the grid would pass 2^31 - 1
@@ -557,22 +566,20 @@ int dbscan_grid_launch(const float* sorted, const long long* table_keys, const i
 int radius_launch(const float* query, const float* ref, const long long* row_start, int* idx, float* d2, int* count, int B, int M, int N,
                   float r2, int exclude_self, int K, hipStream_t st);
 // grid.hip — the uniform-grid index of the fixed-radius search (definition: gecco_grid_build_f32).  keys: one launch, origin nullable.
-// build: the table fill and one launch over the sorted positions.  radius: one launch over the index; qorder, origin, d2 nullable; idx
-// null: the counts alone (count required), otherwise the CSR fill (row_start required).  -2: arguments out of range (a radius2 above
+// build: the table fill and one launch over the sorted positions.  radius: one launch over the index; qorder, d2 nullable; idx null: the
+// counts alone (count required), otherwise the CSR fill (row_start required).  -2: arguments out of range (a radius2 above
 // fp32(cell_size^2) among them), -3: the grid would pass 2^31 - 1 workgroups
 int grid_keys_launch(const float* points, const float* origin, float cell_size, long long* keys, int B, int N, hipStream_t st);
 int grid_build_launch(const float* points, const long long* keys, const int* perm, float* sorted, long long* table_keys, int* table_range,
                       int* n_in_grid, int B, int N, hipStream_t st);
-int grid_radius_launch(const float* query, const int* qorder, const float* sorted, const long long* table_keys, const int* table_range,
-                       const int* n_in_grid, const float* origin, float cell_size, const long long* row_start, int* idx, float* d2, int* count,
-                       int B, int M, int N, float r2, int exclude_self, hipStream_t st);
+int grid_radius_launch(const float* query, const int* qorder, const GridIndexArgs& index, const long long* row_start, int* idx, float* d2,
+                       int* count, int B, int M, int N, float r2, int exclude_self, hipStream_t st);
 // iss.hip — ISS keypoints on the grid index (definition: gecco_iss_keypoints_f32): two launches over the sorted positions, the
-// saliency of every point and the selection.  r2s, r2n = fp32(radius^2) of the salient and the non-maximum radius; origin,
-// eigenvalues, counts nullable.  -2: arguments out of range (a radius2 above fp32(cell_size^2) among them), -3: the grid would pass
-// 2^31 - 1 workgroups
-int iss_launch(const float* sorted, const long long* table_keys, const int* table_range, const int* n_in_grid, const float* origin,
-               float cell_size, double* saliency, double* eigenvalues, int* counts, unsigned char* mask, int B, int N, float r2s, float r2n,
-               double gamma_21, double gamma_32, int min_neighbors, hipStream_t st);
+// saliency of every point and the selection.  r2s, r2n = fp32(radius^2) of the salient and the non-maximum radius; eigenvalues,
+// counts nullable.  -2: arguments out of range (a radius2 above fp32(cell_size^2) among them), -3: the grid would pass 2^31 - 1
+// workgroups
+int iss_launch(const GridIndexArgs& index, double* saliency, double* eigenvalues, int* counts, unsigned char* mask, int B, int N, float r2s,
+               float r2n, double gamma_21, double gamma_32, int min_neighbors, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

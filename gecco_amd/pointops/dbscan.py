@@ -37,7 +37,6 @@ Nothing takes the grid by default: the caller asks for it by calling this functi
 17 % faster and 28 % slower than the direct form; its docstring and DESIGN.md)."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple
 
 import torch
@@ -45,9 +44,8 @@ from torch import Tensor
 
 from .. import _lib
 from ..hip_ops import _stream
-from ._args import (VOXEL_MAX_POINTS, _cloud, _f32, _integer, _integer_tensor, _need_device, _not_empty, _radius_f32, _same_batching,
-                    _unbatch, _vp)
-from .radius import GridIndex, _grid_build, _grid_cell_size
+from ._args import VOXEL_MAX_POINTS, _cloud, _f32, _integer, _integer_tensor, _not_empty, _radius_f32, _unbatch, _vp
+from .radius import GridIndex, _grid_for
 
 DBSCAN_MAX_ROUNDS = 64            # GECCO_DBSCAN_MAX_ROUNDS
 
@@ -148,24 +146,9 @@ def cluster_dbscan_grid(points: Tensor, eps: float, min_points: int = 10, max_ro
         raise ValueError(f"N = {N} above {VOXEL_MAX_POINTS}")
     e, eps2 = _radius_f32(eps, "eps")
     min_points, R = _dbscan_limits(min_points, max_rounds, N)
-    if index is None:
-        size = _grid_cell_size(e)
-    elif isinstance(index, GridIndex):
-        _same_batching(p, single, index.points, index.single, "points", "index")
-        if index.points.shape[1] != N:
-            raise ValueError(f"points has {N} points a cloud, the index was built over {index.points.shape[1]}")
-        size = index.cell_size
-    else:
-        raise ValueError("index must be None or a GridIndex")
-    if not eps2 <= C.c_float(size * size).value:   # the library's fp32 product
-        raise ValueError(f"eps: its square {eps2} is above the square of the index's cell_size = {size}: build an index with a larger cell")
-    if index is None:
-        x, px = _f32(p)
-        index = _grid_build(x, px, size, None, single)
-    else:
-        _need_device(p, index.sorted_points)
-    inputs = (_vp(index.sorted_points), _vp(index.table_keys), _vp(index.table_range), _vp(index.n_in_grid), _vp(index.origin), index.cell_size)
-    return _dbscan_call("gecco_dbscan_grid_f32", inputs, index.sorted_points.device, B, N, eps2, min_points, R, return_counts, single)
+    index = _grid_for(p, single, index, e, eps=eps2)
+    return _dbscan_call("gecco_dbscan_grid_f32", index._arguments(), index.sorted_points.device, B, N, eps2, min_points, R, return_counts,
+                        single)
 
 
 def cluster_sizes(labels: Tensor, n_clusters) -> Tensor:

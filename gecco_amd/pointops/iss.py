@@ -38,7 +38,6 @@ Two launches, one thread per sorted position: the saliency of every point, then 
 atomics, no workspace.  `cloud_resolution` is Open3D's ComputeModelResolution, the mean distance to the nearest other point."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import NamedTuple
 
@@ -47,8 +46,8 @@ from torch import Tensor
 
 from .. import _lib
 from ..hip_ops import _stream
-from ._args import VOXEL_MAX_POINTS, _cloud, _f32, _integer, _need_device, _not_empty, _number, _radius_f32, _same_batching, _unbatch, _vp
-from .radius import GridIndex, _grid_build, _grid_cell_size
+from ._args import VOXEL_MAX_POINTS, _cloud, _integer, _not_empty, _number, _radius_f32, _unbatch, _vp
+from .radius import GridIndex, _grid_for
 
 
 class ISSResult(NamedTuple):
@@ -97,30 +96,12 @@ def iss_keypoints(points: Tensor, salient_radius: float, non_max_radius: float, 
     min_neighbors = _integer(min_neighbors, "min_neighbors")
     if not 1 <= min_neighbors <= 0x7fffffff:
         raise ValueError(f"min_neighbors = {min_neighbors} must be in 1 .. 2^31 - 1")
-    if index is None:
-        size = _grid_cell_size(max(rs, rn))
-    elif isinstance(index, GridIndex):
-        _same_batching(p, single, index.points, index.single, "points", "index")
-        if index.points.shape[1] != N:
-            raise ValueError(f"points has {N} points a cloud, the index was built over {index.points.shape[1]}")
-        size = index.cell_size
-    else:
-        raise ValueError("index must be None or a GridIndex")
-    cell2 = C.c_float(size * size).value   # the library's fp32 product
-    for name, r2 in (("salient_radius", r2s), ("non_max_radius", r2n)):
-        if not r2 <= cell2:
-            raise ValueError(f"{name}: its square {r2} is above the square of the index's cell_size = {size}: build an index with a larger cell")
-    if index is None:
-        x, px = _f32(p)
-        index = _grid_build(x, px, size, None, single)
-    else:
-        _need_device(p, index.sorted_points)
+    index = _grid_for(p, single, index, max(rs, rn), salient_radius=r2s, non_max_radius=r2n)
     dev = index.sorted_points.device
     saliency = torch.empty(B, N, device=dev, dtype=torch.float64)
     eig = torch.empty(B, N, 3, device=dev, dtype=torch.float64)
     cnt = torch.empty(B, N, device=dev, dtype=torch.int32)
     mask = torch.empty(B, N, device=dev, dtype=torch.bool)
-    _lib.check(_lib.load().gecco_iss_keypoints_f32(_vp(index.sorted_points), _vp(index.table_keys), _vp(index.table_range), _vp(index.n_in_grid),
-                                                   _vp(index.origin), index.cell_size, _vp(saliency), _vp(eig), _vp(cnt), _vp(mask), B, N, r2s,
-                                                   r2n, g21, g32, min_neighbors, _stream()), "gecco_iss_keypoints_f32")
+    _lib.check(_lib.load().gecco_iss_keypoints_f32(*index._arguments(), _vp(saliency), _vp(eig), _vp(cnt), _vp(mask), B, N, r2s, r2n, g21, g32,
+                                                   min_neighbors, _stream()), "gecco_iss_keypoints_f32")
     return ISSResult(*_unbatch([mask, saliency, eig, cnt.long(), mask.sum(1)], single))

@@ -61,8 +61,8 @@ from torch import Tensor
 
 from .. import _lib
 from ..hip_ops import _ptr, _stream
-from ._args import (KNN_MAX_K, VOXEL_MAX_POINTS, _cloud, _f32, _integer, _not_empty, _on_device, _pair_f32, _pair_sizes, _per_cloud,
-                    _positive_f32, _cloud_pair, _radius_f32, _same_batching, _sqrt, _unbatch, _vp)
+from ._args import (KNN_MAX_K, VOXEL_MAX_POINTS, _cloud, _f32, _integer, _need_device, _not_empty, _on_device, _pair_f32, _pair_sizes,
+                    _per_cloud, _positive_f32, _cloud_pair, _radius_f32, _same_batching, _sqrt, _unbatch, _vp)
 from .knn import _knn
 
 
@@ -107,6 +107,10 @@ class GridIndex(NamedTuple):
     cell_size: float        # as rounded to fp32
     single: bool            # built from an (N, 3) cloud
 
+    def _arguments(self) -> tuple:
+        """the index as every entry point that reads it takes it: its six leading arguments, in the order of the C ABI"""
+        return (_vp(self.sorted_points), _vp(self.table_keys), _vp(self.table_range), _vp(self.n_in_grid), _vp(self.origin), self.cell_size)
+
 
 _INT64_MIN = -(1 << 63)
 
@@ -143,6 +147,32 @@ def _grid_build(x: Tensor, px, size: float, org, single: bool) -> GridIndex:
     _lib.check(_lib.load().gecco_grid_build_f32(px, _vp(keys), _vp(perm), _vp(sorted_points), _vp(table_keys), _vp(table_range),
                                                 _vp(n_in_grid), B, N, _stream()), "gecco_grid_build_f32")
     return GridIndex(x, sorted_points, perm, keys, table_keys, table_range, n_in_grid, origin, size, single)
+
+
+def _grid_for(p: Tensor, single: bool, index, default_cell, **radii2) -> GridIndex:
+    """The index an operator that walks the grid runs on (`iss_keypoints`, `cluster_dbscan_grid`).  p: the cloud (B, N, 3) as `_cloud`
+    returned it, with `single`; index: None or a GridIndex built over these points; default_cell: the cell_size of the index built
+    for the call when index is None; radii2: the squares of the radii the walk is asked for, by argument name, each of which must
+    not exceed fp32(cell_size^2).  ValueError, before any device call, for an index of another type, batching or N and for a radius
+    above the cell; then the index, built here (origin 0) or the caller's, on the device"""
+    if index is None:
+        size = _grid_cell_size(default_cell)
+    elif isinstance(index, GridIndex):
+        _same_batching(p, single, index.points, index.single, "points", "index")
+        if index.points.shape[1] != p.shape[1]:
+            raise ValueError(f"points has {p.shape[1]} points a cloud, the index was built over {index.points.shape[1]}")
+        size = index.cell_size
+    else:
+        raise ValueError("index must be None or a GridIndex")
+    cell2 = C.c_float(size * size).value   # the library's fp32 product
+    for name, r2 in radii2.items():
+        if not r2 <= cell2:
+            raise ValueError(f"{name}: its square {r2} is above the square of the index's cell_size = {size}: build an index with a larger cell")
+    if index is None:
+        x, px = _f32(p)
+        return _grid_build(x, px, size, None, single)
+    _need_device(p, index.sorted_points)
+    return index
 
 
 def build_grid_index(points: Tensor, cell_size: float, origin=None) -> GridIndex:
@@ -207,8 +237,7 @@ def _grid_counts(x: Tensor, px, g: GridIndex, qorder: Tensor, r2: float, exclude
     """the count launch on an index: int32 (B, M)"""
     B, M, _ = x.shape
     cnt = torch.empty(B, M, device=x.device, dtype=torch.int32)
-    _lib.check(_lib.load().gecco_grid_radius_count_f32(px, _vp(qorder), _vp(g.sorted_points), _vp(g.table_keys), _vp(g.table_range),
-                                                       _vp(g.n_in_grid), _vp(g.origin), g.cell_size, _vp(cnt), B, M, g.points.shape[1], r2,
+    _lib.check(_lib.load().gecco_grid_radius_count_f32(px, _vp(qorder), *g._arguments(), _vp(cnt), B, M, g.points.shape[1], r2,
                                                        int(exclude_self), _stream()), "gecco_grid_radius_count_f32")
     return cnt
 
@@ -275,8 +304,7 @@ def _grid_radius_search(query, ref, radius, exclude_self, max_neighbors, order, 
     B, M, _ = x.shape
 
     def fill(splits, idx, d2):
-        _lib.check(_lib.load().gecco_grid_radius_search_f32(px, _vp(qorder), _vp(g.sorted_points), _vp(g.table_keys), _vp(g.table_range),
-                                                            _vp(g.n_in_grid), _vp(g.origin), g.cell_size, _vp(splits), _vp(idx), _ptr(d2), B, M,
+        _lib.check(_lib.load().gecco_grid_radius_search_f32(px, _vp(qorder), *g._arguments(), _vp(splits), _vp(idx), _ptr(d2), B, M,
                                                             g.points.shape[1], r2, int(exclude_self), _stream()),
                    "gecco_grid_radius_search_f32")
     return _csr_neighbors(_grid_counts(x, px, g, qorder, r2, exclude_self), fill, order != "grid", order == "distance", return_distances,
