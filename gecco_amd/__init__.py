@@ -17,7 +17,7 @@ from .diffusion import Diffusion  # noqa: E402,F401
 from .hip_ops import frozen_weights, weights_changed  # noqa: E402,F401
 from .pointops import FPS_RESIDENT_MAX_POINTS, farthest_point_sample, farthest_point_subsample  # noqa: E402,F401
 from .pointops import KNN_MAX_K, knn, knn_gather, statistical_outlier_mask  # noqa: E402,F401
-from .pointops import estimate_normals  # noqa: E402,F401
+from .pointops import estimate_normals, estimate_normals_grid  # noqa: E402,F401
 from .pointops import voxel_downsample, voxel_pool  # noqa: E402,F401
 from .pointops import ICP_MAX_ITERATIONS, ICPResult, icp, transform_points  # noqa: E402,F401
 from .pointops import DBSCAN_MAX_ROUNDS, DBSCANResult, cluster_dbscan, cluster_dbscan_grid, cluster_sizes  # noqa: E402,F401

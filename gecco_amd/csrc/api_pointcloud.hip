@@ -499,6 +499,25 @@ int gecco_iss_keypoints_f32(const float* sorted, const int64_t* table_keys, cons
     return 0;
 }
 
+// Normals from radius neighbourhoods on the grid index (normals_grid.hip).  Every refusal is -2, null pointers included; qorder, origin,
+// viewpoint, eigenvalues, curvature and counts nullable
+int gecco_normals_grid_f32(const float* query, const int32_t* qorder, const float* sorted, const int64_t* table_keys,
+                           const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size, const float* viewpoint,
+                           float radius2, int min_neighbors, float* normals, double* eigenvalues, double* curvature, int32_t* counts, int B,
+                           int M, int N, void* stream) {
+    if (!query || !normals) return fail(-2, "normals_grid: null argument");
+    if (const int bad = radius_common("normals_grid", B, M, N, radius2, 0)) return bad;
+    GridIndexArgs index;
+    if (const int bad = grid_index("normals_grid", sorted, table_keys, table_range, n_in_grid, origin, cell_size, B, N, index)) return bad;
+    if (const int bad = grid_radius2_fits("normals_grid", "radius2", cell_size, radius2)) return bad;
+    if (min_neighbors < 1) return fail(-2, "normals_grid: min_neighbors = %d must be >= 1", min_neighbors);
+    const int rc = normals_grid_launch(query, qorder, index, viewpoint, radius2, min_neighbors, normals, eigenvalues, curvature, counts, B, M, N,
+                                       (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "normals_grid: the grid for B = %d, M = %d passes 2^31 - 1 workgroups", B, M);
+    TRY(rc, "normals_grid");
+    return 0;
+}
+
 // DBSCAN on the grid index (dbscan.hip's grid form): gecco_dbscan_f32's outputs and workspace, the index through grid_index as every
 // entry above.  It stands here, behind the grid entries, for their checks.  Every refusal is -2, null pointers included
 int gecco_dbscan_grid_f32(const float* sorted, const int64_t* table_keys, const int32_t* table_range, const int32_t* n_in_grid,

@@ -14,7 +14,7 @@
 //              d = double(p_j) - double(p_i) per axis;  S1 = sum d (3 sums), S2 = sum d d^T (xx, xy, xz, yy, yz, zz), each from 0 in
 //              ball order;  inv = 1 / m;  mu = S1 inv;  C_ab = S2_ab inv - mu_a mu_b.  |d| <= the radius, so the raw moments cancel
 //              against the radius and not against the cloud's distance from the origin
-//   eigen      big = max |C_ab|;  A = C sc with sc = 1 / big;  ISS_JACOBI_SWEEPS = 8 cyclic Jacobi sweeps over (0,1), (0,2), (1,2) with
+//   eigen      big = max |C_ab|;  A = C sc with sc = 1 / big;  SYM3_JACOBI_SWEEPS = 8 cyclic Jacobi sweeps over (0,1), (0,2), (1,2) with
 //              the guarded rotation of rigid_fit.h (icp_rotate: a non-finite theta gives t = 0, a theta whose square would overflow
 //              t = 1 / (2 theta)), a fixed count;  lambda = diag big, negative roundings clamped to 0, sorted lambda0 <= lambda1 <= lambda2
 //   candidate  m_i >= min_neighbors, big a positive finite number (all of the ball identical: not a candidate, Open3D's
@@ -30,8 +30,8 @@
 // Two launches, one thread per SORTED POSITION in both: thread t of a cloud owns the point at sorted[t], whose 16-byte load gives the
 // coordinates and, in .w, the original index i its outputs go to.  The lanes of a wave are neighbours in the sorted order, so they
 // probe the same cells and read the same runs.  iss_saliency_kernel walks the box of r2s, adds the count and the nine fp64 sums in
-// registers, solves the 3 x 3 problem in registers (the matrix and the rotations are scalars: no indexed local array, no scratch;
-// plane.hip's refit keeps arrays in scratch because one thread per cloud runs it, here every thread does) and writes saliency,
+// registers, solves the 3 x 3 problem in registers (sym3_jacobi.h's sym3_eigen, the eigenvalues-only form of the solve that
+// normals_grid.hip shares: the matrix and the rotations are scalars, no indexed local array, no scratch) and writes saliency,
 // eigenvalues and counts at i.  iss_select_kernel starts from saliency[i] > 0 (other threads write false and return), walks the box of
 // r2n, counts the ball and compares saliency[j], a gather by the index carried in .w, and writes the mask byte.  A thread writes its own
 // words only: no atomics, no LDS, no workspace, no thread waits on another, every loop is bounded by a constant, by cap or by N.
@@ -45,36 +45,10 @@
 #include "grid_walk.h"
 #include "kernels.h"
 #include "launch_state.h"
+#include "sym3_jacobi.h"
 #include "voxel_cell.h"
 
 namespace {
-
-constexpr int ISS_JACOBI_SWEEPS = 8;   // rigid_fit.h's count: quadratic convergence, fp64 by the fifth
-
-static __device__ __forceinline__ bool iss_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and inf
-
-// icp_rotate (rigid_fit.h) for a symmetric 3 x 3 matrix held in scalars, eigenvalues only: the rotation that annihilates a_pq; arp, arq
-// are the entries of the third row r against p and q.  Same guard, same order of operations, none contracted
-static __device__ __forceinline__ void iss_rotate(double& app, double& aqq, double& apq, double& arp, double& arq) {
-#pragma clang fp contract(off)
-    double t = 0.0;
-    if (apq != 0.0) {
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double at = fabs(theta);
-        if (at <= 1e150)
-            t = copysign(1.0, theta) / (at + sqrt(theta * theta + 1.0));
-        else if (iss_finite(at))
-            t = 0.5 / theta;
-    }
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    const double shift = t * apq;
-    app -= shift;
-    aqq += shift;
-    apq = 0.0;
-    const double rp = arp, rq = arq;
-    arp = c * rp - s * rq;
-    arq = s * rp + c * rq;
-}
 
 // grid: B * tiles blocks of T sorted positions.  eigenvalues, counts nullable
 template <int T>
@@ -91,40 +65,17 @@ __global__ __launch_bounds__(T) void iss_saliency_kernel(const GridView index, f
     if (i >= (unsigned)N) return;   // a sorted array no build wrote: nothing outside the outputs is written
     const float qx = own[0], qy = own[1], qz = own[2];
     const double cx = (double)qx, cy = (double)qy, cz = (double)qz;
-    int m = 0;
-    double sx = 0.0, sy = 0.0, sz = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+    Sym3Moments sums;   // the count and the nine fp64 sums, in registers
     if (cloud_finite3(qx, qy, qz))   // (a non-finite point has dist2 = +inf to everything)
         grid_walk(index, b, qx, qy, qz, R, r2_bits, [&](const f32x4 p, unsigned) {
-            const double dx = (double)p[0] - cx, dy = (double)p[1] - cy, dz = (double)p[2] - cz;
-            ++m;
-            sx += dx, sy += dy, sz += dz;
-            sxx += dx * dx, sxy += dx * dy, sxz += dx * dz;
-            syy += dy * dy, syz += dy * dz, szz += dz * dz;
+            sums.add((double)p[0] - cx, (double)p[1] - cy, (double)p[2] - cz);
         });
+    const int m = sums.m;
     double l0 = 0.0, l1 = 0.0, l2 = 0.0, sal = 0.0;
     if (m >= min_neighbors) {
-        const double im = 1.0 / (double)m;
-        const double mx = sx * im, my = sy * im, mz = sz * im;
-        double a00 = sxx * im - mx * mx, a01 = sxy * im - mx * my, a02 = sxz * im - mx * mz;
-        double a11 = syy * im - my * my, a12 = syz * im - my * mz, a22 = szz * im - mz * mz;
-        const double big = fmax(fmax(fmax(fabs(a00), fabs(a01)), fmax(fabs(a02), fabs(a11))), fmax(fabs(a12), fabs(a22)));
-        if (big > 0.0 && iss_finite(big)) {
-            const double sc = 1.0 / big;
-            a00 *= sc, a01 *= sc, a02 *= sc, a11 *= sc, a12 *= sc, a22 *= sc;
-            for (int sweep = 0; sweep < ISS_JACOBI_SWEEPS; ++sweep) {
-                iss_rotate(a00, a11, a01, a02, a12);   // (0, 1): the third row is 2
-                iss_rotate(a00, a22, a02, a01, a12);   // (0, 2): the third row is 1
-                iss_rotate(a11, a22, a12, a01, a02);   // (1, 2): the third row is 0
-            }
-            l0 = fmax(a00 * big, 0.0), l1 = fmax(a11 * big, 0.0), l2 = fmax(a22 * big, 0.0);
-            double lo = fmin(l0, l1), hi = fmax(l0, l1);   // three compare-exchanges
-            l0 = lo, l1 = hi;
-            lo = fmin(l1, l2), hi = fmax(l1, l2);
-            l1 = lo, l2 = hi;
-            lo = fmin(l0, l1), hi = fmax(l0, l1);
-            l0 = lo, l1 = hi;
-            if (l1 < gamma_21 * l2 && l0 < gamma_32 * l1 && l0 > 0.0) sal = l0;
-        }
+        const Sym3Eigen e = sym3_eigen<false>(sums);   // (0 where big is no positive finite number)
+        l0 = e.l0, l1 = e.l1, l2 = e.l2;
+        if (e.solved && l1 < gamma_21 * l2 && l0 < gamma_32 * l1 && l0 > 0.0) sal = l0;
     }
     const size_t row = (size_t)b * N + i;
     saliency[row] = sal;

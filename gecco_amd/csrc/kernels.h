@@ -580,6 +580,12 @@ int grid_radius_launch(const float* query, const int* qorder, const GridIndexArg
 // workgroups
 int iss_launch(const GridIndexArgs& index, double* saliency, double* eigenvalues, int* counts, unsigned char* mask, int B, int N, float r2s,
                float r2n, double gamma_21, double gamma_32, int min_neighbors, hipStream_t st);
+// normals_grid.hip — normals and curvature from radius neighbourhoods on the grid index (definition: gecco_normals_grid_f32): one
+// launch, one thread per query, answered in the order of qorder (nullable: as given).  r2 = fp32(radius^2); viewpoint (B, 3),
+// eigenvalues, curvature, counts nullable.  -2: arguments out of range (a radius2 above fp32(cell_size^2) among them), -3: the grid
+// would pass 2^31 - 1 workgroups
+int normals_grid_launch(const float* query, const int* qorder, const GridIndexArgs& index, const float* viewpoint, float r2, int min_neighbors,
+                        float* normals, double* eigenvalues, double* curvature, int* counts, int B, int M, int N, hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

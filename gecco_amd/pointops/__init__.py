@@ -6,7 +6,8 @@ definition, with its worked examples, launch counts and determinism guarantees:
     fps      farthest-point sampling, resident and streaming forms (csrc/fps.hip, gecco_fps_f32)
     knn      k-nearest-neighbour search, direct and split forms, the statistical outlier filter and the cloud resolution built on
              it (csrc/knn.hip, gecco_knn_f32)
-    normals  surface normals with curvature from the neighbour lists (csrc/normals.hip, gecco_normals_f32)
+    normals  surface normals with curvature from the neighbour lists (csrc/normals.hip, gecco_normals_f32) or from the radius balls
+             of the grid index (csrc/normals_grid.hip, gecco_normals_grid_f32)
     voxel    voxel-grid downsampling with attribute pooling (csrc/voxel.hip, gecco_voxel_downsample_f32)
     icp      rigid ICP registration, point-to-point and point-to-plane (csrc/icp.hip, gecco_icp_f32)
     fpfh     FPFH descriptors and nearest-neighbour matching in feature space (csrc/fpfh.hip, gecco_fpfh_f32, gecco_feature_nn_f32)
@@ -18,7 +19,7 @@ definition, with its worked examples, launch counts and determinism guarantees:
     iss      ISS keypoint detection on that index (csrc/iss.hip, gecco_iss_keypoints_f32)
     _args    the argument checks, moves to the device and result tails the families share
 
-Imports point one way: _args <- every family; knn <- normals, fpfh, radius; radius <- iss, dbscan.  Every public name is passed on
+Imports point one way: _args <- every family; knn <- normals, fpfh, radius; radius <- iss, dbscan, normals.  Every public name is passed on
 here and by `gecco_amd`: `gecco_amd.knn_gather is gecco_amd.pointops.knn_gather is` the one in the knn module.  `knn`, `icp` and
 `fpfh` are functions that share their module's name, so as attributes of this package those names are the functions;
 `importlib.import_module("gecco_amd.pointops.knn")` reaches the module.
@@ -27,7 +28,7 @@ HIP tensors only: there is no CPU fallback (`voxel_pool`, `cluster_sizes` and `p
 from ._args import KNN_MAX_K, KNN_SPLIT_SLICE, VOXEL_MAX_POINTS  # noqa: F401
 from .fps import FPS_RESIDENT_MAX_POINTS, _FPS_STREAM_SLICE, _fps_workspace_bytes, farthest_point_sample, farthest_point_subsample  # noqa: F401
 from .knn import _knn, _knn_workspace_bytes, cloud_resolution, knn, knn_gather, statistical_outlier_mask  # noqa: F401
-from .normals import estimate_normals  # noqa: F401
+from .normals import estimate_normals, estimate_normals_grid  # noqa: F401
 from .voxel import _voxel_workspace_bytes, voxel_downsample, voxel_pool  # noqa: F401
 from .icp import ICP_MAX_ITERATIONS, _ICP_STATE_BYTES, ICPResult, _icp_workspace_bytes, icp, transform_points  # noqa: F401
 from .fpfh import FEATURE_MAX_DIM, FPFH_BINS, _feature_nn, _feature_nn_workspace_bytes, fpfh, match_features  # noqa: F401

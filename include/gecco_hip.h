@@ -1494,6 +1494,48 @@ int gecco_iss_keypoints_f32(const float* sorted, const int64_t* table_keys, cons
                             const float* origin, float cell_size, double* saliency, double* eigenvalues, int32_t* counts, uint8_t* mask, int B,
                             int N, float salient_radius2, float non_max_radius2, double gamma_21, double gamma_32, int min_neighbors,
                             void* stream);
+/* Normals and curvature from RADIUS neighbourhoods on the grid index above (csrc/normals_grid.hip): Open3D's estimate_normals(
+ * KDTreeSearchParamRadius(r)), PCL's NormalEstimation::setRadiusSearch, every point within r and no cap (gecco_normals_f32 reads the
+ * k <= GECCO_KNN_MAX_K neighbours of the brute-force search).  sorted, table_keys, table_range, n_in_grid, origin and cell_size are the
+ * index of the cloud; query (B, M, 3) and qorder are gecco_grid_radius_count_f32's.  tests/_normals_grid_ref.py restates the definition
+ * in numpy.  Per batch element, with r2 = radius2 = fp32(radius^2) from the caller:
+ *     queries     q_i: the points of the cloud themselves (query = the cloud, M = N) or other positions.  A point of the cloud is in its
+ *                 own ball because its dist2 is 0: nothing is excluded by index
+ *     ball        the j with dist2(q_i, p_j) <= r2 on the bits, gecco_radius_count_f32's predicate, visited in ascending sorted position
+ *                 of the index (by (cell key, j), the off-grid tail last): that order is part of the definition, as it is for ISS.  A
+ *                 non-finite query has an empty ball; a non-finite point is in nobody's ball
+ *     count       m_i = the size of the ball, never clamped
+ *     moments,    exactly the `moments` and `eigen` steps of gecco_iss_keypoints_f32 above, about the query: fp64 sums of d =
+ *     eigen       double(p_j) - double(q_i) in ball order, C = S2 / m - mu mu^T, big = max |C_ab|, A = C / big, 8 cyclic Jacobi sweeps over
+ *                 (0,1), (0,2), (1,2) with the guarded rotation, nothing contracted, lambda = diag big clamped at 0.  The same rotations
+ *                 are accumulated into V, which starts as the identity: the columns p, q of V rotate as the rows and columns of A do
+ *                 (v_rp' = c v_rp - s v_rq, v_rq' = s v_rp + c v_rq)
+ *     order       the three (lambda, column) pairs sorted ascending by the three compare-exchanges (0,1), (1,2), (0,1) that ISS uses on
+ *                 its eigenvalues; a pair moves only when strictly smaller, so equal eigenvalues keep their column order
+ *     normal      the column of lambda0 divided by its fp64 norm sqrt((xx + yy) + zz), each component rounded once to fp32
+ *     sign        applied after the rounding, so it can be checked exactly on the output.  With a viewpoint v (B, 3): flip when
+ *                 (n_x d_x + n_y d_y) + n_z d_z < 0 in fp64, d = double(v) - double(q_i); a NaN does not flip.  Without (NULL): the fp32
+ *                 component of largest magnitude is positive, the lowest axis among equal magnitudes (gecco_normals_f32's rule)
+ *     curvature   lambda0 / ((lambda0 + lambda1) + lambda2) in fp64, 0 where that sum is not > 0
+ *     invalid     m_i < min_neighbors, a non-finite query, big not a positive finite number (all of the ball identical): normal
+ *                 (0, 0, 1) as in Open3D, eigenvalues 0, curvature 0, count still m_i.  A collinear ball is valid: its normal is some
+ *                 unit vector of the numerical null space
+ * Outputs, at the row of the query: normals (B, M, 3) fp32, eigenvalues (B, M, 3) fp64 ascending (may be NULL), curvature (B, M) fp64
+ * (may be NULL), counts (B, M) int32 = m_i (may be NULL).  A row depends on the cloud, the query and the index's cell_size and origin,
+ * which fix the order of the sums, and on nothing else: the same bits run to run, in any batch position and at any workgroup size.
+ * Worked example: the 6 x 6 x 6 integer grid (x slowest) of the radius block, cell_size 1.5, origin 0, radius2 2.25, the cloud its own
+ * queries.  Point 0, a corner: m = 7, lambda = (8/49, 2/7, 2/7), normal (1, 1, 1) / sqrt(3), curvature 2/9.  Point 7 = (0, 1, 1), on a
+ * face: m = 14, lambda = (45/196, 4/7, 4/7), normal (1, 0, 0), curvature 45/269.
+ * One launch, one thread per query (thread t answers query qorder[b, t]; NULL: query t): the walk of csrc/grid_walk.h, the count and
+ * the nine sums in registers, the solve of csrc/sym3_jacobi.h that gecco_iss_keypoints_f32 runs without the vectors.  A thread writes
+ * its own words only: no atomics, no workspace, no allocation, no synchronisation, asynchronous on `stream`.  Return -2 before anything
+ * is enqueued (and gecco_last_error) for: a null required pointer, B, M or N < 1, N above GECCO_VOXEL_MAX_POINTS, a cell_size that is
+ * not a finite number > 0 with a finite reciprocal, a radius2 that is not a finite number > 0 or is above fp32(cell_size * cell_size)
+ * (build an index with a larger cell), min_neighbors < 1; -3 for a grid above 2^31 - 1 workgroups. */
+int gecco_normals_grid_f32(const float* query, const int32_t* qorder, const float* sorted, const int64_t* table_keys,
+                           const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size, const float* viewpoint,
+                           float radius2, int min_neighbors, float* normals, double* eigenvalues, double* curvature, int32_t* counts, int B,
+                           int M, int N, void* stream);
 /* DBSCAN clustering on the grid index above (csrc/dbscan.hip, the grid form): gecco_dbscan_f32 with its three scans of the whole cloud
  * (count, hook, border) replaced by walks over the cells a ball of eps can reach.  The cloud is the one the index was built over;
  * sorted, table_keys, table_range, n_in_grid, origin and cell_size are that index, as gecco_iss_keypoints_f32 takes it.
