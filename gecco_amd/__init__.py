@@ -24,6 +24,6 @@ from .pointops import DBSCAN_MAX_ROUNDS, DBSCANResult, cluster_dbscan, cluster_d
 from .pointops import RadiusNeighbors, radius_count, radius_outlier_mask, radius_search  # noqa: E402,F401
 from .pointops import GridIndex, build_grid_index  # noqa: E402,F401
 from .pointops import ISSResult, cloud_resolution, iss_keypoints  # noqa: E402,F401
-from .pointops import FEATURE_MAX_DIM, FPFH_BINS, fpfh, match_features  # noqa: E402,F401
+from .pointops import FEATURE_MAX_DIM, FPFH_BINS, fpfh, fpfh_grid, match_features  # noqa: E402,F401
 from .pointops import RANSAC_MAX_HYPOTHESES, RANSAC_MAX_REFINE, RANSACResult, ransac_registration  # noqa: E402,F401
 from .pointops import PLANE_MAX_HYPOTHESES, PLANE_MAX_REFINE, PlaneResult, PlanesResult, point_plane_distance, segment_plane, segment_planes  # noqa: E402,F401

@@ -256,6 +256,7 @@ SIGNATURES = {
     "gecco_grid_radius_search_f32": (i, [vp] * 7 + [fl, vp, vp, vp, i, i, i, fl, i, vp]),
     "gecco_iss_keypoints_f32": (i, [vp] * 5 + [fl] + [vp] * 4 + [i, i, fl, fl, db, db, i, vp]),
     "gecco_normals_grid_f32": (i, [vp] * 7 + [fl, vp, fl, i] + [vp] * 4 + [i, i, i, vp]),
+    "gecco_fpfh_grid_f32": (i, [vp] * 6 + [fl, fl] + [vp] * 3 + [i, i, vp]),
     "gecco_dbscan_grid_f32": (i, [vp] * 5 + [fl] + [vp] * 6 + [i, i, fl, i, i, vp]),
     "gecco_convnext_stem_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),
     "gecco_convnext_dwconv_ln_f32": (i, [vp] * 6 + [i, i, i, i, fl, vp]),

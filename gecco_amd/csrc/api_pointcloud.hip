@@ -518,6 +518,22 @@ int gecco_normals_grid_f32(const float* query, const int32_t* qorder, const floa
     return 0;
 }
 
+// FPFH from radius neighbourhoods on the grid index (fpfh_grid.hip).  Every refusal is -2, null pointers included; origin nullable; spfh
+// and count are required (the first launch's outputs, read by the second)
+int gecco_fpfh_grid_f32(const float* normals, const float* sorted, const int64_t* table_keys, const int32_t* table_range,
+                        const int32_t* n_in_grid, const float* origin, float cell_size, float radius2, float* fpfh, float* spfh, int32_t* count,
+                        int B, int N, void* stream) {
+    if (!normals || !fpfh || !spfh || !count) return fail(-2, "fpfh_grid: null argument");
+    GridIndexArgs index;
+    if (const int bad = grid_index("fpfh_grid", sorted, table_keys, table_range, n_in_grid, origin, cell_size, B, N, index)) return bad;
+    if (!finite_positive(radius2)) return fail(-2, "fpfh_grid: radius2 = %g must be a finite number > 0", (double)radius2);
+    if (const int bad = grid_radius2_fits("fpfh_grid", "radius2", cell_size, radius2)) return bad;
+    const int rc = fpfh_grid_launch(normals, index, radius2, fpfh, spfh, count, B, N, (hipStream_t)stream);
+    if (rc == -3) return fail(-3, "fpfh_grid: the grid for B = %d, N = %d passes 2^31 - 1 workgroups", B, N);
+    TRY(rc, "fpfh_grid");
+    return 0;
+}
+
 // DBSCAN on the grid index (dbscan.hip's grid form): gecco_dbscan_f32's outputs and workspace, the index through grid_index as every
 // entry above.  It stands here, behind the grid entries, for their checks.  Every refusal is -2, null pointers included
 int gecco_dbscan_grid_f32(const float* sorted, const int64_t* table_keys, const int32_t* table_range, const int32_t* n_in_grid,

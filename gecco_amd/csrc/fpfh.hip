@@ -5,7 +5,7 @@
 // histograms (float atomics) -> a gather and a weighted mean, and torch.cdist (an M x N matrix) -> argmin for the matching.
 //
 // Definition (gecco_fpfh_f32 and gecco_feature_nn_f32, include/gecco_hip.h; tests/_fpfh_ref.py restates both in numpy).
-//   pair feature   fp64 on the fp32 inputs, every operation rounded, none contracted (fpfh_pair_bins): three bin coordinates u in
+//   pair feature   fp64 on the fp32 inputs, every operation rounded, none contracted (fpfh_pair_bins, fpfh_pair.h): three bin coordinates u in
 //                  [0, 11], bins clamp(floor(u), 0, 10) in three groups of 11
 //   neighbourhood  entry t of idx[i, 0 .. k) counts when 0 <= j < N, j != i (by index), dist2(p_i, p_j) <= radius2 when there is a
 //                  radius, and the twelve numbers of p_i, n_i, p_j, n_j are finite; m_i of them
@@ -33,53 +33,15 @@
 // No atomics, no thread waits on another, every loop's trip count depends on the sizes alone; a row's bits depend on that row's inputs
 // and nothing else, so they are the same run to run, in any batch position, for any launch geometry and in both forms.
 #include "cloud_nn.h"
+#include "fpfh_pair.h"
 #include "kernels.h"
 #include "launch_state.h"
 
 namespace {
 
-constexpr int FPFH_BINS = GECCO_FPFH_BINS;   // 3 groups of 11
-static_assert(FPFH_BINS == 33 && GECCO_KNN_MAX_K <= 255, "three groups of 11 bins; a count fits a byte");
+static_assert(GECCO_KNN_MAX_K <= 255, "a count fits a byte");   // (FPFH_BINS, fpfh_bin and fpfh_pair_bins: fpfh_pair.h)
 constexpr int FPFH_SUM_THREADS = 256;
 constexpr int FPFH_POINTS = FPFH_SUM_THREADS / FPFH_BINS;   // 7 points, 231 of 256 threads at work
-
-static __device__ __forceinline__ int fpfh_bin(double u) { return u >= 10.0 ? 10 : (u >= 1.0 ? (int)u : 0); }   // a NaN: bin 0
-
-// steps 1 - 8 of the definition for the pair (point i, neighbour j)
-static __device__ __forceinline__ void fpfh_pair_bins(float pix, float piy, float piz, float nix, float niy, float niz, float pjx, float pjy,
-                                                      float pjz, float njx, float njy, float njz, int& b0, int& b1, int& b2) {
-#pragma clang fp contract(off)
-    constexpr double PI = 3.14159265358979323846;
-    double n1x = nix, n1y = niy, n1z = niz, n2x = njx, n2y = njy, n2z = njz;
-    double dx = (double)pjx - (double)pix, dy = (double)pjy - (double)piy, dz = (double)pjz - (double)piz;
-    const double d = sqrt((dx * dx + dy * dy) + dz * dz);
-    double f0 = 0.0, f1 = 0.0, f2 = 0.0;
-    if (d != 0.0) {
-        const double a1 = ((n1x * dx + n1y * dy) + n1z * dz) / d;
-        const double a2 = ((n2x * dx + n2y * dy) + n2z * dz) / d;
-        double g2 = a1;
-        if (fabs(a1) < fabs(a2)) {   // the frame sits at the point whose normal is nearer the line: acos(|a1|) > acos(|a2|)
-            double s;
-            s = n1x, n1x = n2x, n2x = s;
-            s = n1y, n1y = n2y, n2y = s;
-            s = n1z, n1z = n2z, n2z = s;
-            dx = -dx, dy = -dy, dz = -dz;
-            g2 = -a2;
-        }
-        double vx = dy * n1z - dz * n1y, vy = dz * n1x - dx * n1z, vz = dx * n1y - dy * n1x;   // dp x N1
-        const double vn = sqrt((vx * vx + vy * vy) + vz * vz);
-        if (vn != 0.0) {
-            vx = vx / vn, vy = vy / vn, vz = vz / vn;
-            const double wx = n1y * vz - n1z * vy, wy = n1z * vx - n1x * vz, wz = n1x * vy - n1y * vx;   // N1 x v
-            f1 = (vx * n2x + vy * n2y) + vz * n2z;
-            f0 = atan2((wx * n2x + wy * n2y) + wz * n2z, (n1x * n2x + n1y * n2y) + n1z * n2z);
-            f2 = g2;
-        }
-    }
-    b0 = fpfh_bin((11.0 * (f0 + PI)) / (2.0 * PI));
-    b1 = fpfh_bin((11.0 * (f1 + 1.0)) * 0.5);
-    b2 = fpfh_bin((11.0 * (f2 + 1.0)) * 0.5);
-}
 
 // grid: B * tiles blocks, block (b, tile) owns points tile * T .. + T - 1 of cloud b.  LDS: T * (k | 1) words of idx, T words of m,
 // 33 * T bytes of counters.

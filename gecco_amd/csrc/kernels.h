@@ -586,6 +586,12 @@ int iss_launch(const GridIndexArgs& index, double* saliency, double* eigenvalues
 // would pass 2^31 - 1 workgroups
 int normals_grid_launch(const float* query, const int* qorder, const GridIndexArgs& index, const float* viewpoint, float r2, int min_neighbors,
                         float* normals, double* eigenvalues, double* curvature, int* counts, int B, int M, int N, hipStream_t st);
+// fpfh_grid.hip — FPFH descriptors from radius neighbourhoods on the grid index (definition: gecco_fpfh_grid_f32): two launches over
+// the sorted positions; spfh and count are the first one's outputs and the second one's inputs, all three required.  r2 =
+// fp32(radius^2).  -2: arguments out of range (a radius2 above fp32(cell_size^2) among them), -3: the grid would pass 2^31 - 1
+// workgroups
+int fpfh_grid_launch(const float* normals, const GridIndexArgs& index, float r2, float* fpfh, float* spfh, int* count, int B, int N,
+                     hipStream_t st);
 // sampler.hip — inpainting: re-draw the known points of the fp64 state at the current noise level
 int sampler_refresh_known_launch(double* x, const float* known, const float* noise, const double* sched, const int* step, int col,
                                  int m, int n_known, int B, hipStream_t st);

@@ -10,7 +10,8 @@ definition, with its worked examples, launch counts and determinism guarantees:
              of the grid index (csrc/normals_grid.hip, gecco_normals_grid_f32)
     voxel    voxel-grid downsampling with attribute pooling (csrc/voxel.hip, gecco_voxel_downsample_f32)
     icp      rigid ICP registration, point-to-point and point-to-plane (csrc/icp.hip, gecco_icp_f32)
-    fpfh     FPFH descriptors and nearest-neighbour matching in feature space (csrc/fpfh.hip, gecco_fpfh_f32, gecco_feature_nn_f32)
+    fpfh     FPFH descriptors from the neighbour lists (csrc/fpfh.hip, gecco_fpfh_f32) or from the radius balls of the grid index
+             (csrc/fpfh_grid.hip, gecco_fpfh_grid_f32), and nearest-neighbour matching in feature space (gecco_feature_nn_f32)
     ransac   RANSAC registration from correspondences (csrc/ransac.hip, gecco_ransac_f32)
     plane    RANSAC plane segmentation, one plane or several (csrc/plane.hip, gecco_plane_ransac_f32)
     dbscan   DBSCAN clustering, by direct scans (csrc/dbscan.hip, gecco_dbscan_f32) or on the grid index (gecco_dbscan_grid_f32)
@@ -19,7 +20,7 @@ definition, with its worked examples, launch counts and determinism guarantees:
     iss      ISS keypoint detection on that index (csrc/iss.hip, gecco_iss_keypoints_f32)
     _args    the argument checks, moves to the device and result tails the families share
 
-Imports point one way: _args <- every family; knn <- normals, fpfh, radius; radius <- iss, dbscan, normals.  Every public name is passed on
+Imports point one way: _args <- every family; knn <- normals, fpfh, radius; radius <- iss, dbscan, normals, fpfh.  Every public name is passed on
 here and by `gecco_amd`: `gecco_amd.knn_gather is gecco_amd.pointops.knn_gather is` the one in the knn module.  `knn`, `icp` and
 `fpfh` are functions that share their module's name, so as attributes of this package those names are the functions;
 `importlib.import_module("gecco_amd.pointops.knn")` reaches the module.
@@ -31,7 +32,7 @@ from .knn import _knn, _knn_workspace_bytes, cloud_resolution, knn, knn_gather, 
 from .normals import estimate_normals, estimate_normals_grid  # noqa: F401
 from .voxel import _voxel_workspace_bytes, voxel_downsample, voxel_pool  # noqa: F401
 from .icp import ICP_MAX_ITERATIONS, _ICP_STATE_BYTES, ICPResult, _icp_workspace_bytes, icp, transform_points  # noqa: F401
-from .fpfh import FEATURE_MAX_DIM, FPFH_BINS, _feature_nn, _feature_nn_workspace_bytes, fpfh, match_features  # noqa: F401
+from .fpfh import FEATURE_MAX_DIM, FPFH_BINS, _feature_nn, _feature_nn_workspace_bytes, fpfh, fpfh_grid, match_features  # noqa: F401
 from .ransac import RANSAC_MAX_HYPOTHESES, RANSAC_MAX_REFINE, RANSACResult, _ransac_workspace_bytes, ransac_registration  # noqa: F401
 from .plane import PLANE_MAX_HYPOTHESES, PLANE_MAX_REFINE, _PLANE_BLOCK_HYPOTHESES, PlaneResult, PlanesResult, _plane_workspace_bytes  # noqa: F401
 from .plane import point_plane_distance, segment_plane, segment_planes  # noqa: F401

@@ -38,7 +38,32 @@ every d2 is +inf gets j = 0 and d2 = +inf.  No M x N matrix is formed.  Mutual: 
 (the reverse search plus a gather and a compare in torch).  The forms "direct" / "split" and the auto rule are those of `knn`.
 No atomics and no thread waits on another: the same bits run to run, in any batch position, in both forms of either search and with
 `idx` given or searched.  A non-finite point or normal changes the SPFH rows whose lists name it and the FPFH rows whose lists name it
-or one of those rows, nothing else."""
+or one of those rows, nothing else.
+
+FPFH from radius neighbourhoods on the grid index (`fpfh_grid`; csrc/fpfh_grid.hip, gecco_fpfh_grid_f32).  Open3D's
+`compute_fpfh_feature(KDTreeSearchParamRadius(r))`, PCL's `FPFHEstimation::setRadiusSearch`: every point within r, with no cap, the
+ball `estimate_normals_grid` fits its normals to, where `fpfh` reads at most KNN_MAX_K neighbours of a search that tests every point
+against every point.  A thread walks the cells of the grid index its ball can reach (csrc/grid_walk.h, the walk of
+`radius_count(index=...)`, `iss_keypoints` and `estimate_normals_grid`), twice: no neighbour list is written.  Definition
+(include/gecco_hip.h; tests/_fpfh_grid_ref.py restates it in numpy).  Per cloud, with r2 = fp32(radius^2) formed as `radius_count`
+forms it:
+    ball          of point i: the j with dist2(p_i, p_j) <= r2 on the bits, `radius_count`'s predicate, visited in ascending sorted
+                  position of the index, the off-grid tail last: that order is part of the definition, as it is for ISS and
+                  `estimate_normals_grid`.  A non-finite p_i has an empty ball; a non-finite p_j is in nobody's ball
+    counted       a member of the ball with j != i BY INDEX (an exact duplicate of the point stays a neighbour and contributes the
+    neighbour     zero triple, bins 5, 16, 27, as in `fpfh`) and all six numbers of n_i and n_j finite.  m_i = the number of counted
+                  neighbours (`count`), never clamped: it may exceed 64 and 255
+    pair feature  steps 1 - 9 above, by the same code (csrc/fpfh_pair.h)
+    SPFH          spfh[i, b] = fp32((100.0 count_b) / m_i) in double, 32-bit integer counts; a zero row when m_i = 0
+    FPFH          over the counted neighbours in ball order that have dist2 != 0 and m_j > 0: w = 1 / double(dist2), dist2 the value
+                  the walk tested; W = sum w, acc[b] = sum w double(spfh[j, b]), each sum one rounded fp64 operation per term, nothing
+                  contracted; fpfh[i, b] = fp32(double(spfh[i, b]) + (W > 0 ? acc[b] / W : 0))
+`count` and `spfh` do not depend on the index's cell_size or origin: integer counts with one rounding.  `fpfh` has the same bits run to
+run, in any batch position, at any workgroup size and with a prebuilt index or one built for the call with the same parameters; with
+another cell or origin, which change the ball order, it may differ in the last fp32 place only.  The two worked examples above hold
+through `fpfh_grid` at any radius that contains them (radius 2).
+Two launches, one thread per sorted position of the index, so that a wave reads the same cells: the first counts into 33 32-bit
+counters of the thread's own in LDS, the second sums into 33 fp64 accumulators in registers.  No atomics, no workspace."""
 from __future__ import annotations
 
 import torch
@@ -46,9 +71,11 @@ from torch import Tensor
 
 from .. import _lib
 from ..hip_ops import _ptr, _stream
-from ._args import (_KNN_FORMS, _check_form, _cloud, _cloud_like, _f32, _knn_slices, _neighbour_list, _neighbour_list_on_device,
-                    _not_empty, _optional_radius2, _results, _same_batching, _split_workspace, _sqrt, _vp)
+from ._args import (_KNN_FORMS, VOXEL_MAX_POINTS, _check_form, _cloud, _cloud_like, _f32, _knn_slices, _neighbour_list,
+                    _neighbour_list_on_device, _not_empty, _optional_radius2, _radius_f32, _results, _same_batching, _split_workspace, _sqrt,
+                    _vp)
 from .knn import _knn
+from .radius import GridIndex, _grid_for
 
 FPFH_BINS = 33                   # GECCO_FPFH_BINS
 FEATURE_MAX_DIM = 64             # GECCO_FEATURE_MAX_DIM
@@ -79,6 +106,41 @@ def fpfh(points: Tensor, normals: Tensor, k: int = 16, radius: float | None = No
     spfh = torch.empty(B, N, FPFH_BINS, device=x.device, dtype=torch.float32)
     cnt = torch.empty(B, N, device=x.device, dtype=torch.int32)
     _lib.check(_lib.load().gecco_fpfh_f32(px, py, _vp(ix), radius2, _vp(out), _vp(spfh), _vp(cnt), B, N, k, _stream()), "gecco_fpfh_f32")
+    return _results(single, out, *((spfh, cnt.long()) if return_spfh else ()))
+
+
+def fpfh_grid(points: Tensor, normals: Tensor, radius: float, index: GridIndex | None = None, return_spfh: bool = False):
+    """FPFH descriptors of the points of a cloud from every neighbour within `radius` and the normals (module docstring: the
+    definition): Open3D's `compute_fpfh_feature(KDTreeSearchParamRadius(radius))`, PCL's `setRadiusSearch`, on the grid index, for the
+    clouds `fpfh`'s search of every point against every point is too slow for and the balls its KNN_MAX_K neighbours do not hold.
+    points and normals (B, N, 3) or (N, 3) on the HIP device, any float dtype and strides (computed on fp32 contiguous copies); the
+    normals are used as given (`estimate_normals_grid(points, radius, index=index)` or any others); radius a plain number shared by the
+    batch, as `radius_count` takes it.
+    index=None builds a grid index for the call with cell_size = radius and origin 0 (the sort of the build allocates, as
+    `build_grid_index` documents).  index=a GridIndex built over THESE points (its cell_size >= radius) is reused: the call is then two
+    launches with no allocation inside the library and no host synchronisation, and can be captured in a graph.  The same parameters
+    give the same bits either way; an index with another cell or origin gives the same count and spfh and an fpfh that may differ in
+    the last fp32 place.
+    Returns fpfh, fp32 (B, N, 33) or (N, 33); with return_spfh also spfh, fp32 of the same shape, and count, int64 (B, N), which is
+    never clamped.  ValueError, before any device call, for bad shapes or an empty cloud, normals that do not match the points, mixed
+    batched and single inputs, a radius that is not a finite fp32 number > 0 with a finite square > 0, N above VOXEL_MAX_POINTS, an
+    index that is neither None nor a GridIndex, an index of another batching or another N, a radius above the index's cell;
+    GeccoHipError for CPU tensors.  No gradient: the inputs are detached."""
+    p, single = _cloud(points)
+    n = _cloud_like(normals, "normals", p, single, "points")
+    B, N, _ = p.shape
+    _not_empty(B, N)
+    rad, r2 = _radius_f32(radius)
+    if N > VOXEL_MAX_POINTS:
+        raise ValueError(f"N = {N} above {VOXEL_MAX_POINTS}")
+    index = _grid_for(p, single, index, rad, radius=r2)
+    dev = index.sorted_points.device
+    y, py = _f32(n)
+    out = torch.empty(B, N, FPFH_BINS, device=dev, dtype=torch.float32)
+    spfh = torch.empty(B, N, FPFH_BINS, device=dev, dtype=torch.float32)
+    cnt = torch.empty(B, N, device=dev, dtype=torch.int32)
+    _lib.check(_lib.load().gecco_fpfh_grid_f32(py, *index._arguments(), r2, _vp(out), _vp(spfh), _vp(cnt), B, N, _stream()),
+               "gecco_fpfh_grid_f32")
     return _results(single, out, *((spfh, cnt.long()) if return_spfh else ()))
 
 

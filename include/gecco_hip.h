@@ -1536,6 +1536,37 @@ int gecco_normals_grid_f32(const float* query, const int32_t* qorder, const floa
                            const int32_t* table_range, const int32_t* n_in_grid, const float* origin, float cell_size, const float* viewpoint,
                            float radius2, int min_neighbors, float* normals, double* eigenvalues, double* curvature, int32_t* counts, int B,
                            int M, int N, void* stream);
+/* Fast Point Feature Histograms from RADIUS neighbourhoods on the grid index above (csrc/fpfh_grid.hip): Open3D's compute_fpfh_feature(
+ * KDTreeSearchParamRadius(r)), PCL's FPFHEstimation::setRadiusSearch, every point within r and no cap, the ball gecco_normals_grid_f32
+ * fits its normals to (gecco_fpfh_f32 reads the k <= GECCO_KNN_MAX_K neighbours of the brute-force search and counts into bytes).  The
+ * cloud is the one the index was built over; sorted, table_keys, table_range, n_in_grid, origin and cell_size are that index, as
+ * gecco_iss_keypoints_f32 takes it; normals (B, N, 3) are indexed as the cloud was.  tests/_fpfh_grid_ref.py restates the definition in
+ * numpy.  Per batch element, with r2 = radius2 = fp32(radius^2) from the caller:
+ *     ball           of point i: the j with dist2(p_i, p_j) <= r2 on the bits, gecco_radius_count_f32's predicate, visited in ascending
+ *                    sorted position of the index (by (cell key, j), the off-grid tail last): that order is part of the definition, as
+ *                    it is for ISS and gecco_normals_grid_f32.  A non-finite p_i has an empty ball; a non-finite p_j is in nobody's ball
+ *     counted        a member of the ball with j != i BY INDEX (an exact duplicate of the point stays a neighbour and contributes the
+ *     neighbour      zero triple, bins 5, 16, 27, as in gecco_fpfh_f32) and all six numbers of n_i and n_j finite.  m_i = the number
+ *                    of counted neighbours, never clamped: it may exceed 64 and 255
+ *     pair feature   steps 1 - 9 of gecco_fpfh_f32's definition above, by the same code (csrc/fpfh_pair.h)
+ *     SPFH           spfh[i, b] = fp32((100.0 * count_b) / m_i) in double, 32-bit integer counts; a zero row when m_i = 0
+ *     FPFH           over the counted neighbours in ball order that have dist2 != 0 and m_j > 0: w = 1 / double(dist2), dist2 the
+ *                    value the walk tested; W = sum w and acc[b] = sum w * double(spfh[j, b]), each sum one rounded fp64 operation
+ *                    per term, nothing contracted; fpfh[i, b] = fp32(double(spfh[i, b]) + (W > 0 ? acc[b] / W : 0))
+ * Outputs, every element written: fpfh (B, N, 33) fp32; spfh (B, N, 33) fp32 and count (B, N) int32 = m_i, REQUIRED: they are the first
+ * launch's outputs and the second launch's inputs; there is no other workspace.  count and spfh do not depend on the index's cell_size
+ * or origin (integer counts, one rounding).  fpfh has the same bits run to run, in any batch position and at any workgroup size; with
+ * another cell_size or origin, which change the ball order, it may differ in the last fp32 place only.  The worked examples of
+ * gecco_fpfh_f32 hold at any radius that contains them (radius2 = 4, cell_size 2).
+ * Two launches, one thread per sorted position (thread t owns the point at sorted[b, t] and writes row perm = the bits of its .w; a
+ * perm outside [0, N) writes nothing): the walk of csrc/grid_walk.h twice, first counting into 33 32-bit counters of the thread's own
+ * in LDS, then summing into 33 fp64 accumulators in registers.  No atomics, no allocation, no synchronisation, asynchronous on
+ * `stream`.  Return -2 before anything is enqueued (and gecco_last_error) for: a null pointer other than origin, B or N < 1, N above
+ * GECCO_VOXEL_MAX_POINTS, a cell_size that is not a finite number > 0 with a finite reciprocal, a radius2 that is not a finite number
+ * > 0 or is above fp32(cell_size * cell_size) (build an index with a larger cell); -3 for a grid above 2^31 - 1 workgroups. */
+int gecco_fpfh_grid_f32(const float* normals, const float* sorted, const int64_t* table_keys, const int32_t* table_range,
+                        const int32_t* n_in_grid, const float* origin, float cell_size, float radius2, float* fpfh, float* spfh, int32_t* count,
+                        int B, int N, void* stream);
 /* DBSCAN clustering on the grid index above (csrc/dbscan.hip, the grid form): gecco_dbscan_f32 with its three scans of the whole cloud
  * (count, hook, border) replaced by walks over the cells a ball of eps can reach.  The cloud is the one the index was built over;
  * sorted, table_keys, table_range, n_in_grid, origin and cell_size are that index, as gecco_iss_keypoints_f32 takes it.
