@@ -120,7 +120,7 @@ class LogUniformSchedule(nn.Module):
 
 class EDMLoss(nn.Module):
     """Weighted denoising loss (reference diffusion.py:118-143).  With grad enabled the denoiser runs on the unfused
-    HIP training path (gecco_amd/autograd.py), so `loss.backward()` produces every parameter gradient in HIP."""
+    HIP training path (gecco_amd/autograd/), so `loss.backward()` produces every parameter gradient in HIP."""
 
     def __init__(self, schedule: nn.Module, sigma_data: float = 1.0, loss_scale: float = 100.0):
         super().__init__()

@@ -126,7 +126,7 @@ def linear(A: Tensor, W: Tensor, bias: Tensor | None = None, pro: tuple[Tensor, 
            w_image: Tensor | None = None, w_shape: tuple[int, int] | None = None):
     """C = residual + act((A*pro_a + pro_o) @ W^T + bias) on (B, rows, K) x (Nout, K).
     act: GaussianActivation when act_alpha is given (normalized or raw), "relu", or none.
-    w_image (precision "bf16x3" / "fp16"): the READY tiled image of W (autograd.WeightImages) — W may then be None, w_shape = (Nout, K)."""
+    w_image (precision "bf16x3" / "fp16"): the READY tiled image of W (autograd/_images.py: WeightImages) — W may then be None, w_shape = (Nout, K)."""
     lib = _lib.load()
     B, rows, K = A.shape
     Nout = W.shape[0] if W is not None else w_shape[0]
@@ -215,7 +215,7 @@ def linear_f16io(A: Tensor, W: Tensor | None, bias: Tensor | None = None, act_al
                  normalized: bool = True, out: Tensor | None = None, w_image: Tensor | None = None,
                  w_shape: tuple[int, int] | None = None):
     """fp16-mode linear whose A and / or C are fp16 TENSORS (the stored intermediates of precision "fp16").
-    w_image: the READY fp16 image of W (autograd.WeightImages) — W may then be None, w_shape = (Nout, K)."""
+    w_image: the READY fp16 image of W (autograd/_images.py: WeightImages) — W may then be None, w_shape = (Nout, K)."""
     lib = _lib.load()
     B, rows, K = A.shape
     Nout = W.shape[0] if W is not None else w_shape[0]
@@ -524,7 +524,7 @@ def linear_pair(A: Tensor, W1: Tensor, b1: Tensor | None, W2: Tensor, b2: Tensor
                 pro: tuple[Tensor, Tensor] | None = None, out: tuple[Tensor, Tensor] | None = None,
                 precision: str = "fp32", w_image: Tensor | None = None) -> tuple[Tensor, Tensor]:
     """(A' @ W1^T + b1, A' @ W2^T + b2) with A' = A*pro_a + pro_o, one launch (A read once).
-    w_image (precision "bf16x3" / "fp16"): the READY images of W1 | W2 (autograd.WeightImages): launch only."""
+    w_image (precision "bf16x3" / "fp16"): the READY images of W1 | W2 (autograd/_images.py: WeightImages): launch only."""
     lib = _lib.load()
     B, rows, K = A.shape
     n1, n2 = W1.shape[0], W2.shape[0]

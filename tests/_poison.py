@@ -9,8 +9,8 @@ THIS call: the stale bits are the right bits.  These helpers put NaN where a cor
   poisoned_out(like)     a NaN-filled destination for `out=`
 
 The fill is 0xFF bytes: a quiet NaN read as fp32, fp16, bf16 and either fp8 format.  State that is meant to persist is never
-touched: the weight-gradient ticket counters (`autograd._tn_counters`, zeroed once and left zero by every launch), the step's
-weight images (`autograd.WEIGHT_IMAGES`), the fp16 texel cache of a conditional plan, graph-private pools, and any plan inside a
+touched: the weight-gradient ticket counters (`autograd/_linear.py: _tn_counters`, zeroed once and left zero by every launch), the step's
+weight images (`autograd/_images.py: WEIGHT_IMAGES`), the fp16 texel cache of a conditional plan, graph-private pools, and any plan inside a
 `frozen_weights()` scope (its workspaces then hold weight images that are valid on purpose)."""
 from __future__ import annotations
 

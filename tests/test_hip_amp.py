@@ -235,17 +235,17 @@ def test_mlp_backward_gradient_as_halves_is_the_same_arithmetic(monkeypatch):
             leaves = [_leaf(v) for v in (x, t, sw, sb, bw, bb, W0, b0, alpha, W2, b2)]
             xg, tg, swg, sbg, bwg, bbg, W0g, b0g, ag_, W2g, b2g = leaves
             seen = {}
-            orig = ag._act_linear_dx
+            orig = ag._mlp._act_linear_dx
 
             def spy(*a, **k):
                 r = orig(*a, **k)
                 seen["du"] = r[0].dtype
                 return r
-            monkeypatch.setattr(ag, "_act_linear_dx", spy)
+            monkeypatch.setattr(ag._mlp, "_act_linear_dx", spy)
             with torch.autocast("cuda", dtype=torch.float16):
                 y = ag.AdaGNMlpFn.apply(xg, tg, swg, sbg, bwg, bbg, G, 1e-5, None, W0g, b0g, ag_, W2g, b2g, 1, False)
             y.backward(dy.cuda())
-            monkeypatch.setattr(ag, "_act_linear_dx", orig)
+            monkeypatch.setattr(ag._mlp, "_act_linear_dx", orig)
             return seen["du"], y.detach(), [v.grad for v in leaves]
         d16, y16, g16 = run("1")
         d32, y32, g32 = run("0")

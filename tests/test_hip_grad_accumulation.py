@@ -311,7 +311,9 @@ def test_standard_step_keeps_weight_gradients_on_the_side_stream(arith, monkeypa
             names[q.data_ptr()] = k + "[q]"
             names[q.data_ptr() + 4 * d * d] = k + "[kv]"
     calls, stack, joins = [], [], []
-    dw, dw_main, join = ag._linear_dw, ag._linear_dw_main, ag._join_thirds
+    dw, dw_main, join = ag._linear_dw, ag._linear_dw_main, ag._side._join_thirds
+    # (the modules that call each of the three by name: `_linear_dw` is called by `_wgrads` and by AdaGNPairFn's backward)
+    sites = [(ag._linear, "_linear_dw"), (ag._adagn, "_linear_dw"), (ag._linear, "_linear_dw_main"), (ag._side, "_join_thirds")]
 
     def rec_dw(*a, **kw):
         stack.append(kw.get("leaf"))
@@ -330,13 +332,11 @@ def test_standard_step_keeps_weight_gradients_on_the_side_stream(arith, monkeypa
         joins.append(torch.cuda.current_stream() == ag._SIDE["stream"])
         return join(*a, **kw)
     r.single(0)   # (creates the side stream and records the weight images)
-    monkeypatch.setattr(ag, "_linear_dw", rec_dw)
-    monkeypatch.setattr(ag, "_linear_dw_main", rec_dw_main)
-    monkeypatch.setattr(ag, "_join_thirds", rec_join)
+    for mod, name in sites:
+        monkeypatch.setattr(mod, name, {"_linear_dw": rec_dw, "_linear_dw_main": rec_dw_main, "_join_thirds": rec_join}[name])
     g_side = r.single(0)
-    monkeypatch.setattr(ag, "_linear_dw", dw)
-    monkeypatch.setattr(ag, "_linear_dw_main", dw_main)
-    monkeypatch.setattr(ag, "_join_thirds", join)
+    for mod, name in sites:
+        monkeypatch.setattr(mod, name, {"_linear_dw": dw, "_linear_dw_main": dw_main, "_join_thirds": join}[name])
     on_side = {k for k, s in calls if k is not None and s}
     on_main = {k for k, s in calls if k is not None and not s}
     assert not on_main, sorted(on_main)
