@@ -42,7 +42,7 @@ def patched(Bb, call, tensors, parts=2):
     return orig(Bb, call2, tensors, parts)
 
 
-ops._two_stream_halves = patched
+ops._plans._two_stream_halves = patched   # (the submodule whose evaluation path calls it)
 net = ops.LinearLiftPlan(p, 8, 64, precision="w2")
 out = torch.empty_like(x)
 ref = None
