@@ -90,7 +90,7 @@ def module_act(m) -> tuple[int, Tensor | None]:
     raise NotImplementedError(f"activation {type(m).__name__} has no HIP epilogue (GaussianActivation, nn.ReLU, nn.Identity do)")
 
 
-MAX_GEOMETRY_DIM = 16   # GECCO_MAX_GEOMETRY_DIM: the 16-lane row group of the lowering kernels, one lane per output
+MAX_GEOMETRY_DIM = _lib.CONSTANTS["GECCO_MAX_GEOMETRY_DIM"]   # 16: the 16-lane row group of the lowering kernels, one lane per output
 
 
 def check_geometry_dim(G: int) -> None:

@@ -150,8 +150,8 @@ def scipy_emd(p1: Tensor, p2: Tensor, match: str = "l1", average: str = "l1") ->
     return res[0] if single else res
 
 
-EMD_MAX_POINTS = 2048    # GECCO_EMD_MAX_POINTS: both clouds and the solver state of a pair stay in one CU's LDS
-EMD_Q = 24               # GECCO_EMD_Q: match costs are quantised to 2^-Q of the pair's cost bound c_max
+EMD_MAX_POINTS = _lib.CONSTANTS["GECCO_EMD_MAX_POINTS"]   # both clouds and the solver state of a pair stay in one CU's LDS
+EMD_Q = _lib.CONSTANTS["GECCO_EMD_Q"]                     # match costs are quantised to 2^-Q of the pair's cost bound c_max
 _SQUARED = {"l1": False, "l2": True}
 
 
@@ -262,7 +262,7 @@ def sinkhorn_emd(p1: Tensor, p2: Tensor, epsilon: float = 0.01, iterations: int 
     return out[0] if single else out
 
 
-SINKHORN_RESIDENT_MAX_POINTS = 7768   # GECCO_SINKHORN_RESIDENT_MAX_POINTS: N + M of a pair whose clouds and potentials fit one CU's LDS
+SINKHORN_RESIDENT_MAX_POINTS = _lib.CONSTANTS["GECCO_SINKHORN_RESIDENT_MAX_POINTS"]   # N + M of a pair whose clouds and potentials fit one CU's LDS
 _SINKHORN_FORMS = {None: 0, "resident": 1, "streaming": 2}
 
 

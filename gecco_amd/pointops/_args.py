@@ -15,10 +15,10 @@ from torch import Tensor
 from .. import _lib
 from ..hip_ops import _ptr
 
-KNN_MAX_K = 64                   # GECCO_KNN_MAX_K
-KNN_SPLIT_SLICE = 4096           # GECCO_KNN_SPLIT_SLICE: reference points per slice of the split form
+KNN_MAX_K = _lib.CONSTANTS["GECCO_KNN_MAX_K"]
+KNN_SPLIT_SLICE = _lib.CONSTANTS["GECCO_KNN_SPLIT_SLICE"]   # reference points per slice of the split form
 _KNN_FORMS = {None: 0, "direct": 1, "split": 2}
-VOXEL_MAX_POINTS = 1 << 30       # GECCO_VOXEL_MAX_POINTS
+VOXEL_MAX_POINTS = _lib.CONSTANTS["GECCO_VOXEL_MAX_POINTS"]
 
 
 def _cloud(points: Tensor):

@@ -47,7 +47,7 @@ from ..hip_ops import _stream
 from ._args import VOXEL_MAX_POINTS, _cloud, _f32, _integer, _integer_tensor, _not_empty, _radius_f32, _unbatch, _vp
 from .radius import GridIndex, _grid_for
 
-DBSCAN_MAX_ROUNDS = 64            # GECCO_DBSCAN_MAX_ROUNDS
+DBSCAN_MAX_ROUNDS = _lib.CONSTANTS["GECCO_DBSCAN_MAX_ROUNDS"]
 
 
 class DBSCANResult(NamedTuple):

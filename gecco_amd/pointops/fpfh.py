@@ -77,8 +77,8 @@ from ._args import (_KNN_FORMS, VOXEL_MAX_POINTS, _check_form, _cloud, _cloud_li
 from .knn import _knn
 from .radius import GridIndex, _grid_for
 
-FPFH_BINS = 33                   # GECCO_FPFH_BINS
-FEATURE_MAX_DIM = 64             # GECCO_FEATURE_MAX_DIM
+FPFH_BINS = _lib.CONSTANTS["GECCO_FPFH_BINS"]
+FEATURE_MAX_DIM = _lib.CONSTANTS["GECCO_FEATURE_MAX_DIM"]
 
 
 def fpfh(points: Tensor, normals: Tensor, k: int = 16, radius: float | None = None, idx: Tensor | None = None, return_spfh: bool = False,

@@ -23,8 +23,8 @@ from .. import _lib
 from ..hip_ops import _ptr, _stream
 from ._args import _cloud, _f32, _not_empty, _results, _sqrt, _vp
 
-FPS_RESIDENT_MAX_POINTS = 8192   # GECCO_FPS_RESIDENT_MAX_POINTS: 1024 threads * 8 points in registers
-_FPS_STREAM_SLICE = 1024         # GECCO_FPS_STREAM_SLICE: points per workgroup of the streaming form
+FPS_RESIDENT_MAX_POINTS = _lib.CONSTANTS["GECCO_FPS_RESIDENT_MAX_POINTS"]   # 8192: 1024 threads * 8 points in registers
+_FPS_STREAM_SLICE = _lib.CONSTANTS["GECCO_FPS_STREAM_SLICE"]                 # points per workgroup of the streaming form
 _FPS_FORMS = {None: 0, "resident": 1, "streaming": 2}
 
 

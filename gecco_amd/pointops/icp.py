@@ -43,8 +43,8 @@ from ..hip_ops import _stream
 from ._args import (_KNN_FORMS, _check_form, _cloud, _cloud_like, _f32, _knn_slices, _long, _on_device, _pair_sizes, _per_cloud,
                     _positive_f32, _same_batching, _unbatch, _vp)
 
-ICP_MAX_ITERATIONS = 1000        # GECCO_ICP_MAX_ITERATIONS
-_ICP_STATE_BYTES = 160           # GECCO_ICP_STATE_BYTES
+ICP_MAX_ITERATIONS = _lib.CONSTANTS["GECCO_ICP_MAX_ITERATIONS"]
+_ICP_STATE_BYTES = _lib.CONSTANTS["GECCO_ICP_STATE_BYTES"]
 _ICP_METHODS = {"point_to_point": 0, "point_to_plane": 1}
 
 

@@ -52,9 +52,9 @@ from ..hip_ops import _stream
 from ._args import (_candidates_or_count, _cloud, _f32, _integer, _not_empty, _number, _on_device, _per_cloud, _positive_f32,
                     _refits_and_seed, _unbatch, _vp)
 
-PLANE_MAX_HYPOTHESES = 1 << 24   # GECCO_PLANE_RANSAC_MAX_HYPOTHESES
-PLANE_MAX_REFINE = 8             # GECCO_PLANE_RANSAC_MAX_REFINE
-_PLANE_BLOCK_HYPOTHESES = 1024   # GECCO_PLANE_RANSAC_BLOCK_HYPOTHESES
+PLANE_MAX_HYPOTHESES = _lib.CONSTANTS["GECCO_PLANE_RANSAC_MAX_HYPOTHESES"]
+PLANE_MAX_REFINE = _lib.CONSTANTS["GECCO_PLANE_RANSAC_MAX_REFINE"]
+_PLANE_BLOCK_HYPOTHESES = _lib.CONSTANTS["GECCO_PLANE_RANSAC_BLOCK_HYPOTHESES"]
 
 
 class PlaneResult(NamedTuple):

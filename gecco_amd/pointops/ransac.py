@@ -48,9 +48,9 @@ from ..hip_ops import _stream
 from ._args import (_candidates_or_count, _cloud, _f32, _integer_tensor, _long, _number, _on_device, _pair_sizes, _positive_f32,
                     _refits_and_seed, _same_batching, _unbatch, _vp)
 
-RANSAC_MAX_HYPOTHESES = 1 << 24  # GECCO_RANSAC_MAX_HYPOTHESES
-RANSAC_MAX_REFINE = 8            # GECCO_RANSAC_MAX_REFINE
-_RANSAC_BLOCK_HYPOTHESES = 1024  # GECCO_RANSAC_BLOCK_HYPOTHESES
+RANSAC_MAX_HYPOTHESES = _lib.CONSTANTS["GECCO_RANSAC_MAX_HYPOTHESES"]
+RANSAC_MAX_REFINE = _lib.CONSTANTS["GECCO_RANSAC_MAX_REFINE"]
+_RANSAC_BLOCK_HYPOTHESES = _lib.CONSTANTS["GECCO_RANSAC_BLOCK_HYPOTHESES"]
 
 
 class RANSACResult(NamedTuple):
