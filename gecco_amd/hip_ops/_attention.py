@@ -39,11 +39,11 @@ def pool_attn_f16in(KV16: Tensor, inducers: Tensor, H: int, head_major: bool = F
     return merged
 
 
-def unpool_attn(q: Tensor, kvh: Tensor, H: int, precision: str = "fp32") -> Tensor:
+def unpool_attn(q: Tensor, kvh: Tensor, H: int, precision: str = "fp32", out: Tensor | None = None) -> Tensor:
     pr = PRECISIONS[precision]
     B, N, Cc = q.shape
     I = kvh.shape[1]
-    out = torch.empty_like(q)
+    out = torch.empty_like(q) if out is None else out
     _launch("gecco_unpool_attn_ex_f32", _ptr(q), _ptr(kvh), _ptr(out), B, N, Cc, H, I, pr)
     return out
 

@@ -7,6 +7,7 @@ THIS call: the stale bits are the right bits.  These helpers put NaN where a cor
   poison_free_memory()   the caching allocator's free blocks (both pools) hold NaN, so every later `torch.empty` returns NaN bytes
   poison_workspaces(x)   the workspace caches of a plan (or of every plan a module has built) hold NaN
   poisoned_out(like)     a NaN-filled destination for `out=`
+  guarded(*shape)        a NaN-filled fp32 destination with GUARD NaN floats behind it; check_guard finds a store past its end
 
 The fill is 0xFF bytes: a quiet NaN read as fp32, fp16, bf16 and either fp8 format.  State that is meant to persist is never
 touched: the weight-gradient ticket counters (`autograd/_linear.py: _tn_counters`, zeroed once and left zero by every launch), the step's
@@ -86,6 +87,23 @@ def poison_workspaces(obj) -> int:
 def poisoned_out(like: torch.Tensor) -> torch.Tensor:
     """A destination shaped like `like`, every byte 0xFF (NaN)."""
     return fill_poison(torch.empty_like(like, memory_format=torch.contiguous_format))
+
+
+GUARD = 4096           # NaN floats behind every destination: a store past its end shows up there (and lands in our own memory)
+
+
+def guarded(*shape):
+    """A NaN-filled destination of `shape` with GUARD NaN floats behind it: (the view, the whole buffer)."""
+    n = 1
+    for s in shape:
+        n *= int(s)
+    buf = fill_poison(torch.empty(n + GUARD, device="cuda"))
+    return buf[:n].view(*shape), buf
+
+
+def check_guard(buf, n, what):
+    tail = bits(buf[n:])
+    assert bool((tail == -1).all()), f"{what}: {int((tail != -1).sum())} floats written past the end"
 
 
 def bits(t: torch.Tensor) -> torch.Tensor:

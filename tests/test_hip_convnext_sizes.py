@@ -13,7 +13,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import cases, cpu_ref
-from tests._poison import bits, fill_poison, poison_free_memory
+from tests._poison import GUARD, bits, fill_poison, poison_free_memory
+from tests._poison import check_guard as _check_guard, guarded as _guarded
 from tests.test_hip_convnext import _seeded_state
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +33,6 @@ FWD_BARS = {"fp32": 2e-5, "bf16x3": 2e-4}
 GRAD_BARS = {"fp32": 1e-4, "bf16x3": 1e-3}
 COND_BARS = {"fp32": 1e-4, "bf16x3": 5e-4, "mixed": 5e-4, "w2": 1e-3}
 KERNEL_BAR = 1e-5      # single kernels against float64: tighter than the fp32 conditioner's 2e-5
-GUARD = 4096           # NaN floats behind every destination: a store past its end shows up there (and lands in our own memory)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -167,18 +167,6 @@ def _call(name, *args):
     conv = [_ptr(a) if (a is None or isinstance(a, torch.Tensor)) else a for a in args]
     L.check(getattr(L.load(), name)(*conv, _stream()), name)
     torch.cuda.synchronize()
-
-
-def _guarded(*shape):
-    """A NaN-filled destination of `shape` with GUARD NaN floats behind it: (the view, the whole buffer)."""
-    n = int(np.prod(shape))
-    buf = fill_poison(torch.empty(n + GUARD, device="cuda"))
-    return buf[:n].view(*shape), buf
-
-
-def _check_guard(buf, n, what):
-    tail = bits(buf[n:])
-    assert bool((tail == -1).all()), f"{what}: {int((tail != -1).sum())} floats written past the end"
 
 
 def _rand(rs, *shape, scale=1.0, shift=0.0):

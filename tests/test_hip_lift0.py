@@ -151,8 +151,10 @@ def _today(ops, c):
 
 
 # N = 4096 is the smallest point count at which pool_attn_nsplit (2048 keys per split) cuts the keys in two
-@pytest.mark.parametrize("N,sigmas,scale", [(128, SIGMAS, 1.0), (333, SIGMAS, 1.0), (4096, SIGMAS, 1.0), (333, (165.0, 165.0, 1.0), 8.0)],
-                         ids=["N128", "N333", "N4096-two-splits", "inducers-x8-sigma165"])
+# N = 4097: the second split ends in a tile of one key; N = 8200: four splits, the last one ragged
+@pytest.mark.parametrize("N,sigmas,scale", [(128, SIGMAS, 1.0), (333, SIGMAS, 1.0), (4096, SIGMAS, 1.0), (333, (165.0, 165.0, 1.0), 8.0),
+                                            (4097, SIGMAS, 1.0), (8200, SIGMAS, 1.0)],
+                         ids=["N128", "N333", "N4096-two-splits", "inducers-x8-sigma165", "N4097-ragged-split", "N8200-four-splits"])
 def test_pool_on_points_vs_float64(ops, N, sigmas, scale):
     """The merged, normalised pooled output against float64 attention over float64 K | V.  The yardstick is today's path on the same
     inputs: the new path's maximum error must not exceed it (it forms K, V and the scores in fp32 where today's path rounds K | V to

@@ -79,13 +79,16 @@ def test_cached_mode_golden(ops, golden_dir, precision, tol):
 @pytest.mark.parametrize("precision,tol", [("fp32", TOL), ("bf16x3", 2e-4), ("mixed", 2e-4), ("w2", 5e-4), ("fp16", 1e-3)])
 @pytest.mark.parametrize("B,N,d,L", [(3, 333, 128, 2), (2, 2048, 384, 1), (1, 4096, 512, 1), (2, 100, 64, 3), (2, 130, 256, 1),
                                      (2, 384, 384, 2), (1, 640, 512, 1), (3, 128, 256, 2), (2, 256, 64, 2), (2, 256, 192, 2), (1, 200, 320, 1),
-                                     (2, 2048, 128, 4)])   # the last: BASELINE config C1 (airplane: d = 128, 4 layers) at its true N
+                                     (2, 2048, 128, 4),    # BASELINE config C1 (airplane: d = 128, 4 layers) at its true N
+                                     (1, 8192, 256, 2), (1, 16384, 128, 2)])   # four and eight key splits (upsampled clouds)
 def test_uncond_vs_oracle_ragged(ops, B, N, d, L, precision, tol):
     """Sizes the golden set does not hold (ragged N, d=512, N=4096, head dim 8 that stays on the fp32 attention
     kernels, rows < 128; N = 128, 384, 640: an odd number of 128-row tiles under the 256-row tiles and the activation
     images; d = 64 at N = 256: head dim 8 on the fp32 attention kernels with the hidden-layer image at K = 128; d = 192, 320: head
     dims 24, 40), oracle computed on the fly, every arithmetic mode ("w2": the one-launch point MLP at d = 128, 256, 384, 512 with whole 128-row tiles, the
-    mixed mode's launches everywhere else)."""
+    mixed mode's launches everywhere else).  N = 8192, 16384: pool_attn_nsplit cuts the keys in four and in eight — the inducer chain's
+    own merge of the partials (inducer_chain_f16.hip, `switch (g.nsplit)`) in its cluster form (d = 256) and its one-block form
+    (d = 128), and layer 0's pool on the points (lift0) at four splits; whole 128-row tiles, as the mixed and w2 modes need."""
     from oracle import weights as W
     p = W.linear_lift_state_dict(77 + N, d, L, cases.I, cases.H)
     x, sigma = W.synthetic_cloud(N, B, N)
